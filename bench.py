@@ -14,10 +14,11 @@ data-path collective, only the end-of-rollout all_gather of the final state.
 
 Prints ONE JSON line (rank 0) with the driver contract fields plus
   "roofline":     HBM roofline of the step kernel (algorithmic bytes / time; bound "hbm" as north_star asks), with
-                  "flop" (algorithmic FLOPs counted on the CPU restatement vs the lanes the device issues) and
                   "issue_occupancy" (VALU issue slots taken -- what actually limits the kernel) beside it
-  "queue", "per_tick_launches": the queue launches of the window (count, waves, envs handed to the large kernel inside a
-                  launch) and the same ticks stepped as one launch per tick and env group
+  "queue":        the queue launches of the window (count, waves, envs handed to the large kernel inside a launch)
+A plain run times the headline solver's window and nothing else.  --full adds every other measurement below (and
+"flop" in the roofline: algorithmic FLOPs counted on the CPU restatement vs the lanes the device issues):
+  "per_tick_launches": the same ticks stepped as one launch per tick and env group
   "default_regime": the same workload timed a second time in the same run over ticks 200..400 (arms on the table,
                   cubes knocked about: the heavy regime), whatever --steps / --warmup the headline window used
   "pgs":          the same two windows with north_star's PGS (<= 100 sweeps); the headline is the solver whose parity
@@ -27,6 +28,7 @@ Prints ONE JSON line (rank 0) with the driver contract fields plus
                   converged fraction and constraint high-water marks per phase, capacity promotions
   "cpu_baseline": the fp64 CPU oracle ("port" of the same pipeline, NOT MuJoCo) timed
                   on this host's cores on a bounded sample of the same workload.
+--dump-outputs DIR writes the final state of the headline window (what a caller of the rollout reads back) as .npy files.
 """
 from __future__ import annotations
 
@@ -434,9 +436,17 @@ def main():
                          "exceeds the GPU's wave slots, else one launch; 1 = one launch per tick and env group (rounds 1-5)")
     ap.add_argument("--solver", choices=["both", "PGS", "Newton"], default="both",
                     help="both (default): Newton is the headline line (MuJoCo's default, what the reference runs, and the "
-                         "path whose parity tests hold north_star's bar); north_star's PGS <= 100 sweeps is timed on the same "
-                         "start state and actions and printed beside it in `pgs` / `value_by_solver`")
+                         "path whose parity tests hold north_star's bar); with --full, north_star's PGS <= 100 sweeps is timed "
+                         "on the same start state and actions and printed beside it in `pgs` / `value_by_solver`")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement beside the headline window: PGS next to Newton, the per-tick launches, the "
+                         "default_regime window, the pick_place leg, the CPU baseline with counted FLOPs and the MuJoCo probe "
+                         "(each still subject to the --no-* options)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline window's final state (qpos, qvel as float64, status as float32) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -486,13 +496,16 @@ def main():
     total_env_steps = world * n_local * K * CONTROL_STEPS
     pmc = (F == 0 and n_local == ENVS_PER_GPU)   # (the committed counter passes describe the default cut)
 
-    K2, W2 = 200, 200   # the second window of every run: ticks 200 .. 400, the heavy regime
-    need = (W + K) if args.no_second_window else max(W + K, W2 + K2)
+    second_window = args.full and not args.no_second_window
+    K2, W2 = 200, 200   # the second window of every --full run: ticks 200 .. 400, the heavy regime
+    need = max(W + K, W2 + K2) if second_window else (W + K)
     if acts.shape[0] < need:
         acts2 = rng.random_actions(args.seed, env_ids, np.arange(need)).astype(np.float32)
         seq_all = torch.from_numpy(acts2).to(phys.device).contiguous()
     else:
         seq_all = seq
+
+    outputs = {}
 
     def run(solver):
         phys.set_solver(solver)
@@ -501,6 +514,10 @@ def main():
         phys.set_warmstart(ws0)
         phys.sync()
         elapsed, kern_ms, launches, gather_ms = timed_run(phys, seq, K, W, F, world, backend, dist, torch, n_local, dist_on)
+        if args.dump_outputs and not outputs:
+            # the headline window's result as its caller reads it back, before any other leg touches the state
+            qpos, qvel = phys.get_state_f64()
+            outputs.update(qpos=qpos, qvel=qvel, status=phys.status().astype(np.float32))
         q0 = timed_run.queue0
         status, stats = phys.status(), phys.solver_stats()
         fb = phys.fallback_stats()
@@ -545,7 +562,7 @@ def main():
         # the same start state and ticks stepped the old way -- one launch per tick and env group (rounds 1-5) -- beside
         # the headline: what the queue launches are worth, measured in this very run
         per_tick_leg = None
-        if queue and not args.no_second_window:
+        if queue and second_window:
             phys.reset()
             phys.set_state(qp0, qv0)
             phys.set_warmstart(ws0)
@@ -556,7 +573,7 @@ def main():
                                     "final states are bit-identical to the headline's (tests/test_gpu_properties.py)"}
         # the same start state again, timed over ticks 200 .. 400 (no gather, no counters: a second clock on the workload)
         second = None
-        if not args.no_second_window:
+        if second_window:
             phys.reset()
             phys.set_state(qp0, qv0)
             phys.set_warmstart(ws0)
@@ -603,9 +620,14 @@ def main():
                        "capacity_fallback": fb},
         }
 
-    order = ["Newton", "PGS"] if args.solver == "both" else [args.solver]
+    order = (["Newton", "PGS"] if args.full else ["Newton"]) if args.solver == "both" else [args.solver]
     runs = {s: run(s) for s in order}
     head = runs[order[0]]
+    if args.dump_outputs:
+        # one set per rank (its own global env ids): a multi-rank job writes <name>_rank<r>.npy
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ("" if world == 1 else f"_rank{rank}") + ".npy"), a)
     res = {
         "metric": baseline_metric(),
         "value": head["value"], "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -622,7 +644,7 @@ def main():
                                    "tasks/rearrangement.py:77-80 sets no solver)"),
                    "solver_note": "the headline is the solver whose parity tests hold north_star's bar (1e-4 on all 43 qpos "
                                   "coordinates over 1000 steps) as a hard assertion in 64 / 64 envs; north_star's PGS <= 100 sweeps "
-                                  "is timed on the same start state and actions in `pgs` (63 / 64: DESIGN.md section 7)",
+                                  "is timed on the same start state and actions in `pgs` with --full (63 / 64: DESIGN.md section 7)",
                    "integrator": "implicitfast"},
         "control_ticks_per_s": head["value"] / CONTROL_STEPS,
         "pick_place_macro_steps_per_s": head["value"] / 18000.0,
@@ -639,7 +661,7 @@ def main():
     for s_, key in (("PGS", "pgs"), ("Newton", "newton")):
         if s_ in runs and runs[s_] is not head:
             res[key] = runs[s_]
-    if rank == 0 and world == 1 and not args.no_pick_place:
+    if rank == 0 and world == 1 and args.full and not args.no_pick_place:
         phys.close()
         try:
             res["pick_place"] = pick_place_leg(n_local, local_rank, order[0])
@@ -658,7 +680,7 @@ def main():
                                                                                     "envs_done_after_the_pair")}
         except Exception as e:  # the headline line must still be printed
             res["pick_place"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(args.seed)
         flops = counted_flops(args.seed, [(W, W + K)] + ([] if args.no_second_window else [(W2, W2 + K2)]))
         res["cpu_baseline"]["counted_flops"] = flops

@@ -420,6 +420,33 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     assert abs(d["value"] - 2 * 4096 * 5 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
 
 
+def test_bench_plain_run_dumps_the_window_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: exactly K timed ticks of the
+    headline solver and nothing else, the contract fields of the line, and the window's final state written as .npy."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "env-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["headline_solver"] == "Newton"
+    assert abs(d["value"] - 4096 * 5 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    # the other measurements are --full's
+    assert d["cpu_baseline"] is None and d["default_regime"] is None and d["per_tick_launches"] is None
+    assert "pick_place" not in d and "pgs" not in d and list(d["value_by_solver"]) == ["Newton"]
+    q, v, st = (np.load(os.path.join(tmp_path, n + ".npy")) for n in ("qpos", "qvel", "status"))
+    assert q.shape == (4096, 43) and v.shape == (4096, 39) and st.shape == (4096,)
+    assert q.dtype == np.float64 and v.dtype == np.float64 and st.dtype == np.float32
+    assert np.isfinite(q).all() and np.isfinite(v).all() and ((st.astype(np.uint32) & 2) == 0).all()   # no MRE_ST_NAN
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)) <= 64 << 20
+
+
 def test_placement_failure_is_per_env(compiled_model):
     """PropPlacer raises _REJECTION_SAMPLING_FAILED for ITS env when a prop finds no collision-free pose within
     max_attempts_per_prop (environment/prop_initializer.py:230-233).  Batched: that env gets MRE_ST_PLACEMENT_FAILED

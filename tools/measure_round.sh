@@ -35,10 +35,10 @@ passes() {  # solver K W [pertick]   (pertick: the window is shorter than the li
 for P in $PARTS; do
   case $P in
     default)
-      python bench.py > $PROFILES_OUT/${T}_bench.json 2> $PROFILES_OUT/${T}_bench.err
+      python bench.py --full > $PROFILES_OUT/${T}_bench.json 2> $PROFILES_OUT/${T}_bench.err
       passes Newton 200 20; passes PGS 200 20 ;;
     s20w5)
-      python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-pick-place > $PROFILES_OUT/${T}_bench_s20w5.json 2>/dev/null
+      python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-pick-place > $PROFILES_OUT/${T}_bench_s20w5.json 2>/dev/null
       passes Newton 20 5 1; passes PGS 20 5 1 ;;
     pickplace)
       A="--pick-place-only --solver Newton"

@@ -1,9 +1,9 @@
 """What bounds a bench tick: per env group (= HIP stream) the launch durations and the gaps between consecutive
 launches, and how many of the groups' launches are in flight at a time -- from a rocprofv3 kernel trace.
 
-  rocprofv3 --kernel-trace --output-format csv -d gpurun_out/ktrace -- python bench.py --solver Newton --no-cpu-baseline
-  python tools/trace_summary.py gpurun_out/ktrace k_step_newton [warmup_launches_per_group=20]
-  python tools/trace_summary.py gpurun_out/ktrace k_step_queue_newton 1        (queue launches: bench.py's default cut)
+  rocprofv3 --kernel-trace --output-format csv -d TRACE_DIR -- python bench.py --full --solver Newton --no-cpu-baseline
+  python tools/trace_summary.py TRACE_DIR k_step_newton [warmup_launches_per_group=20]
+  python tools/trace_summary.py TRACE_DIR k_step_queue_newton 1        (queue launches: bench.py's default cut)
 
 A launch "starts" when its first workgroup gets a slot: with every slot of the GPU taken, the gap between two launches
 of one group is the wait for a slot, not host latency (the host enqueues a group's next launch before the running one
