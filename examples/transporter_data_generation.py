@@ -3,8 +3,9 @@
 (mujoco_robot_environments/transporter_network_data_generation.py:97-143) driving thousands of
 RearrangementEnv instances on one MI355X for ``dataset.max_steps`` pick / place pairs (config/dataset/default.yaml).
 Observations are zero images of the reference shapes, or the batched overhead camera's images with --render; with
---out the episodes of the first --log-envs envs are written as RLDS / TFDS shards (mujoco_robot_environments_amd/
-dataset.py) in place of envlogger's TFDSBackendWriter.
+--out the episodes of the first --log-envs envs (-1: all of them) are written as RLDS / TFDS shards
+(mujoco_robot_environments_amd/dataset.py) in place of envlogger's TFDSBackendWriter; with --render the frames are
+encoded on the device (csrc/mre_records.hip).
 
     python examples/transporter_data_generation.py --num-envs 8192 --render --out /tmp/shards
 """
@@ -31,7 +32,7 @@ def main():
     ap.add_argument("--render", action="store_true", help="overhead-camera observations (depth + RGB, CUDA tensors) instead of zero images")
     ap.add_argument("--out", default=None, help="write the episodes as RLDS shards (TFRecord, the reference ds_config's feature "
                     "keys: mujoco_robot_environments_amd/dataset.py) into this directory")
-    ap.add_argument("--log-envs", type=int, default=64, help="with --out: episodes of the first K envs are written")
+    ap.add_argument("--log-envs", type=int, default=64, help="with --out: episodes of the first K envs are written (-1: all envs)")
     ap.add_argument("--solver", choices=["Newton", "PGS"], default="Newton", help="constraint solver (the reference's MuJoCo runs Newton)")
     args = ap.parse_args()
     cfg = colour_separator_task_config()
@@ -54,7 +55,7 @@ def main():
         from mujoco_robot_environments_amd.dataset import BatchedEpisodeLogger, EpisodeWriter
         writer = EpisodeWriter(args.out, f"{cfg.get('name', 'colour_splitter')}", env.overhead_camera_height, env.overhead_camera_width,
                                max_episodes_per_file=cfg.dataset.max_episodes_per_file)
-        mask = np.arange(args.num_envs) < args.log_envs
+        mask = np.arange(args.num_envs) < (args.num_envs if args.log_envs < 0 else args.log_envs)
         logger = BatchedEpisodeLogger(env, writer, mask)
         logger.reset(ts)
     print(f"reset: {time.time() - t0:.1f} s; placement failed in {int(env.placement_failed.sum())} envs, "
@@ -103,18 +104,23 @@ def main():
               f"sorted so far {int((~still).sum())}/{args.num_envs}; "
               f"{args.num_envs * (step + 1) * nsim / (time.time() - t0):.3g} env-steps/s so far "
               f"(reset, camera{', shard logging' if logger else ''} included)", flush=True)
+    log_rate = ""
     if logger:
         t1 = time.time()
         logger.flush()
-        print("episode shards:", writer.close())
+        info = writer.close()
+        print("episode shards:", info)
         t_log += time.time() - t1
+        gb = int(info["splits"][0]["numBytes"]) / 1e9
+        log_rate = (f" = {gb:.2f} GB of {int(mask.sum())} envs at {gb / max(t_log, 1e-9):.2f} GB/s, "
+                    f"{logger.frames_encoded_on_device} frames encoded on the device")
     done = ~env.sort_colours(peek=True)[0]
     n_pairs = len(episodes)
     print(f"{int(done.sum())}/{args.num_envs} envs have every cube in its colour's target after {n_pairs} pairs "
           f"({int((done & alive).sum())} of them with every phase converged -- the episodes the reference's loop would keep); "
           f"steps per env episode: min {int(steps_logged.min())} median {int(np.median(steps_logged))} max {int(steps_logged.max())}; "
           f"intrinsics fx={metadata['intrinsics']['fx']:.1f}; wall {time.time() - t0:.1f} s "
-          f"(step() incl. camera {t_phys:.1f} s, logging + shards {t_log:.1f} s); "
+          f"(step() incl. camera {t_phys:.1f} s, logging + shards {t_log:.1f} s{log_rate}); "
           f"{args.num_envs * n_pairs * 18000 / max(t_phys, 1e-9):.3g} env-steps/s inside step()")
     env.close()
 

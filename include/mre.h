@@ -268,6 +268,33 @@ int mre_wait_stream(mre_env*, void* stream);
  * (transporter_network_data_generation.py:103-111; mujoco_robot_environments_amd/dataset.py) */
 uint32_t mre_crc32c(const void* data, size_t nbytes);
 
+/* Episode records on the device (csrc/mre_records.hip): the two per-byte stages of the shard writer
+ * (dataset.py), for frames that are already in device memory.  Both calls read `rows` rows of row_bytes bytes (1 ..
+ * 2^30) from src [src_rows][row_stride]: row r is source row rows_idx[r] (device int32 [rows]; an index outside
+ * 0 .. src_rows - 1 is clamped, never followed) or source row r when rows_idx is NULL.  Everything is enqueued on
+ * `stream` (hipStream_t, NULL = the legacy default stream) of the current device; nothing synchronises.  All pointers
+ * but the stream are device pointers; workspace holds mre_records_workspace_bytes(rows, row_bytes) bytes (0 = bad
+ * arguments) and may be reused by the next call on the same stream.
+ *
+ * mre_varint_pack_rows: every byte as a protobuf varint (v < 128: one byte v; otherwise (v & 0x7f) | 0x80, then
+ * v >> 7) -- the packed int64_list TFDS stores a uint8 tensor as.
+ *   out   the packed rows, contiguous, in row order; out_capacity must cover the worst case 2 * rows * row_bytes
+ *         (MRE_ERR_ARG otherwise, nothing is launched).  NULL = sizing pass: only off and len are written.
+ *   off   int64 [rows] offset of each row in out (one call over 8192 frames of 480 x 640 x 3 emits up to 15 GB)
+ *   len   uint32 [rows] packed length of each row
+ *   crc   uint32 [rows] CRC-32C of each row's packed bytes, in the form mre_crc32c returns
+ * mre_crc32c_rows: crc [rows] = CRC-32C of each row's bytes as they are (a float32 frame is a packed float_list). */
+size_t mre_records_workspace_bytes(int rows, size_t row_bytes);
+int mre_varint_pack_rows(void* stream, const uint8_t* src, size_t row_stride, size_t row_bytes,
+                         const int32_t* rows_idx, int src_rows, int rows, uint8_t* out, size_t out_capacity,
+                         int64_t* off, uint32_t* len, uint32_t* crc, void* workspace, size_t workspace_bytes);
+int mre_crc32c_rows(void* stream, const uint8_t* src, size_t row_stride, size_t row_bytes,
+                    const int32_t* rows_idx, int src_rows, int rows, uint32_t* crc, void* workspace,
+                    size_t workspace_bytes);
+/* CRC-32C of A || B from the CRCs of A and B and the length of B (host arithmetic, no data is read):
+ * crc_a * x^(8 len_b) mod P xor crc_b over the reflected Castagnoli polynomial. */
+uint32_t mre_crc32c_combine(uint32_t crc_a, uint32_t crc_b, size_t len_b);
+
 #define MRE_SOLVER_PGS 0
 #define MRE_SOLVER_NEWTON 2
 int mre_set_solver(mre_env*, int solver);

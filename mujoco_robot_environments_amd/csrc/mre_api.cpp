@@ -15,6 +15,7 @@
 
 #include "../../include/mre.h"
 #include "mre_dev.h"
+#include "mre_records.h"
 
 using namespace mre;
 
@@ -1469,6 +1470,80 @@ extern "C" uint32_t mre_crc32c(const void* data, size_t n) {
   }
   while (n--) crc = T[0][(crc ^ *p++) & 0xFFu] ^ (crc >> 8);
   return crc ^ 0xFFFFFFFFu;
+}
+
+// ---- episode records on the device (csrc/mre_records.hip): packed varints and CRC-32C of byte rows
+extern "C" uint32_t mre_crc32c_combine(uint32_t crc_a, uint32_t crc_b, size_t len_b) {
+  return mre_rec_crc32c_combine(crc_a, crc_b, len_b);
+}
+
+static size_t rec_segments(size_t row_bytes) { return (row_bytes + REC_PACK_SEG - 1) / REC_PACK_SEG; }
+
+extern "C" size_t mre_records_workspace_bytes(int rows, size_t row_bytes) {
+  if (rows <= 0 || row_bytes == 0 || row_bytes > REC_MAX_ROW_BYTES) return 0;
+  return 2 * (size_t)rows * rec_segments(row_bytes) * sizeof(uint32_t);   // segment offsets + segment CRCs
+}
+
+// the checks the two calls share; fills the row interface of RecArgs (nseg for `seg` bytes per segment)
+static int rec_args(const char* who, RecArgs& a, const uint8_t* src, size_t row_stride, size_t row_bytes,
+                    const int32_t* rows_idx, int src_rows, int rows, void* workspace, size_t workspace_bytes, size_t seg) {
+  const std::string w(who);
+  if (!src || rows <= 0 || src_rows <= 0 || row_bytes == 0 || !workspace)
+    return fail(MRE_ERR_ARG, w + ": null argument or empty row set");
+  if (row_bytes > REC_MAX_ROW_BYTES) return fail(MRE_ERR_ARG, w + ": row_bytes above 2^30");
+  if (row_stride < row_bytes && src_rows > 1) return fail(MRE_ERR_ARG, w + ": row_stride below row_bytes");
+  if (!rows_idx && rows > src_rows) return fail(MRE_ERR_ARG, w + ": more rows than the source holds and no index list");
+  const size_t nseg = (row_bytes + seg - 1) / seg;
+  if ((size_t)rows * nseg > 0x7FFFFFFFull) return fail(MRE_ERR_ARG, w + ": rows x segments above 2^31 - 1");
+  if (workspace_bytes < mre_records_workspace_bytes(rows, row_bytes) || ((uintptr_t)workspace & 3))
+    return fail(MRE_ERR_ARG, w + ": workspace smaller than mre_records_workspace_bytes() or not 4-byte aligned");
+  if (!is_device_ptr(src) || !is_device_ptr(workspace) || (rows_idx && !is_device_ptr(rows_idx)))
+    return fail(MRE_ERR_ARG, w + ": src, rows_idx and workspace must be device pointers");
+  memset(&a, 0, sizeof(a));
+  a.src = src; a.stride = row_stride; a.row_bytes = (uint32_t)row_bytes; a.idx = rows_idx;
+  a.src_rows = (uint32_t)src_rows; a.rows = (uint32_t)rows; a.nseg = (uint32_t)nseg;
+  a.segoff = (uint32_t*)workspace;
+  a.segcrc = a.segoff + (size_t)rows * rec_segments(row_bytes);
+  return MRE_OK;
+}
+
+extern "C" int mre_varint_pack_rows(void* stream, const uint8_t* src, size_t row_stride, size_t row_bytes,
+                                    const int32_t* rows_idx, int src_rows, int rows, uint8_t* out, size_t out_capacity,
+                                    int64_t* off, uint32_t* len, uint32_t* crc, void* workspace, size_t workspace_bytes) {
+  RecArgs a;
+  int rc = rec_args("mre_varint_pack_rows", a, src, row_stride, row_bytes, rows_idx, src_rows, rows, workspace,
+                    workspace_bytes, REC_PACK_SEG);
+  if (rc) return rc;
+  if (!off || !len || !is_device_ptr(off) || !is_device_ptr(len) || ((uintptr_t)off & 7) || ((uintptr_t)len & 3))
+    return fail(MRE_ERR_ARG, "mre_varint_pack_rows: off / len must be aligned device pointers");
+  if (out) {
+    // the worst case, not the actual length: the length is only known on the device, and nothing may be written
+    // beyond the caller's buffer whatever the rows hold
+    if (out_capacity / 2 / (size_t)rows < row_bytes)
+      return fail(MRE_ERR_ARG, "mre_varint_pack_rows: out_capacity below the worst case 2 * rows * row_bytes");
+    if (!crc || !is_device_ptr(out) || !is_device_ptr(crc) || ((uintptr_t)crc & 3))
+      return fail(MRE_ERR_ARG, "mre_varint_pack_rows: out / crc must be device pointers (crc 4-byte aligned)");
+  }
+  a.out = out; a.off = (long long*)off; a.len = len; a.crc = crc;
+  mre_launch_varint_size(&a, (hipStream_t)stream);
+  if (out) mre_launch_varint_pack(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+extern "C" int mre_crc32c_rows(void* stream, const uint8_t* src, size_t row_stride, size_t row_bytes,
+                               const int32_t* rows_idx, int src_rows, int rows, uint32_t* crc, void* workspace,
+                               size_t workspace_bytes) {
+  RecArgs a;
+  int rc = rec_args("mre_crc32c_rows", a, src, row_stride, row_bytes, rows_idx, src_rows, rows, workspace,
+                    workspace_bytes, REC_CRC_SEG);
+  if (rc) return rc;
+  if (!crc || !is_device_ptr(crc) || ((uintptr_t)crc & 3))
+    return fail(MRE_ERR_ARG, "mre_crc32c_rows: crc must be a 4-byte aligned device pointer");
+  a.crc = crc;
+  mre_launch_crc32c_rows(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
 }
 
 extern "C" int mre_wait_stream(mre_env* e, void* stream) {

@@ -29,6 +29,12 @@ directory -- skips here and runs wherever tensorflow_datasets is importable):
 * ``dataset_info.json``: proto3 JSON of ``DatasetInfo`` (name, version 0.0.1 -- TFDSBackendWriter's default --,
   ``fileFormat``, one split with ``shardLengths`` / ``numBytes`` as strings and the standard ``filepathTemplate``).
 
+Where the per-byte work runs: ``BatchedEpisodeLogger`` looks at the observations it is handed.  CUDA tensors (env
+``render=True``) are encoded on the device -- the varints of the rgb frames and the CRC-32C of both images come from
+``records.py`` / csrc/mre_records.hip, and ``EpisodeWriter.write_encoded_episode`` frames the finished pieces without
+reading them again (the record's CRC is combined from the pieces' CRCs).  numpy observations take the host path below
+(``write_episode``), which is also what the device path is tested against, byte for byte.
+
 ``read_episodes`` parses a directory back BY ITS features.json (it is a generic reader of this format, not a mirror
 of the writer), and tests/test_dataset.py round-trips through it.
 """
@@ -100,9 +106,12 @@ def _native_crc():
     return _NATIVE
 
 
-def _masked_crc(data: bytes) -> int:
-    c = crc32c(data)
+def _mask(c: int) -> int:
     return ((((c >> 15) | (c << 17)) & 0xFFFFFFFF) + 0xA282EAD8) & 0xFFFFFFFF
+
+
+def _masked_crc(data: bytes) -> int:
+    return _mask(crc32c(data))
 
 
 def write_record(f, payload: bytes) -> None:
@@ -111,6 +120,31 @@ def write_record(f, payload: bytes) -> None:
     f.write(struct.pack("<I", _masked_crc(head)))
     f.write(payload)
     f.write(struct.pack("<I", _masked_crc(payload)))
+
+
+def crc32c_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """CRC-32C of A || B from crc32c(A), crc32c(B) and len(B) (mre_crc32c_combine of the C-ABI library: the record
+    CRC of an episode whose image pieces were checksummed elsewhere)."""
+    from . import lib as _lib
+    return int(_lib.lib().mre_crc32c_combine(int(crc_a) & 0xFFFFFFFF, int(crc_b) & 0xFFFFFFFF, int(len_b)))
+
+
+class EncodedLeaf:
+    """One step's share of a big feature, already in wire form: ``data`` (any buffer: bytes, numpy uint8 array) are the
+    bytes that go INSIDE the feature's packed list -- packed varints for an int64_list, little-endian float32 for a
+    float_list -- and ``crc`` is the CRC-32C of exactly those bytes."""
+    __slots__ = ("data", "crc", "nbytes")
+
+    def __init__(self, data, crc: int):
+        self.data, self.crc = data, int(crc) & 0xFFFFFFFF
+        self.nbytes = memoryview(data).nbytes
+
+    @classmethod
+    def from_host(cls, array: np.ndarray) -> "EncodedLeaf":
+        """The host encoding of one frame (what the device path must reproduce)."""
+        a = np.asarray(array)
+        data = a.astype("<f4").tobytes() if a.dtype.kind == "f" else _pack_varints(a)
+        return cls(data, crc32c(data))
 
 
 def read_records(path: str) -> Iterator[bytes]:
@@ -335,25 +369,16 @@ class EpisodeWriter:
         self._file = open(self._tmp_path(len(self._shards)), "wb")
         self._in_file = 0
 
-    def write_episode(self, steps: List[dict], metadata: dict) -> None:
-        """steps: RLDS steps, each {"observation": {...}, "action": {...} or None (last step), "reward",
-        "discount", "is_first", "is_last", "is_terminal"}."""
-        if self._file is None or self._in_file >= self.max_per_file:
-            self._roll()
+    RGB_KEY = "steps/observation/overhead_camera/rgb"
+    DEPTH_KEY = "steps/observation/overhead_camera/depth"
+
+    @staticmethod
+    def _small_features(steps: List[dict], metadata: dict) -> dict:
+        """Every feature of an episode but the two images."""
         T = len(steps)
         zero_act = {"pose": np.zeros(7), "pixel_coords": np.zeros(2, np.int64), "gripper_rot": 0.0}
         acts = [s.get("action") or zero_act for s in steps]
-        rgb, depth = [], []
-        for s in steps:
-            o = s["observation"]
-            r = np.asarray(o["overhead_camera/rgb"], np.uint8)
-            d = np.asarray(o["overhead_camera/depth"], np.float32)
-            assert r.shape == (self.h, self.w, 3) and d.shape == (self.h, self.w), (r.shape, d.shape)
-            rgb.append(r.reshape(-1))
-            depth.append(d.reshape(-1))
         feats = {
-            "steps/observation/overhead_camera/rgb": np.concatenate(rgb) if rgb else np.zeros(0, np.uint8),
-            "steps/observation/overhead_camera/depth": np.concatenate(depth) if depth else np.zeros(0, np.float32),
             "steps/action/pose": np.concatenate([np.asarray(a["pose"], np.float64).reshape(7) for a in acts]),
             "steps/action/pixel_coords": np.concatenate([np.asarray(a["pixel_coords"], np.int64).reshape(2) for a in acts]),
             "steps/action/gripper_rot": np.asarray([float(a["gripper_rot"]) for a in acts]),
@@ -366,9 +391,82 @@ class EpisodeWriter:
         for grp in ("intrinsics", "extrinsics"):       # episode_metadata_info entries: top-level features
             for k, v in metadata[grp].items():
                 feats[f"{grp}/{k}"] = np.asarray([float(v)])
+        return feats
+
+    def write_episode(self, steps: List[dict], metadata: dict) -> None:
+        """steps: RLDS steps, each {"observation": {...}, "action": {...} or None (last step), "reward",
+        "discount", "is_first", "is_last", "is_terminal"}."""
+        if self._file is None or self._in_file >= self.max_per_file:
+            self._roll()
+        rgb, depth = [], []
+        for s in steps:
+            o = s["observation"]
+            r = np.asarray(o["overhead_camera/rgb"], np.uint8)
+            d = np.asarray(o["overhead_camera/depth"], np.float32)
+            assert r.shape == (self.h, self.w, 3) and d.shape == (self.h, self.w), (r.shape, d.shape)
+            rgb.append(r.reshape(-1))
+            depth.append(d.reshape(-1))
+        feats = self._small_features(steps, metadata)
+        feats[self.RGB_KEY] = np.concatenate(rgb) if rgb else np.zeros(0, np.uint8)
+        feats[self.DEPTH_KEY] = np.concatenate(depth) if depth else np.zeros(0, np.float32)
         payload = encode_example(feats)
         write_record(self._file, payload)
         self._bytes += len(payload)
+        self._in_file += 1
+        self._episodes += 1
+
+    def write_encoded_episode(self, steps: List[dict], metadata: dict) -> None:
+        """``write_episode`` for steps whose two images are ``EncodedLeaf`` pieces (observation: {"overhead_camera/rgb":
+        packed varints of the frame, "overhead_camera/depth": its float32 bytes}), and the same bytes in the file.  The
+        small features are encoded here as usual; the Example's framing around the images is built from the pieces'
+        LENGTHS, the record's CRC from their CRCs (``crc32c_combine``), and the pieces go to the file one after
+        another -- no megabyte is read or copied on the way."""
+        if self._file is None or self._in_file >= self.max_per_file:
+            self._roll()
+        small = self._small_features(steps, metadata)
+        big = {self.RGB_KEY: (3, [s["observation"]["overhead_camera/rgb"] for s in steps]),      # int64_list
+               self.DEPTH_KEY: (2, [s["observation"]["overhead_camera/depth"] for s in steps])}  # float_list
+        assert all(p.nbytes == 4 * self.h * self.w for p in big[self.DEPTH_KEY][1]), "depth piece: H * W float32"
+
+        def head(field: int, n: int) -> bytes:    # what _ld(field, payload of n bytes) puts in front of the payload
+            return _varint((field << 3) | 2) + _varint(n)
+
+        # the map entries in key order, as encode_example lays them out; parts = [bytes | EncodedLeaf]
+        parts: list = []
+        for k in sorted(list(small) + list(big)):
+            key = _ld(1, k.encode())
+            if k in small:
+                parts.append(_ld(1, key + _ld(2, _feature(small[k]))))
+                continue
+            kind, pieces = big[k]
+            n = sum(p.nbytes for p in pieces)
+            h_list = head(1, n)                          # <kind>_list.value, packed
+            h_kind = head(kind, len(h_list) + n)         # Feature.<kind>_list
+            h_feat = head(2, len(h_kind) + len(h_list) + n)      # map entry: value
+            n_entry = len(key) + len(h_feat) + len(h_kind) + len(h_list) + n
+            parts.append(head(1, n_entry) + key + h_feat + h_kind + h_list)
+            parts.extend(pieces)
+        total = sum(len(p) if isinstance(p, bytes) else p.nbytes for p in parts)
+        parts.insert(0, head(1, total))                  # Example.features
+        merged: list = []                                # neighbouring small parts as one
+        for p in parts:
+            if isinstance(p, bytes) and merged and isinstance(merged[-1], bytes):
+                merged[-1] += p
+            else:
+                merged.append(p)
+        n_payload, crc = 0, 0
+        for p in merged:
+            c, n = (crc32c(p), len(p)) if isinstance(p, bytes) else (p.crc, p.nbytes)
+            crc = crc32c_combine(crc, c, n)
+            n_payload += n
+        f = self._file
+        lead = struct.pack("<Q", n_payload)
+        f.write(lead)
+        f.write(struct.pack("<I", _masked_crc(lead)))
+        for p in merged:
+            f.write(p if isinstance(p, bytes) else p.data)
+        f.write(struct.pack("<I", _mask(crc)))
+        self._bytes += n_payload
         self._in_file += 1
         self._episodes += 1
 
@@ -448,16 +546,65 @@ def read_episodes(data_directory: str, name: Optional[str] = None, split_name: s
             raise ValueError(f"{p}: {count} records, dataset_info.json says {split['shardLengths'][k]}")
 
 
+class _HostArena:
+    """Host memory for the encoded frames of the device path: pinned blocks (a device-to-host copy into pinned memory
+    is asynchronous and runs at the link's rate), carved front to back -- torch's pinned allocator rounds every request
+    up to a power of two, so the blocks are asked for in such sizes and shared.  Falls back to pageable memory (the
+    copies then block) if the host refuses to pin."""
+
+    def __init__(self, block_bytes: int, pin: bool = True):
+        self.block_bytes, self.pin = int(block_bytes), bool(pin)
+        self._block, self._used = None, 0
+
+    def _empty(self, n: int):
+        import torch
+        if self.pin:
+            try:
+                return torch.empty(n, dtype=torch.uint8, pin_memory=True)
+            except RuntimeError:
+                self.pin = False
+        return torch.empty(n, dtype=torch.uint8)
+
+    def take(self, n: int):
+        """A uint8 host tensor of n bytes."""
+        if n > self.block_bytes:
+            return self._empty(n)
+        if self._block is None or self._used + n > self.block_bytes:
+            self._block, self._used = self._empty(self.block_bytes), 0
+        t = self._block[self._used:self._used + n]
+        self._used += (n + 63) & ~63
+        return t
+
+
 class BatchedEpisodeLogger:
     """The EnvLogger of the batched env: collects (observation, action) of every env step by step and
     writes one episode per env -- ``with BatchedEpisodeLogger(env, writer) as log: log.reset(ts);
-    log.step(action, ts)``.  Observations may be CUDA tensors (env render=True) or numpy arrays."""
+    log.step(action, ts)``.  Observations may be CUDA tensors (env render=True) or numpy arrays, and that decides
+    where the frames are encoded; the files are the same.
 
-    def __init__(self, env, writer: EpisodeWriter, env_mask: Optional[np.ndarray] = None):
+    CUDA observations: the logged, active rows are encoded on the device (records.py: varints + CRC-32C of the rgb
+    frames, CRC-32C of the depth frames) in chunks of envs that keep the device staging at ``staging_bytes`` whatever
+    N x T is, and come back as a few large asynchronous copies -- one synchronise per logged step (for the packed
+    lengths; it also retires the previous step's copies), none per env.  ``frames_encoded_on_device`` counts them.
+    numpy observations: copied as they are and encoded by ``EpisodeWriter.write_episode`` on the host.
+
+    Either way the HOST holds every logged frame until ``flush()`` -- packed on the device path (1 .. 2 bytes per rgb
+    byte + 4 per depth pixel), raw on the host path -- because episodes are written in env order, which keeps the shards
+    comparable byte for byte.  Writing finished episodes early would bound that memory, and reorder the records."""
+
+    def __init__(self, env, writer: EpisodeWriter, env_mask: Optional[np.ndarray] = None,
+                 staging_bytes: int = 1 << 30, pin_host: bool = True, time_kernels: bool = False):
         self.env, self.writer = env, writer
         self.mask = np.ones(env.num_envs, bool) if env_mask is None else np.asarray(env_mask, bool)
         self._steps: List[List[dict]] = [[] for _ in range(env.num_envs)]
         self._meta = None
+        self.frames_encoded_on_device = 0
+        self.staging_bytes = int(staging_bytes)
+        self._arena = _HostArena(self.staging_bytes, pin_host)
+        self._staging = None      # device uint8 [staging_bytes], reused by every chunk of every step
+        self._in_flight: list = []   # device tensors that enqueued work still reads; dropped at the next synchronise
+        self._lazy: list = []     # (EncodedLeaf list, host int32 tensor of their CRCs): filled in once the copy landed
+        self._events = [] if time_kernels else None   # device events, in (start, end) pairs around the encode kernels
 
     def __enter__(self):
         return self
@@ -474,6 +621,95 @@ class BatchedEpisodeLogger:
         return {"overhead_camera/rgb": self._np(o["overhead_camera/rgb"][i]),
                 "overhead_camera/depth": self._np(o["overhead_camera/depth"][i])}
 
+    # ---------------------------------------------------------------- device path
+    @staticmethod
+    def _on_device(ts) -> bool:
+        return bool(getattr(ts.observation["overhead_camera/rgb"], "is_cuda", False))
+
+    def _settle(self) -> None:
+        """After a synchronise: everything enqueued before it has landed."""
+        for leaves, crcs in self._lazy:
+            for leaf, c in zip(leaves, crcs.numpy().view(np.uint32)):
+                leaf.crc = int(c)
+        self._lazy, self._in_flight = [], []
+
+    def _encode_on_device(self, ts, rows: np.ndarray) -> List[dict]:
+        """Observations (EncodedLeaf pairs) of env rows[k] for every k.  The leaves' bytes and CRCs are valid after the
+        next synchronise of the stream (the next logged step's, or flush's)."""
+        import torch
+        from . import records as R
+        rgb, depth = ts.observation["overhead_camera/rgb"], ts.observation["overhead_camera/depth"]
+        n_src = int(rgb.shape[0])
+        rgb, depth = rgb.reshape(n_src, -1), depth.reshape(n_src, -1)
+        assert rgb.dtype == torch.uint8 and depth.dtype == torch.float32, (rgb.dtype, depth.dtype)
+        rb, db = int(rgb.shape[1]), 4 * int(depth.shape[1])
+        dev = rgb.device
+        with torch.cuda.device(dev):
+            idx = R.row_index(rows, n_src, dev)
+            self._stamp()
+            _, sizes = R.varint_size_rows(rgb, idx)
+            self._stamp()
+            sizes_h = sizes.cpu().numpy().astype(np.int64)    # the step's one synchronise
+            self._settle()
+            whole = rows.size == n_src                         # every env, in order: depth rows leave from where they are
+            if self._staging is None:
+                self._staging = torch.empty(self.staging_bytes, dtype=torch.uint8, device=dev)
+            per_row = 2 * rb + (0 if whole else db)
+            chunk = max(1, (self.staging_bytes - 16) // per_row)
+            if per_row + 16 > self._staging.numel():           # a single frame above the budget: its own buffer
+                self._staging = torch.empty(per_row + 16, dtype=torch.uint8, device=dev)
+            obs: List[dict] = []
+            for a in range(0, rows.size, chunk):
+                b = min(rows.size, a + chunk)
+                n = b - a
+                out = self._staging[:2 * n * rb]
+                self._stamp()
+                _, _, _, crc = R.varint_pack_rows(rgb, idx[a:b], out)
+                dcrc = R.crc32c_rows(depth, idx[a:b])
+                self._stamp()
+                if whole:
+                    dsrc = depth[a:b]
+                else:
+                    d0 = (2 * n * rb + 15) & ~15
+                    dsrc = self._staging[d0:d0 + n * db].view(torch.float32).view(n, -1)
+                    torch.index_select(depth, 0, idx[a:b], out=dsrc)
+                total = int(sizes_h[a:b].sum())
+                h_rgb, h_depth = self._arena.take(total), self._arena.take(n * db)
+                h_crc = self._arena.take(8 * n).view(torch.int32)
+                h_rgb.copy_(out[:total], non_blocking=True)
+                h_depth.view(torch.float32).view(n, -1).copy_(dsrc, non_blocking=True)
+                h_crc.copy_(torch.cat([crc, dcrc]), non_blocking=True)
+                np_rgb, np_depth = h_rgb.numpy(), h_depth.numpy()
+                ends = np.cumsum(sizes_h[a:b])
+                l_rgb = [EncodedLeaf(np_rgb[e - m:e], 0) for e, m in zip(ends, sizes_h[a:b])]
+                l_depth = [EncodedLeaf(np_depth[k * db:(k + 1) * db], 0) for k in range(n)]
+                self._lazy.append((l_rgb + l_depth, h_crc))
+                self._in_flight += [crc, dcrc, idx]
+                obs += [{"overhead_camera/rgb": r, "overhead_camera/depth": d} for r, d in zip(l_rgb, l_depth)]
+            self._in_flight += [rgb, depth]
+        self.frames_encoded_on_device += int(rows.size)
+        return obs
+
+    def _stamp(self) -> None:
+        if self._events is not None:
+            import torch
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            self._events.append(e)
+
+    def kernel_ms(self) -> float:
+        """Device time [ms] of the encode kernels so far (time_kernels=True): device events around the sizing pass of
+        every logged step and around the pack + CRC launches of every chunk; gathers and copies are outside."""
+        import torch
+        torch.cuda.synchronize()
+        ev = self._events or []
+        return float(sum(a.elapsed_time(b) for a, b in zip(ev[0::2], ev[1::2])))
+
+    def _observations(self, ts, rows: np.ndarray) -> List[dict]:
+        if rows.size and self._on_device(ts):
+            return self._encode_on_device(ts, rows)
+        return [self._obs(ts, i) for i in rows]
+
     def reset(self, ts) -> None:
         self._meta = self.env.get_camera_metadata()   # calibration_metadata on the FIRST step (:88-95)
         # an env whose reset() failed (PropPlacer found no pose: the reference's reset() raises and the loop drops the
@@ -481,8 +717,9 @@ class BatchedEpisodeLogger:
         failed = getattr(self.env, "placement_failed", None)
         if failed is not None:
             self.mask = self.mask & ~np.asarray(failed, bool)
-        for i in np.nonzero(self.mask)[0]:
-            self._steps[i] = [{"observation": self._obs(ts, i), "action": None, "reward": 0.0, "discount": 0.0,
+        rows = np.nonzero(self.mask)[0]
+        for i, o in zip(rows, self._observations(ts, rows)):
+            self._steps[i] = [{"observation": o, "action": None, "reward": 0.0, "discount": 0.0,
                                "is_first": True, "is_last": False, "is_terminal": False}]
 
     def step(self, action: dict, ts, active: Optional[np.ndarray] = None) -> None:
@@ -490,16 +727,30 @@ class BatchedEpisodeLogger:
         the next step."""
         act = self.mask if active is None else (self.mask & np.asarray(active, bool))
         pose, pix = np.asarray(action["pose"]), np.asarray(action["pixel_coords"])
-        for i in np.nonzero(act)[0]:
+        rows = np.nonzero(act)[0]
+        for i, o in zip(rows, self._observations(ts, rows)):
             self._steps[i][-1]["action"] = {"pose": pose[i], "pixel_coords": pix[i],
                                             "gripper_rot": float(np.broadcast_to(action["gripper_rot"], (self.env.num_envs,))[i])}
-            self._steps[i].append({"observation": self._obs(ts, i), "action": None, "reward": float(np.broadcast_to(ts.reward, (self.env.num_envs,))[i]),
+            self._steps[i].append({"observation": o, "action": None, "reward": float(np.broadcast_to(ts.reward, (self.env.num_envs,))[i]),
                                    "discount": float(np.broadcast_to(ts.discount, (self.env.num_envs,))[i]),
                                    "is_first": False, "is_last": False, "is_terminal": False})
 
     def flush(self) -> None:
+        if self._lazy or self._in_flight:
+            import torch
+            torch.cuda.synchronize()
+            self._settle()
         for i in np.nonzero(self.mask)[0]:
             if self._steps[i]:
                 self._steps[i][-1]["is_last"] = True
-                self.writer.write_episode(self._steps[i], self._meta)
+                obs = [s["observation"] for s in self._steps[i]]
+                if any(isinstance(v, EncodedLeaf) for o in obs for v in o.values()):
+                    for o in obs:     # an episode with both kinds of steps: the host ones are encoded here
+                        for name, v in o.items():
+                            if not isinstance(v, EncodedLeaf):
+                                o[name] = EncodedLeaf.from_host(v)
+                    self.writer.write_encoded_episode(self._steps[i], self._meta)
+                else:
+                    self.writer.write_episode(self._steps[i], self._meta)
                 self._steps[i] = []
+        self._arena = _HostArena(self._arena.block_bytes, self._arena.pin)

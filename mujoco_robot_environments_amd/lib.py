@@ -15,6 +15,10 @@ _SO = os.path.join(_CSRC, "libmre.so")
 _SOURCES = ["mre_kernels.hip", "mre_render.hip", "mre_api.cpp"]
 _HEADERS = ["mre_dev.h", "mre_math.h", "mre_collide.h", "mre_solver.h", "mre_newton.h", "mre_osc.h",
             os.path.join("..", "..", "include", "mre.h")]
+# Built and watched by needs_build(), but NOT hashed by source_hash(): the record kernels (varint packing, CRC-32C of
+# episode shards) launch nothing that bench.py times, and the hash names the step / camera sources that the committed
+# counter passes (profiles/*pmc_summary*.json) were taken on -- adding a unit beside them must not orphan those.
+_UNHASHED_SOURCES = ["mre_records.hip", "mre_records.h"]
 _LIB: Optional[C.CDLL] = None
 
 MRE_NQ, MRE_NV, MRE_NU, MRE_NQ_PAD, MRE_NV_PAD, MRE_MAX_PROPS = 43, 39, 8, 44, 40, 4
@@ -31,6 +35,7 @@ EXPORTS = [
     "mre_profile_enable", "mre_profile_read", "mre_set_env_id_offset", "mre_set_env_order",
     "mre_set_fallback", "mre_get_fallback_stats", "mre_get_queue_info", "mre_set_solver", "mre_get_solver", "mre_wait_stream", "mre_osc_compute", "mre_get_contacts", "mre_get_settle_steps", "mre_get_launch_info", "mre_prop_place", "mre_sort_colours", "mre_crc32c", "mre_osc_configure_env", "mre_set_env_ids", "mre_set_render_colours", "mre_render",
     "mre_get_state_f64", "mre_set_state_f64", "mre_get_time", "mre_pack_final_state",
+    "mre_records_workspace_bytes", "mre_varint_pack_rows", "mre_crc32c_rows", "mre_crc32c_combine",
 ]
 
 
@@ -55,7 +60,7 @@ def needs_build() -> bool:
     if not os.path.exists(_SO):
         return True
     t = os.path.getmtime(_SO)
-    for f in _SOURCES + _HEADERS:
+    for f in _SOURCES + _HEADERS + _UNHASHED_SOURCES:
         p = os.path.join(_CSRC, f)
         if os.path.exists(p) and os.path.getmtime(p) > t:
             return True
@@ -84,7 +89,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     units = [("kernels", "mre_kernels.hip", []), ("kernels_large", "mre_kernels.hip", ["-DMRE_LARGE_CAPS"]),
              ("kernels_newton", "mre_kernels.hip", ["-DMRE_NEWTON"]),
              ("kernels_large_newton", "mre_kernels.hip", ["-DMRE_LARGE_CAPS", "-DMRE_NEWTON"]),
-             ("render", "mre_render.hip", []), ("api", "mre_api.cpp", [])]
+             ("render", "mre_render.hip", []), ("records", "mre_records.hip", []), ("api", "mre_api.cpp", [])]
     procs = [(name, subprocess.Popen(base + flags + ["-c", os.path.join(_CSRC, src), "-o",
                                                      os.path.join(bdir, name + ".o")]))
              for name, src, flags in units]
@@ -162,8 +167,18 @@ def lib() -> C.CDLL:
     L.mre_osc_configure_env.argtypes = [vp, fp, fp, fp]
     L.mre_get_fallback_stats.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.mre_get_queue_info.argtypes = [vp, C.POINTER(C.c_longlong)]
+    sz = C.c_size_t
+    L.mre_crc32c.restype = C.c_uint32
+    L.mre_crc32c.argtypes = [C.c_char_p, sz]
+    L.mre_crc32c_combine.restype = C.c_uint32
+    L.mre_crc32c_combine.argtypes = [C.c_uint32, C.c_uint32, sz]
+    L.mre_records_workspace_bytes.restype = sz
+    L.mre_records_workspace_bytes.argtypes = [ci, sz]
+    L.mre_varint_pack_rows.argtypes = [vp, fp, sz, sz, fp, ci, ci, fp, sz, fp, fp, fp, fp, sz]
+    L.mre_crc32c_rows.argtypes = [vp, fp, sz, sz, fp, ci, ci, fp, fp, sz]
     for name in EXPORTS:
-        if name not in ("mre_last_error", "mre_stream", "mre_crc32c"):
+        if name not in ("mre_last_error", "mre_stream", "mre_crc32c", "mre_crc32c_combine",
+                        "mre_records_workspace_bytes"):
             getattr(L, name).restype = ci
     _LIB = L
     return L
