@@ -807,6 +807,198 @@ struct Blob {
 #define RI(name, dst, n) if (!b.ints(name, (int*)(dst), n)) return fail(MRE_ERR_MODEL, std::string("model entry ") + name)
 #define RF(name, dst, n) if (!b.flts(name, (float*)(dst), n)) return fail(MRE_ERR_MODEL, std::string("model entry ") + name)
 
+// The per-lane records of mre_dev.h (BodyRec .. OptRec): filled from the tables, then every field is compared with the
+// table entry it packs -- a record that disagrees with its table would change results silently.
+static bool same_bits(const void* a, const void* b, size_t n) { return memcmp(a, b, n) == 0; }
+static int pack_records(DevModel& m) {
+  if (m.ten_dof[0] == m.ten_dof[1] || m.ten_dof[0] < 0 || m.ten_dof[0] >= NRV || m.ten_dof[1] < 0 || m.ten_dof[1] >= NRV)
+    return fail(MRE_ERR_MODEL, "the gripper tendon must couple two different robot dofs");
+  for (int e = 0; e < NEQ; e++)
+    for (int k = 0; k < 2; k++)
+      if (m.eq_obj[e][k] < 1 || m.eq_obj[e][k] >= NRB) return fail(MRE_ERR_MODEL, "equality constraints must couple robot bodies");
+  if (m.tcp_site < 0 || m.tcp_site >= NSITE || m.eef_site < 0 || m.eef_site >= NSITE) return fail(MRE_ERR_MODEL, "tcp_site / eef_site name no site");
+  // (the phases take a finger body's place in the tree from its number: even bodies hang off the arm's last link, odd ones off the body below)
+  for (int b = 1; b < NRB; b++)
+    if (m.body_parent[b] != ROBOT_DOF_PARENT[b - 1] + 1) return fail(MRE_ERR_MODEL, "robot body tree differs from the one the kernels are unrolled for (mre_dev.h)");
+  for (int d = 0; d < NV; d++)
+    if (m.dof_body[d] != (d < NRV ? d + 1 : NRB + (d - NRV) / 6)) return fail(MRE_ERR_MODEL, "dof layout differs from the compiled kernels");
+  auto ten_of = [&](int d) { return d == m.ten_dof[0] ? 0 : (d == m.ten_dof[1] ? 1 : -1); };
+  for (int b = 0; b < NB; b++) {
+    BodyRec& r = m.body_rec[b];
+    memset(&r, 0, sizeof(r));
+    for (int c = 0; c < 4; c++) { r.quat[c] = m.body_quat[b][c]; r.iquat[c] = m.body_iquat[b][c]; }
+    for (int c = 0; c < 3; c++) { r.pos[c] = m.body_pos[b][c]; r.ipos[c] = m.body_ipos[b][c]; r.jnt_pos[c] = m.jnt_pos[b][c];
+                                  r.jnt_axis[c] = m.jnt_axis[b][c]; r.inertia[c] = m.body_inertia[b][c]; }
+    for (int c = 0; c < 2; c++) { r.jnt_range[c] = m.jnt_range[b][c]; r.invweight0[c] = m.body_invweight0[b][c]; }
+    r.mass = m.body_mass[b]; r.qposadr = m.body_qposadr[b]; r.dofadr = m.body_dofadr[b]; r.propid = m.body_propid[b];
+    r.qpos0 = (r.qposadr >= 0 && r.qposadr < NQ) ? m.qpos0[r.qposadr] : 0.f;
+    r.jnt_stiffness = m.jnt_stiffness[b]; r.jnt_springref = m.jnt_springref[b];
+    r.parent = m.body_parent[b]; r.jnt_limited = m.jnt_limited[b];
+  }
+  for (int d = 0; d < NV; d++) {
+    DofRec& r = m.dof_rec[d];
+    memset(&r, 0, sizeof(r));
+    const int b = m.dof_body[d];
+    if (b < 0 || b >= NB) return fail(MRE_ERR_MODEL, "dof_bodyid names a body that does not exist");
+    r.body = b; r.propid = m.body_propid[b]; r.dofadr = m.body_dofadr[b]; r.ten = ten_of(d);
+    r.armature = m.dof_armature[d]; r.damping = m.dof_damping[d]; r.invweight0 = m.dof_invweight0[d];
+    r.ten_coef = r.ten >= 0 ? m.ten_coef[r.ten] : 0.f;
+    r.jnt_stiffness = m.jnt_stiffness[b]; r.jnt_springref = m.jnt_springref[b];
+    if (d < 7) {   // arm actuator d drives dof d (checked in build_model)
+      r.act_gain = m.act_gain[d]; r.act_bias0 = m.act_bias[d][0]; r.act_bias1 = m.act_bias[d][1]; r.act_bias2 = m.act_bias[d][2];
+      r.act_ctrl_lo = m.act_ctrlrange[d][0]; r.act_ctrl_hi = m.act_ctrlrange[d][1];
+      r.act_force_lo = m.act_forcerange[d][0]; r.act_force_hi = m.act_forcerange[d][1];
+      r.act_forcelimited = m.act_forcelimited[d];
+    }
+  }
+  for (int e = 0; e < NMR; e++) {
+    MEntryRec& r = m.m_rec[e];
+    memset(&r, 0, sizeof(r));
+    r.i = m.M_i[e]; r.j = m.M_j[e];
+    r.armature = m.dof_armature[r.i]; r.damping = m.dof_damping[r.i];
+    r.act_bias2 = r.i < 7 ? m.act_bias[r.i][2] : 0.f;
+    r.ten = ten_of(r.i); r.ten_coef = r.ten >= 0 ? m.ten_coef[r.ten] : 0.f;
+  }
+  for (int k = 0; k < NROWREC; k++) memset(&m.row_rec[k], 0, sizeof(RowRec));
+  for (int e = 0; e < NEQ; e++) {
+    RowRec& r = m.row_rec[e];
+    const int b1 = m.eq_obj[e][0], b2 = m.eq_obj[e][1];
+    for (int c = 0; c < 2; c++) r.solref[c] = m.eq_solref[e][c];
+    for (int c = 0; c < 5; c++) r.solimp[c] = m.eq_solimp[e][c];
+    // (the kernels treat equalities 0 and 1 as the `connect` rows of the finger linkage, 2 as the joint coupling)
+    r.invw1 = e < 2 ? m.body_invweight0[b1][0] : m.dof_invweight0[b1 - 1];
+    r.invw2 = e < 2 ? m.body_invweight0[b2][0] : m.dof_invweight0[b2 - 1];
+    EqRec& q = m.eq_rec[e];
+    memset(&q, 0, sizeof(q));
+    q.type = m.eq_type[e]; q.b1 = b1; q.b2 = b2; q.pb1 = m.body_parent[b1]; q.pb2 = m.body_parent[b2];
+    q.root = b1;
+    while (q.root >= GRIP_BODY0) q.root = m.body_parent[q.root];
+    for (int c = 0; c < 8; c++) q.data[c] = m.eq_data[e][c];
+    q.qpos0_1 = m.qpos0[b1 - 1]; q.qpos0_2 = m.qpos0[b2 - 1];
+    q.root_chain_len = m.chain_len[q.root];
+    for (int c = 0; c < MAXCHAIN; c++) q.root_chain[c] = m.chain_dof[q.root][c];
+  }
+  for (int b = 1; b < NRB; b++) {
+    RowRec& r = m.row_rec[ROWREC_JNT + b];
+    for (int c = 0; c < 2; c++) r.solref[c] = m.jnt_solref[b][c];
+    for (int c = 0; c < 5; c++) r.solimp[c] = m.jnt_solimp[b][c];
+    r.invw1 = m.dof_invweight0[b - 1];
+  }
+  for (int k = 0; k < NPAIR; k++) {
+    if (m.pair_g1[k] < 0) continue;
+    RowRec& r = m.row_rec[ROWREC_PAIR + k];
+    const int b1 = m.pair_rec[k].b1, b2 = m.pair_rec[k].b2;
+    for (int c = 0; c < 2; c++) r.solref[c] = m.pair_solref[k][c];
+    for (int c = 0; c < 5; c++) r.solimp[c] = m.pair_solimp[k][c];
+    r.margin = m.pair_margin[k]; r.gap = m.pair_gap[k]; r.friction = m.pair_friction[k][0];
+    r.invw1 = (b1 > 0 && b1 < NRB) ? m.body_invweight0[b1][0] : 0.f;
+    r.invw2 = (b2 > 0 && b2 < NRB) ? m.body_invweight0[b2][0] : 0.f;
+  }
+  for (int k = 0; k < NSITE; k++) {
+    SiteRec& r = m.site_rec[k];
+    memset(&r, 0, sizeof(r));
+    if (m.site_body[k] < 0 || m.site_body[k] >= NB) return fail(MRE_ERR_MODEL, "site_bodyid names a body that does not exist");
+    r.body = m.site_body[k];
+    for (int c = 0; c < 3; c++) r.pos[c] = m.site_pos[k][c];
+    for (int c = 0; c < 4; c++) r.quat[c] = m.site_quat[k][c];
+  }
+  {
+    OptRec& o = m.opt_rec;
+    memset(&o, 0, sizeof(o));
+    o.timestep = m.timestep; o.impratio = m.impratio; o.tolerance = m.tolerance; o.iterations = m.iterations;
+    for (int c = 0; c < 3; c++) { o.gravity[c] = m.gravity[c]; o.grip_biasprm[c] = m.grip_biasprm[c]; }
+    o.cone = m.cone;
+    for (int c = 0; c < 2; c++) { o.ten_coef[c] = m.ten_coef[c]; o.ten_dof[c] = m.ten_dof[c]; o.grip_forcerange[c] = m.grip_forcerange[c];
+                                  o.grip_ctrlrange[c] = m.act_ctrlrange[NU - 1][c]; }
+    o.grip_gainprm = m.grip_gainprm; o.robot_mass = m.robot_mass; o.M0_diag_robot_sum = m.M0_diag_robot_sum;
+    o.tcp_site = m.tcp_site; o.eef_site = m.eef_site;
+    for (int c = 0; c < 3; c++) o.tcp_pos[c] = m.site_pos[m.tcp_site][c];
+  }
+
+  // ---- verification: every field against the table entry it packs (bit patterns: a NaN compares equal to itself)
+  bool ok = true;
+#define SAME(a, b) ok = ok && sizeof(a) == sizeof(b) && same_bits(&(a), &(b), sizeof(a))
+  for (int b = 0; b < NB && ok; b++) {
+    const BodyRec& r = m.body_rec[b];
+    SAME(r.quat, m.body_quat[b]); SAME(r.pos, m.body_pos[b]); SAME(r.mass, m.body_mass[b]); SAME(r.jnt_pos, m.jnt_pos[b]);
+    SAME(r.jnt_axis, m.jnt_axis[b]); SAME(r.qposadr, m.body_qposadr[b]); SAME(r.ipos, m.body_ipos[b]);
+    SAME(r.propid, m.body_propid[b]); SAME(r.iquat, m.body_iquat[b]); SAME(r.inertia, m.body_inertia[b]);
+    SAME(r.dofadr, m.body_dofadr[b]); SAME(r.jnt_range, m.jnt_range[b]); SAME(r.invweight0, m.body_invweight0[b]);
+    SAME(r.jnt_stiffness, m.jnt_stiffness[b]); SAME(r.jnt_springref, m.jnt_springref[b]); SAME(r.parent, m.body_parent[b]);
+    SAME(r.jnt_limited, m.jnt_limited[b]);
+    if (b >= 1) SAME(r.qpos0, m.qpos0[m.body_qposadr[b]]);
+  }
+  for (int d = 0; d < NV && ok; d++) {
+    const DofRec& r = m.dof_rec[d];
+    const int b = m.dof_body[d];
+    SAME(r.body, m.dof_body[d]); SAME(r.propid, m.body_propid[b]); SAME(r.dofadr, m.body_dofadr[b]);
+    ok = ok && r.ten == (d == m.ten_dof[0] ? 0 : (d == m.ten_dof[1] ? 1 : -1));
+    SAME(r.armature, m.dof_armature[d]); SAME(r.damping, m.dof_damping[d]); SAME(r.invweight0, m.dof_invweight0[d]);
+    if (r.ten >= 0) SAME(r.ten_coef, m.ten_coef[r.ten]);
+    SAME(r.jnt_stiffness, m.jnt_stiffness[b]); SAME(r.jnt_springref, m.jnt_springref[b]);
+    if (d < 7) {
+      SAME(r.act_gain, m.act_gain[d]); SAME(r.act_bias0, m.act_bias[d][0]); SAME(r.act_bias1, m.act_bias[d][1]);
+      SAME(r.act_bias2, m.act_bias[d][2]); SAME(r.act_ctrl_lo, m.act_ctrlrange[d][0]); SAME(r.act_ctrl_hi, m.act_ctrlrange[d][1]);
+      SAME(r.act_force_lo, m.act_forcerange[d][0]); SAME(r.act_force_hi, m.act_forcerange[d][1]);
+      SAME(r.act_forcelimited, m.act_forcelimited[d]);
+    }
+  }
+  for (int e = 0; e < NMR && ok; e++) {
+    const MEntryRec& r = m.m_rec[e];
+    SAME(r.i, m.M_i[e]); SAME(r.j, m.M_j[e]);
+    const int i = m.M_i[e];
+    SAME(r.armature, m.dof_armature[i]); SAME(r.damping, m.dof_damping[i]);
+    if (i < 7) SAME(r.act_bias2, m.act_bias[i][2]);
+    ok = ok && r.ten == (i == m.ten_dof[0] ? 0 : (i == m.ten_dof[1] ? 1 : -1));
+    if (r.ten >= 0) SAME(r.ten_coef, m.ten_coef[r.ten]);
+  }
+  for (int e = 0; e < NEQ && ok; e++) {
+    const RowRec& r = m.row_rec[e];
+    const EqRec& q = m.eq_rec[e];
+    const int b1 = m.eq_obj[e][0], b2 = m.eq_obj[e][1];
+    SAME(r.solref, m.eq_solref[e]); SAME(r.solimp, m.eq_solimp[e]);
+    if (e < 2) { SAME(r.invw1, m.body_invweight0[b1][0]); SAME(r.invw2, m.body_invweight0[b2][0]); }
+    else { SAME(r.invw1, m.dof_invweight0[b1 - 1]); SAME(r.invw2, m.dof_invweight0[b2 - 1]); }
+    SAME(q.type, m.eq_type[e]); SAME(q.b1, m.eq_obj[e][0]); SAME(q.b2, m.eq_obj[e][1]);
+    SAME(q.pb1, m.body_parent[b1]); SAME(q.pb2, m.body_parent[b2]); SAME(q.data, m.eq_data[e]);
+    SAME(q.qpos0_1, m.qpos0[b1 - 1]); SAME(q.qpos0_2, m.qpos0[b2 - 1]);
+    int root = b1;
+    while (root >= GRIP_BODY0) root = m.body_parent[root];
+    ok = ok && q.root == root;
+    SAME(q.root_chain_len, m.chain_len[root]);
+    for (int c = 0; c < MAXCHAIN; c++) SAME(q.root_chain[c], m.chain_dof[root][c]);
+  }
+  for (int b = 1; b < NRB && ok; b++) {
+    const RowRec& r = m.row_rec[ROWREC_JNT + b];
+    SAME(r.solref, m.jnt_solref[b]); SAME(r.solimp, m.jnt_solimp[b]); SAME(r.invw1, m.dof_invweight0[b - 1]);
+  }
+  for (int k = 0; k < NPAIR && ok; k++) {
+    if (m.pair_g1[k] < 0) continue;
+    const RowRec& r = m.row_rec[ROWREC_PAIR + k];
+    const int b1 = m.geom_body[m.pair_g1[k]], b2 = m.geom_body[m.pair_g2[k]];
+    SAME(r.solref, m.pair_solref[k]); SAME(r.solimp, m.pair_solimp[k]); SAME(r.margin, m.pair_margin[k]);
+    SAME(r.gap, m.pair_gap[k]); SAME(r.friction, m.pair_friction[k][0]);
+    if (b1 > 0 && b1 < NRB) SAME(r.invw1, m.body_invweight0[b1][0]);
+    if (b2 > 0 && b2 < NRB) SAME(r.invw2, m.body_invweight0[b2][0]);
+  }
+  for (int k = 0; k < NSITE && ok; k++) {
+    const SiteRec& r = m.site_rec[k];
+    SAME(r.body, m.site_body[k]); SAME(r.pos, m.site_pos[k]); SAME(r.quat, m.site_quat[k]);
+  }
+  {
+    const OptRec& o = m.opt_rec;
+    SAME(o.timestep, m.timestep); SAME(o.impratio, m.impratio); SAME(o.tolerance, m.tolerance); SAME(o.iterations, m.iterations);
+    SAME(o.gravity, m.gravity); SAME(o.cone, m.cone); SAME(o.ten_coef, m.ten_coef); SAME(o.ten_dof, m.ten_dof);
+    SAME(o.grip_gainprm, m.grip_gainprm); SAME(o.grip_biasprm, m.grip_biasprm); SAME(o.grip_forcerange, m.grip_forcerange);
+    SAME(o.grip_ctrlrange, m.act_ctrlrange[NU - 1]); SAME(o.robot_mass, m.robot_mass);
+    SAME(o.M0_diag_robot_sum, m.M0_diag_robot_sum); SAME(o.tcp_site, m.tcp_site); SAME(o.eef_site, m.eef_site);
+    SAME(o.tcp_pos, m.site_pos[m.tcp_site]);
+  }
+#undef SAME
+  if (!ok) return fail(MRE_ERR_MODEL, "a packed model record differs from the table it was filled from");
+  return MRE_OK;
+}
+
 static int build_model(const void* blob, size_t nbytes, DevModel& m) {
   if (nbytes < 16) return fail(MRE_ERR_MODEL, "blob too small");
   Blob b{(const unsigned char*)blob, nbytes};
@@ -990,7 +1182,7 @@ static int build_model(const void* blob, size_t nbytes, DevModel& m) {
   for (int p = 0; p < NPROP; p++) {  // same parking grid as the oracle's reset
     m.park_pos[p][0] = 2.0f + 0.5f * p; m.park_pos[p][1] = 2.0f; m.park_pos[p][2] = -5.0f;
   }
-  return MRE_OK;
+  return pack_records(m);
 }
 
 // ------------------------------------------------------------------- lifecycle

@@ -112,6 +112,74 @@ struct alignas(16) PairRec {
 };
 static_assert(sizeof(PairRec) == 128, "PairRec is eight 16-byte words");
 
+// The same treatment for the rest of the step (round 6).  A phase used to fetch its model constants where it used
+// them: one dword, waited for at once, and often the index of the next one (dof -> body -> prop id; matrix entry -> dof
+// -> damping -> actuator bias) -- some 95 separate trips to memory per step outside the solver, at two waves per SIMD.
+// The records below hold, per lane, what a phase reads for its own body / dof / matrix entry / constraint row, so that
+// it costs ONE group of independent 16-byte loads issued at the phase's entry.  They carry the very float32 / int
+// values of the tables above them (mre_create fills them from the tables and compares every field afterwards), and the
+// kernels apply the same operations in the same order: results do not change by a bit.  The tables stay: the host, the
+// exports and the zero-step paths read them.
+struct alignas(16) BodyRec {   // lane = body
+  float quat[4];
+  float pos[3], mass;
+  float jnt_pos[3], qpos0;          // qpos0[qposadr]
+  float jnt_axis[3]; int qposadr;
+  float ipos[3]; int propid;
+  float iquat[4];
+  float inertia[3]; int dofadr;
+  float jnt_range[2], invweight0[2];
+  float jnt_stiffness, jnt_springref; int parent, jnt_limited;
+};
+static_assert(sizeof(BodyRec) == 144, "BodyRec is nine 16-byte words");
+struct alignas(16) DofRec {    // lane = dof
+  int body, propid, dofadr, ten;    // the dof's body, that body's prop id and first dof; tendon slot of this dof (-1: none)
+  float armature, damping, invweight0, ten_coef;   // ten_coef[ten] (0 where none)
+  float jnt_stiffness, jnt_springref, act_gain, act_bias0;   // of the dof's body; of the arm actuator on this dof (0 where none)
+  float act_bias1, act_bias2, act_ctrl_lo, act_ctrl_hi;
+  float act_force_lo, act_force_hi; int act_forcelimited, pad;
+};
+static_assert(sizeof(DofRec) == 80, "DofRec is five 16-byte words");
+struct alignas(16) MEntryRec {  // lane = entry of the robot block of the sparse mass matrix
+  int i, j; float armature, damping;     // M(i, j); dof_armature[i], dof_damping[i]
+  float act_bias2, ten_coef; int ten, pad;   // act_bias[i][2] (0 past the arm), ten_coef[ten] of dof i (ten = -1: none)
+};
+static_assert(sizeof(MEntryRec) == 32, "MEntryRec is two 16-byte words");
+// parameters of one constraint row by its source: equality e -> row_rec[e], limit of the joint of body b ->
+// row_rec[ROWREC_JNT + b], contact of pair pr -> row_rec[ROWREC_PAIR + pr]
+struct alignas(16) RowRec {
+  float solref[2], margin, gap;     // (margin, gap: pairs only)
+  float solimp[5], friction;        // (friction: pairs only, pair_friction[pr][0])
+  float invw1, invw2;               // connect: body_invweight0[b][0] of its two bodies; joint equality / limit:
+                                    //  dof_invweight0 of its dof(s); pair: body_invweight0[b][0] of each ROBOT body (cubes: per env)
+};
+static_assert(sizeof(RowRec) == 48, "RowRec is three 16-byte words");
+constexpr int ROWREC_JNT = NEQ, ROWREC_PAIR = NEQ + NB, NROWREC = NEQ + NB + NPAIR;
+struct alignas(16) EqRec {     // equality constraint e
+  int type, b1, b2, pb1;            // eq_type, eq_obj, body_parent of both bodies
+  int pb2, root, pad0, pad1;        // first body at or above b1 that is no finger body (the arm link the linkage hangs off)
+  float data[8];
+  float qpos0_1, qpos0_2; int pad2, root_chain_len;   // qpos0 of the dofs of b1 / b2 (joint equality); chain_len[root]
+  int root_chain[12];               // chain_dof[root][0 .. MAXCHAIN), padded
+};
+static_assert(sizeof(EqRec) == 128 && MAXCHAIN <= 12, "EqRec is eight 16-byte words");
+struct alignas(16) SiteRec {   // lane = site
+  float pos[3]; int body;
+  float quat[4];
+};
+static_assert(sizeof(SiteRec) == 32, "SiteRec is two 16-byte words");
+// wave-uniform options, tendon and gripper-actuator scalars in one block
+struct alignas(16) OptRec {
+  float timestep, impratio, tolerance; int iterations;
+  float gravity[3]; int cone;
+  float ten_coef[2]; int ten_dof[2];
+  float grip_gainprm, grip_biasprm[3];
+  float grip_forcerange[2], grip_ctrlrange[2];   // act_ctrlrange[NU - 1]
+  float robot_mass, M0_diag_robot_sum; int tcp_site, eef_site;
+  float tcp_pos[3]; int pad;                     // site_pos[tcp_site]
+};
+static_assert(sizeof(OptRec) == 112, "OptRec is seven 16-byte words");
+
 struct DevModel {
   // ---- bodies (index = body id)
   int body_parent[NB], body_level[NB], body_jnttype[NB], body_dofadr[NB], body_qposadr[NB];
@@ -167,6 +235,14 @@ struct DevModel {
   int cone;                      // mjtCone: 0 = pyramidal, 1 = elliptic (mre_solver.h: assemble_constraints)
   float home_qpos[7];
   float park_pos[NPROP][3];      // where inactive cube slots are parked
+  // ---- the tables above packed per lane for the step's phases (filled and verified by mre_create)
+  BodyRec body_rec[NB];
+  DofRec dof_rec[NV];
+  MEntryRec m_rec[NMR];
+  RowRec row_rec[NROWREC];
+  EqRec eq_rec[NEQ];
+  SiteRec site_rec[NSITE];
+  OptRec opt_rec;
 };
 
 // OSC controller parameters (config/robots/arm/controller_config/osc.yaml:5-22)

@@ -192,6 +192,27 @@ struct BodyRegs {
 MRE_DEV double robot_q(const Sm& s, int d) { return (double)s.qpos[d] + (double)s.qlo[d]; }
 MRE_DEV double robot_v(const Sm& s, int d) { return (double)s.qvel[d] + (double)s.qlo[QFINE / 2 + d]; }
 
+MRE_DEV bool prop_is_active(const Sm& s, int propid) { return propid < 0 || propid < s.nprops; }
+
+// What the position stage reads of its lane's body, taken from the body's record (BodyRec, mre_dev.h) in one group of
+// independent loads at the phase's entry.
+struct BodyK {
+  float quat[4], pos[3], mass, jnt_pos[3], qpos0, jnt_axis[3], ipos[3], iquat[4], inertia[3];
+  int qposadr, propid, dofadr, parent;
+};
+MRE_DEV BodyK load_body(ModelP M, int b) {
+  const auto* R = &M->body_rec[b];
+  BodyK B;
+#pragma unroll
+  for (int k = 0; k < 4; k++) { B.quat[k] = R->quat[k]; B.iquat[k] = R->iquat[k]; }
+#pragma unroll
+  for (int k = 0; k < 3; k++) { B.pos[k] = R->pos[k]; B.jnt_pos[k] = R->jnt_pos[k]; B.jnt_axis[k] = R->jnt_axis[k];
+                                B.ipos[k] = R->ipos[k]; B.inertia[k] = R->inertia[k]; }
+  B.mass = R->mass; B.qpos0 = R->qpos0; B.qposadr = R->qposadr; B.propid = R->propid; B.dofadr = R->dofadr;
+  B.parent = R->parent;
+  return B;
+}
+
 MRE_DEV bool body_is_active(ModelP M, const Sm& s, int b) {
   int p = M->body_propid[b];
   return p < 0 || p < s.nprops;
@@ -242,15 +263,16 @@ MRE_DEV void dq_rot(double* r, const double* q, const double* v) {
   r[0] = v[0] + 2.0 * (w * cx + dx); r[1] = v[1] + 2.0 * (w * cy + dy); r[2] = v[2] + 2.0 * (w * cz + dz);
 }
 // pose of hinge body b in its parent's frame (mj_kinematics, one body): position p, rotation q
-MRE_DEV void hinge_local_d(ModelP M, const Sm& s, int b, double* p, double* q) {
+// (the body's constants come in its record, loaded once by the caller: BodyK)
+MRE_DEV void hinge_local_d(const BodyK& B, const Sm& s, double* p, double* q) {
   double q0[4], ql[4], ax[3], jp[3], t0[3], t1[3];
-  for (int k = 0; k < 4; k++) q0[k] = (double)M->body_quat[b][k];
-  for (int k = 0; k < 3; k++) { ax[k] = (double)M->jnt_axis[b][k]; jp[k] = (double)M->jnt_pos[b][k]; }
-  const int qa = M->body_qposadr[b];
+  for (int k = 0; k < 4; k++) q0[k] = (double)B.quat[k];
+  for (int k = 0; k < 3; k++) { ax[k] = (double)B.jnt_axis[k]; jp[k] = (double)B.jnt_pos[k]; }
+  const int qa = B.qposadr;
   // (the half angle of an arm joint reaches 1.9 rad: the polynomials are evaluated at a quarter of the angle, where
   //  their truncation is below 1e-16, and doubled)
   double s4, c4;
-  sincos_poly_d(0.25 * (robot_q(s, qa) - (double)M->qpos0[qa]), s4, c4);
+  sincos_poly_d(0.25 * (robot_q(s, qa) - (double)B.qpos0), s4, c4);
   const double sn = 2.0 * s4 * c4, cs = 1.0 - 2.0 * s4 * s4;
   ql[0] = cs; ql[1] = ax[0] * sn; ql[2] = ax[1] * sn; ql[3] = ax[2] * sn;
   dq_mul(q, q0, ql);
@@ -258,7 +280,7 @@ MRE_DEV void hinge_local_d(ModelP M, const Sm& s, int b, double* p, double* q) {
   for (int k = 0; k < 4; k++) q[k] *= n;
   dq_rot(t0, q0, jp);
   dq_rot(t1, q, jp);
-  for (int k = 0; k < 3; k++) p[k] = (double)M->body_pos[b][k] + t0[k] - t1[k];
+  for (int k = 0; k < 3; k++) p[k] = (double)B.pos[k] + t0[k] - t1[k];
 }
 template <int CTRL>
 MRE_DEV double dpp_row_d(double v, double fill) {   // the row shift CTRL of a double (two dwords), `fill` where the row has no source lane
@@ -338,12 +360,17 @@ MRE_DEV void chain_step_d(double (&q)[4], double (&p)[3]) {
   for (int c = 0; c < 3; c++) p[c] = ap[c] + t[c];
 }
 template <bool WRITEBACK>
-MRE_DEV void kinematics(ModelP M, Sm& s, int l, BodyRegs& br) {
+MRE_DEV void kinematics(ModelP M, Sm& s, int l, BodyRegs& br, const BodyK& B) {
   constexpr int LINK7 = GRIP_BODY0 - 1;
   const bool arm = l >= 1 && l <= LINK7, fin = l >= GRIP_BODY0 && l < NRB;
+  // (the lane's site, for the last part: its record is fetched now, with the body's)
+  const auto* SR = &M->site_rec[l < NSITE ? l : 0];
+  const int site_b = SR->body, eef_site = M->opt_rec.eef_site;
+  const float site_pos[3] = {SR->pos[0], SR->pos[1], SR->pos[2]};
+  const float site_quat[4] = {SR->quat[0], SR->quat[1], SR->quat[2], SR->quat[3]};
   // ---- every robot body in its parent's frame (fp64; identity elsewhere)
   double q[4] = {1.0, 0.0, 0.0, 0.0}, p[3] = {0.0, 0.0, 0.0};
-  if (arm || fin) hinge_local_d(M, s, l, p, q);
+  if (arm || fin) hinge_local_d(B, s, p, q);
   // a finger body that hangs off another finger body (9, 11, 13, 15 off 8, 10, 12, 14: the dof tree mre_create
   // checks) takes its parent's pose from the lane below: its pose in link 7's frame
   {
@@ -353,7 +380,7 @@ MRE_DEV void kinematics(ModelP M, Sm& s, int l, BodyRegs& br) {
 #pragma unroll
     for (int k = 0; k < 4; k++) pq[k] = dpp_shr1_d(q[k]);
     if (fin) {
-      if (M->body_parent[l] >= GRIP_BODY0) {
+      if (B.parent >= GRIP_BODY0) {
         double t[3], q2[4];
         dq_rot(t, pq, p);
 #pragma unroll
@@ -409,10 +436,10 @@ MRE_DEV void kinematics(ModelP M, Sm& s, int l, BodyRegs& br) {
     for (int k = 0; k < 3; k++) mine.p[k] = (float)wp[k];
 #pragma unroll
     for (int k = 0; k < 9; k++) mine.m[k] = (float)Rm[k];
-    const double jp[3] = {(double)M->jnt_pos[b][0], (double)M->jnt_pos[b][1], (double)M->jnt_pos[b][2]};
-    const double ax[3] = {(double)M->jnt_axis[b][0], (double)M->jnt_axis[b][1], (double)M->jnt_axis[b][2]};
-    const double ip[3] = {(double)M->body_ipos[b][0], (double)M->body_ipos[b][1], (double)M->body_ipos[b][2]};
-    const double iq[4] = {(double)M->body_iquat[b][0], (double)M->body_iquat[b][1], (double)M->body_iquat[b][2], (double)M->body_iquat[b][3]};
+    const double jp[3] = {(double)B.jnt_pos[0], (double)B.jnt_pos[1], (double)B.jnt_pos[2]};
+    const double ax[3] = {(double)B.jnt_axis[0], (double)B.jnt_axis[1], (double)B.jnt_axis[2]};
+    const double ip[3] = {(double)B.ipos[0], (double)B.ipos[1], (double)B.ipos[2]};
+    const double iq[4] = {(double)B.iquat[0], (double)B.iquat[1], (double)B.iquat[2], (double)B.iquat[3]};
 #pragma unroll
     for (int r = 0; r < 3; r++) {
       // the joint anchor is fixed in the body: x + R jnt_pos; a rotation about the axis leaves the axis where it was
@@ -427,7 +454,7 @@ MRE_DEV void kinematics(ModelP M, Sm& s, int l, BodyRegs& br) {
     (void)t;
   }
   if (l >= NRB && l < NB) {   // cubes: free joints
-    const int qa = M->body_qposadr[b];
+    const int qa = B.qposadr;
     v3copy(mine.p, &s.qpos[qa]);
     for (int k = 0; k < 4; k++) mine.q[k] = s.qpos[qa + 3 + k];
     // mj_kinematics normalises the quaternion in qpos.  The state is a double-float pair that the integrator keeps at
@@ -452,41 +479,46 @@ MRE_DEV void kinematics(ModelP M, Sm& s, int l, BodyRegs& br) {
     for (int k = 0; k < 9; k++) s.xmat[b][k] = mine.m[k];
     if (l >= NRB) {   // cubes: the inertial frame from the float32 frame (robot bodies: above, fp64)
       float tmp[3], qi[4];
-      m3mulv(tmp, mine.m, M->body_ipos[b]);
+      m3mulv(tmp, mine.m, B.ipos);
       v3add(br.xipos, mine.p, tmp);
-      qmul(qi, mine.q, M->body_iquat[b]);
+      qmul(qi, mine.q, B.iquat);
       q2mat(br.ximat, qi);
     }
   }
   MRE_SYNC();
   // sites (lane = site)
   if (l < NSITE) {
-    const int b = M->site_body[l];
+    const int b = site_b;
     float tmp[3], q[4];
-    m3mulv(tmp, s.xmat[b], M->site_pos[l]);
+    m3mulv(tmp, s.xmat[b], site_pos);
     v3add(s.site_xpos[l], s.xpos[b], tmp);
-    qmul(q, s.xquat[b], M->site_quat[l]);
-    if (l == M->eef_site) q2mat(s.site_xmat[0], q);
+    qmul(q, s.xquat[b], site_quat);
+    if (l == eef_site) q2mat(s.site_xmat[0], q);
   }
+  keep_live(site_b); keep_live(eef_site);
+#pragma unroll
+  for (int k = 0; k < 3; k++) keep_live(site_pos[k]);
+#pragma unroll
+  for (int k = 0; k < 4; k++) keep_live(site_quat[k]);
 }
 
 // ---------------------------------------------------------------- mj_comPos
-MRE_DEV void com_pos(ModelP M, Sm& s, int l, const BodyRegs& br) {
+MRE_DEV void com_pos(ModelP M, Sm& s, int l, const BodyRegs& br, const BodyK& B, float robot_mass) {
   const bool robot = (l >= 1 && l < NRB);
   float mass = 0.f;
-  if (l < NB) mass = (M->body_propid[l] >= 0) ? s.prop_mass[M->body_propid[l]] : M->body_mass[l];
+  if (l < NB) mass = (B.propid >= 0) ? s.prop_mass[B.propid] : B.mass;
   float c0 = robot ? mass * br.xipos[0] : 0.f;
   float c1 = robot ? mass * br.xipos[1] : 0.f;
   float c2 = robot ? mass * br.xipos[2] : 0.f;
   wave_sum3(c0, c1, c2);
-  const float inv = 1.0f / M->robot_mass;
+  const float inv = 1.0f / robot_mass;
   float com[3] = {c0 * inv, c1 * inv, c2 * inv};
   if (l == 0) v3copy(s.com_robot, com);
   if (l >= 1 && l < NB) {
-    const int b = l, pid = M->body_propid[b];
+    const int b = l, pid = B.propid;
     if (pid >= 0) v3copy(com, br.xipos);  // each cube is its own tree: subtree COM = own COM
     float inertia[3];
-    if (pid >= 0) v3copy(inertia, s.prop_inertia[pid]); else v3copy(inertia, M->body_inertia[b]);
+    if (pid >= 0) v3copy(inertia, s.prop_inertia[pid]); else v3copy(inertia, B.inertia);
     float dif[3], tmp[9];
     v3sub(dif, br.xipos, com);
     const float* mat = br.ximat;
@@ -505,7 +537,7 @@ MRE_DEV void com_pos(ModelP M, Sm& s, int l, const BodyRegs& br) {
     ci[5] = tmp[5] - mass * dif[1] * dif[2];
     ci[6] = mass * dif[0]; ci[7] = mass * dif[1]; ci[8] = mass * dif[2]; ci[9] = mass;
     // cdof (mju_dofCom)
-    const int da = M->body_dofadr[b];
+    const int da = B.dofadr;
     float off[3];
     v3sub(off, com, br.anchor);
     if (pid < 0) {
@@ -523,16 +555,19 @@ MRE_DEV void com_pos(ModelP M, Sm& s, int l, const BodyRegs& br) {
 MRE_PHASE_FN void position_stage(ModelP M, Sm& s, int l) {
   MRE_DBG_T0();
   BodyRegs br;
-  kinematics<true>(M, s, l, br);
+  const BodyK B = load_body(M, l < NB ? l : 0);
+  const float robot_mass = M->opt_rec.robot_mass;
+  kinematics<true>(M, s, l, br, B);
   MRE_DBG_STAMP(5, 0);
-  com_pos(M, s, l, br);
+  com_pos(M, s, l, br, B, robot_mass);
   MRE_SYNC();
   MRE_DBG_STAMP(5, 1);
 }
 // kinematics only (site queries at the end of a launch)
 MRE_PHASE_FN void kinematics_only(ModelP M, Sm& s, int l) {
   BodyRegs br;
-  kinematics<false>(M, s, l, br);
+  const BodyK B = load_body(M, l < NB ? l : 0);
+  kinematics<false>(M, s, l, br, B);
   MRE_SYNC();
 }
 
@@ -548,9 +583,9 @@ MRE_DEV void prop_cdof(const Sm& s, int b, int j, float* c) {
 }
 
 // spatial inertia (10) of body c about point O, axes of the frame its pose (p, q) is given in
-MRE_DEV void inert_about_d(ModelP M, int c, const double* p, const double* q, const double* O, double* ci) {
-  double ip[3] = {(double)M->body_ipos[c][0], (double)M->body_ipos[c][1], (double)M->body_ipos[c][2]}, t[3], qi[4];
-  double iq[4] = {(double)M->body_iquat[c][0], (double)M->body_iquat[c][1], (double)M->body_iquat[c][2], (double)M->body_iquat[c][3]};
+MRE_DEV void inert_about_d(const BodyK& B, const double* p, const double* q, const double* O, double* ci) {
+  double ip[3] = {(double)B.ipos[0], (double)B.ipos[1], (double)B.ipos[2]}, t[3], qi[4];
+  double iq[4] = {(double)B.iquat[0], (double)B.iquat[1], (double)B.iquat[2], (double)B.iquat[3]};
   dq_rot(t, q, ip);
   const double d[3] = {p[0] + t[0] - O[0], p[1] + t[1] - O[1], p[2] + t[2] - O[2]};
   dq_mul(qi, q, iq);
@@ -562,8 +597,8 @@ MRE_DEV void inert_about_d(ModelP M, int c, const double* p, const double* q, co
     R[3] = 2 * (x * y + w * z); R[4] = w * w - x * x + y * y - z * z; R[5] = 2 * (y * z - w * x);
     R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = w * w - x * x - y * y + z * z;
   }
-  const double m = (double)M->body_mass[c];
-  const double in[3] = {(double)M->body_inertia[c][0], (double)M->body_inertia[c][1], (double)M->body_inertia[c][2]};
+  const double m = (double)B.mass;
+  const double in[3] = {(double)B.inertia[0], (double)B.inertia[1], (double)B.inertia[2]};
   double T[9];
   for (int r = 0; r < 3; r++)
     for (int k = 0; k < 3; k++)
@@ -583,26 +618,28 @@ MRE_DEV void inert_about_d(ModelP M, int c, const double* p, const double* q, co
 MRE_PHASE_FN void gripper_local(ModelP M, Sm& s, int l) {
   const bool fin = l >= GRIP_BODY0 && l < NRB;
   const int b = fin ? l : GRIP_BODY0;
+  // the body's record and the pinch site: one group of loads, issued before the pose is read from LDS
+  const BodyK B = load_body(M, b);
+  const float tcp[3] = {M->opt_rec.tcp_pos[0], M->opt_rec.tcp_pos[1], M->opt_rec.tcp_pos[2]};
   const double* pose = s.gpose[b - GRIP_BODY0];
   const double p[3] = {pose[0], pose[1], pose[2]}, q[4] = {pose[3], pose[4], pose[5], pose[6]};
-  const int ts = M->tcp_site;
-  const double O[3] = {(double)M->site_pos[ts][0], (double)M->site_pos[ts][1], (double)M->site_pos[ts][2]};
+  const double O[3] = {(double)tcp[0], (double)tcp[1], (double)tcp[2]};
   // the body's own spatial inertia; a body off link 7 adds its child's, which the lane above has just computed
   // (bodies 9, 11, 13, 15 hang off 8, 10, 12, 14: the dof tree mre_create checks)
   double ci[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (fin) inert_about_d(M, b, p, q, O, ci);
+  if (fin) inert_about_d(B, p, q, O, ci);
   double up[10];
 #pragma unroll
   for (int k = 0; k < 10; k++) up[k] = dpp_shl1_d(ci[k]);
   if (fin) {
 #pragma unroll
     for (int k = 0; k < 10; k++) s.gI[b - GRIP_BODY0][k] = ci[k];
-    if (M->body_parent[b] < GRIP_BODY0 && b + 1 < NRB && M->body_parent[b + 1] == b) {
+    if (B.parent < GRIP_BODY0 && (b & 1) == 0) {   // (the odd body above hangs off this one: mre_create checks the body tree)
 #pragma unroll
       for (int k = 0; k < 10; k++) ci[k] += up[k];
     }
-    double ax[3] = {(double)M->jnt_axis[b][0], (double)M->jnt_axis[b][1], (double)M->jnt_axis[b][2]};
-    double jp[3] = {(double)M->jnt_pos[b][0], (double)M->jnt_pos[b][1], (double)M->jnt_pos[b][2]};
+    double ax[3] = {(double)B.jnt_axis[0], (double)B.jnt_axis[1], (double)B.jnt_axis[2]};
+    double jp[3] = {(double)B.jnt_pos[0], (double)B.jnt_pos[1], (double)B.jnt_pos[2]};
     double u[3], a[3];
     dq_rot(u, q, ax);
     dq_rot(a, q, jp);
@@ -623,21 +660,30 @@ MRE_PHASE_FN void gripper_local(ModelP M, Sm& s, int l) {
 // One side of a `connect` constraint in the frame of the arm's last link: the anchor point x of body
 // b and, for the finger dofs on the way up (b, then its parent if that is a finger body), the lever
 // vectors u_c x (x - a_c) (axis u_c, joint anchor a_c), times `sign`.
-MRE_DEV void connect_side_d(ModelP M, const Sm& s, int b, const float* a, double sign, double* x,
+// (par: b's parent; H[0], H[1]: joint axis and anchor of b and of its parent, loaded by the caller)
+struct HingeK { float ax[3], jp[3]; };
+MRE_DEV HingeK load_hinge(ModelP M, int b) {
+  const auto* R = &M->body_rec[b];
+  HingeK H;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { H.ax[k] = R->jnt_axis[k]; H.jp[k] = R->jnt_pos[k]; }
+  return H;
+}
+MRE_DEV void connect_side_d(const Sm& s, int b, int par, const HingeK (&H)[2], const float* a, double sign, double* x,
                             double (*vec)[3]) {
   const double* pose = s.gpose[b - GRIP_BODY0];
   const double al[3] = {(double)a[0], (double)a[1], (double)a[2]};
   double t[3];
   dq_rot(t, pose + 3, al);
   for (int k = 0; k < 3; k++) x[k] = pose[k] + t[k];
-  const int par = M->body_parent[b];
+#pragma unroll
   for (int m = 0; m < 2; m++) {
     vec[m][0] = vec[m][1] = vec[m][2] = 0.0;
     const int c = m == 0 ? b : par;
     if (c < GRIP_BODY0) break;
     const double* cp = s.gpose[c - GRIP_BODY0];
-    const double ax[3] = {(double)M->jnt_axis[c][0], (double)M->jnt_axis[c][1], (double)M->jnt_axis[c][2]};
-    const double jp[3] = {(double)M->jnt_pos[c][0], (double)M->jnt_pos[c][1], (double)M->jnt_pos[c][2]};
+    const double ax[3] = {(double)H[m].ax[0], (double)H[m].ax[1], (double)H[m].ax[2]};
+    const double jp[3] = {(double)H[m].jp[0], (double)H[m].jp[1], (double)H[m].jp[2]};
     double u[3], ja[3];
     dq_rot(u, cp + 3, ax);
     dq_rot(ja, cp + 3, jp);
@@ -659,10 +705,19 @@ MRE_DEV void connect_side_d(ModelP M, const Sm& s, int b, const float* a, double
 // constraint: [0:3] residual, [4 + 3 m : 7 + 3 m] lever vector of finger dof m (body1, its parent,
 // body2, its parent; zero where the chain is shorter), all in the arm link's axes.
 MRE_PHASE_FN void connect_rows_local(ModelP M, Sm& s, int l) {
-  if (l < 2 && M->eq_type[l] == 0) {
+  // the constraint's record, then the hinges of its two bodies and their parents: two trips to memory
+  const auto* E = &M->eq_rec[l < 2 ? l : 0];
+  const int type = E->type, b1 = E->b1, b2 = E->b2, pb1 = E->pb1, pb2 = E->pb2;
+  float data[6];
+#pragma unroll
+  for (int k = 0; k < 6; k++) data[k] = E->data[k];
+  // (a parent above the fingers takes no part: its slot repeats the body's own hinge, unused)
+  const HingeK H1[2] = {load_hinge(M, b1), load_hinge(M, pb1 >= GRIP_BODY0 ? pb1 : b1)};
+  const HingeK H2[2] = {load_hinge(M, b2), load_hinge(M, pb2 >= GRIP_BODY0 ? pb2 : b2)};
+  if (l < 2 && type == 0) {
     double x1[3], x2[3], v1[2][3], v2[2][3];
-    connect_side_d(M, s, M->eq_obj[l][0], M->eq_data[l], 1.0, x1, v1);
-    connect_side_d(M, s, M->eq_obj[l][1], M->eq_data[l] + 3, -1.0, x2, v2);
+    connect_side_d(s, b1, pb1, H1, data, 1.0, x1, v1);
+    connect_side_d(s, b2, pb2, H2, data + 3, -1.0, x2, v2);
     float* o = &s.qfrc_con[16 * l];
     for (int k = 0; k < 3; k++) {
       o[k] = (float)(x1[k] - x2[k]);
@@ -733,6 +788,7 @@ MRE_DEV void tree_suffix(float (&x)[N], int l) {
 
 // ------------------------------------------------------- mj_crb (robot block)
 MRE_DEV void crb_mass_matrix(ModelP M, Sm& s, int l) {
+  const int tcp_site = M->opt_rec.tcp_site;
   {  // composite inertia of every robot body = its own plus its descendants' (lane = body, tree_suffix)
     float acc[10];
 #pragma unroll
@@ -745,7 +801,9 @@ MRE_DEV void crb_mass_matrix(ModelP M, Sm& s, int l) {
   }
   MRE_SYNC();
   for (int e = l; e < NMR; e += 64) {
-    const int i = M->M_i[e], j = M->M_j[e];
+    const auto* R = &M->m_rec[e];   // (i, j, armature of dof i: one 16-byte load)
+    const int i = R->i, j = R->j;
+    const float armature = R->armature;
     float v;
     if (i >= GRIP_BODY0 - 1) {
       // rows of the finger dofs: momentum map of the finger subtree from gripper_local (fp64, frame
@@ -756,7 +814,7 @@ MRE_DEV void crb_mass_matrix(ModelP M, Sm& s, int l) {
         for (int k = 0; k < 6; k++) cj[k] = s.gC[j - (GRIP_BODY0 - 1)][k];
       } else {
         float off[3], t[3], lin[3];
-        v3sub(off, s.site_xpos[M->tcp_site], s.com_robot);
+        v3sub(off, s.site_xpos[tcp_site], s.com_robot);
         v3cross(t, s.cdof[j], off);
         v3add(lin, s.cdof[j] + 3, t);
         m3tmulv(cj, s.xmat[root], s.cdof[j]);
@@ -765,10 +823,10 @@ MRE_DEV void crb_mass_matrix(ModelP M, Sm& s, int l) {
       v = dot6(cj, s.gP[i - (GRIP_BODY0 - 1)]);
     } else {
       float buf[6];
-      mul_inert_vec(buf, s.crb[M->dof_body[i]], s.cdof[i]);
+      mul_inert_vec(buf, s.crb[i + 1], s.cdof[i]);   // (robot dof i belongs to body i + 1: mre_create checks)
       v = dot6(s.cdof[j], buf);
     }
-    if (i == j) v += M->dof_armature[i];
+    if (i == j) v += armature;
     s.qM[e] = v;
   }
 }
@@ -921,6 +979,11 @@ namespace mre {
 MRE_PHASE_FN void velocity_stage(ModelP M, Sm& s, int l) {
   constexpr int LINK7 = GRIP_BODY0 - 1;
   const bool rob = l >= 1 && l < NRB;   // lane = robot body l, whose hinge is dof l - 1
+  // the model constants of the phase -- gravity, and for the last part (lane = dof) the dof's body, that body's first
+  // dof and prop id -- in one group of loads
+  const auto* DR = &M->dof_rec[l < NV ? l : 0];
+  const int dof_b = DR->body, dof_pid = DR->propid, dof_da = DR->dofadr;
+  const float grav[3] = {M->opt_rec.gravity[0], M->opt_rec.gravity[1], M->opt_rec.gravity[2]};
   // ---- robot: cvel, cdof_dot, cacc in registers (mj_comVel, mj_rne forward pass)
   float cd[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, qv = 0.f;
   if (rob) {
@@ -953,7 +1016,7 @@ MRE_PHASE_FN void velocity_stage(ModelP M, Sm& s, int l) {
     const int b = l;
 #pragma unroll
     for (int t = 0; t < 6; t++) { cv[t] = 0.f; ca[t] = 0.f; }
-    const int da = M->body_dofadr[b];
+    const int da = NRV + 6 * (b - NRB);   // (a cube's first dof: the layout mre_create checks)
 #pragma unroll
     for (int j = 0; j < 3; j++) cv[3 + j] += s.qvel[da + j];
     float cdot[3][6];
@@ -976,7 +1039,7 @@ MRE_PHASE_FN void velocity_stage(ModelP M, Sm& s, int l) {
   float f[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (l >= 1 && l < NB) {
     const int b = l;
-    ca[3] -= M->gravity[0]; ca[4] -= M->gravity[1]; ca[5] -= M->gravity[2];
+    ca[3] -= grav[0]; ca[4] -= grav[1]; ca[5] -= grav[2];
     if (l == LINK7) {   // spatial velocity and bias acceleration of the arm's last link, for finger_bias
 #pragma unroll
       for (int t = 0; t < 6; t++) { s.scratch[t] = cv[t]; s.scratch[6 + t] = ca[t]; }
@@ -1000,7 +1063,7 @@ MRE_PHASE_FN void velocity_stage(ModelP M, Sm& s, int l) {
   MRE_SYNC();
   // qfrc_bias (lane = dof): cdof . sum of cfrc over the subtree of the dof's body
   if (l < NV) {
-    const int b = M->dof_body[l];
+    const int b = dof_b;
     float c6[6];
     if (b < NRB) {
 #pragma unroll
@@ -1008,9 +1071,9 @@ MRE_PHASE_FN void velocity_stage(ModelP M, Sm& s, int l) {
     } else {
 #pragma unroll
       for (int t = 0; t < 6; t++) tot[t] = s.cfrc[b][t];
-      prop_cdof(s, b, l - M->body_dofadr[b], c6);
+      prop_cdof(s, b, l - dof_da, c6);
     }
-    const bool act = body_is_active(M, s, b);
+    const bool act = prop_is_active(s, dof_pid);
     s.qfrc_bias[l] = act ? dot6(c6, tot) : 0.f;
   }
 }
@@ -1055,13 +1118,14 @@ MRE_PHASE_FN void finger_bias(ModelP M, Sm& s, int l) {
   constexpr int LINK7 = GRIP_BODY0 - 1;
   const bool fin = l >= GRIP_BODY0 && l < NRB;
   const int i = fin ? l - GRIP_BODY0 : 0;
+  const int tcp_site = M->opt_rec.tcp_site;
   // link 7's spatial velocity / bias acceleration: c-frame (about the robot's centre of mass, world axes) -> about
   // the pinch site, axes of link 7
   double V7[6], A7[6];
   {
     const float* R = s.xmat[LINK7];
     float r[3];
-    v3sub(r, s.site_xpos[M->tcp_site], s.com_robot);
+    v3sub(r, s.site_xpos[tcp_site], s.com_robot);
     const double rd[3] = {(double)r[0], (double)r[1], (double)r[2]};
     for (int h = 0; h < 2; h++) {
       const float* c = &s.scratch[6 * h];
@@ -1083,7 +1147,7 @@ MRE_PHASE_FN void finger_bias(ModelP M, Sm& s, int l) {
   for (int k = 0; k < 10; k++) I[k] = fin ? s.gI[i][k] : 0.0;
   const double qd = fin ? robot_v(s, l - 1) : 0.0;
   // bodies 8, 10, 12, 14 hang off link 7; 9, 11, 13, 15 off the lane below (the tree mre_create checks)
-  const bool child = fin && M->body_parent[l] >= GRIP_BODY0;
+  const bool child = fin && (l & 1) != 0;   // (the body tree mre_create checks)
   double v[6], a0[6], sd[6];
   dcross_motion(sd, V7, S);
 #pragma unroll
@@ -1125,12 +1189,17 @@ MRE_PHASE_FN void finger_bias(ModelP M, Sm& s, int l) {
 // A function of its own so that the model reads stay out of the step loop's register budget.
 MRE_PHASE_FN unsigned arm_actuation(ModelP M, Sm& s, int l) {
   bool arm_clamped = false;
+  // the actuator on this lane's dof: the tail of the dof's record (one group of loads)
+  const auto* R = &M->dof_rec[l < 7 ? l : 0];
+  const float gain = R->act_gain, bias0 = R->act_bias0, bias1 = R->act_bias1, bias2 = R->act_bias2;
+  const float ctrl_lo = R->act_ctrl_lo, ctrl_hi = R->act_ctrl_hi, force_lo = R->act_force_lo, force_hi = R->act_force_hi;
+  const int forcelimited = R->act_forcelimited;
   if (l < 7) {
-    float fa = (float)((double)(M->act_gain[l] * clampf(s.ctrl[l], M->act_ctrlrange[l][0], M->act_ctrlrange[l][1]) + M->act_bias[l][0]) +
-                       (double)M->act_bias[l][1] * robot_q(s, l) + (double)M->act_bias[l][2] * robot_v(s, l));
-    if (M->act_forcelimited[l]) {
-      if (fa <= M->act_forcerange[l][0]) { fa = M->act_forcerange[l][0]; arm_clamped = true; }
-      if (fa >= M->act_forcerange[l][1]) { fa = M->act_forcerange[l][1]; arm_clamped = true; }
+    float fa = (float)((double)(gain * clampf(s.ctrl[l], ctrl_lo, ctrl_hi) + bias0) +
+                       (double)bias1 * robot_q(s, l) + (double)bias2 * robot_v(s, l));
+    if (forcelimited) {
+      if (fa <= force_lo) { fa = force_lo; arm_clamped = true; }
+      if (fa >= force_hi) { fa = force_hi; arm_clamped = true; }
     }
     s.qfrc_smooth[l] = fa;
   }
@@ -1144,28 +1213,38 @@ MRE_PHASE_FN unsigned arm_actuation(ModelP M, Sm& s, int l) {
 MRE_PHASE_FN unsigned smooth_forces_assemble(ModelP M, Sm& s, int l, unsigned arm_mask) {
   // (the tendon length and velocity from the full finger state: the actuator's position gain of 100 N / rad acts on
   //  joints with 5e-3 kg m^2 of armature)
-  const double ten_len = (double)M->ten_coef[0] * robot_q(s, M->ten_dof[0]) + (double)M->ten_coef[1] * robot_q(s, M->ten_dof[1]);
-  const double ten_vel = (double)M->ten_coef[0] * robot_v(s, M->ten_dof[0]) + (double)M->ten_coef[1] * robot_v(s, M->ten_dof[1]);
-  const float cg = clampf(s.ctrl[NU - 1], M->act_ctrlrange[NU - 1][0], M->act_ctrlrange[NU - 1][1]);
-  float fg = (float)((double)(M->grip_gainprm * cg + M->grip_biasprm[0]) + (double)M->grip_biasprm[1] * ten_len +
-                     (double)M->grip_biasprm[2] * ten_vel);
+  // the tendon / gripper-actuator block and the lane's dof record: one group of loads
+  const auto* O = &M->opt_rec;
+  const float ten_coef[2] = {O->ten_coef[0], O->ten_coef[1]};
+  const int ten_dof[2] = {O->ten_dof[0], O->ten_dof[1]};
+  const float grip_gainprm = O->grip_gainprm, grip_biasprm[3] = {O->grip_biasprm[0], O->grip_biasprm[1], O->grip_biasprm[2]};
+  const float grip_forcerange[2] = {O->grip_forcerange[0], O->grip_forcerange[1]};
+  const float grip_ctrlrange[2] = {O->grip_ctrlrange[0], O->grip_ctrlrange[1]};
+  const auto* DR = &M->dof_rec[l < NV ? l : 0];
+  const int dof_b = DR->body, dof_pid = DR->propid;
+  const float dof_damping = DR->damping, dof_stiffness = DR->jnt_stiffness, dof_springref = DR->jnt_springref;
+  const double ten_len = (double)ten_coef[0] * robot_q(s, ten_dof[0]) + (double)ten_coef[1] * robot_q(s, ten_dof[1]);
+  const double ten_vel = (double)ten_coef[0] * robot_v(s, ten_dof[0]) + (double)ten_coef[1] * robot_v(s, ten_dof[1]);
+  const float cg = clampf(s.ctrl[NU - 1], grip_ctrlrange[0], grip_ctrlrange[1]);
+  float fg = (float)((double)(grip_gainprm * cg + grip_biasprm[0]) + (double)grip_biasprm[1] * ten_len +
+                     (double)grip_biasprm[2] * ten_vel);
   bool clamped = false;
-  if (fg <= M->grip_forcerange[0]) { fg = M->grip_forcerange[0]; clamped = true; }
-  if (fg >= M->grip_forcerange[1]) { fg = M->grip_forcerange[1]; clamped = true; }
+  if (fg <= grip_forcerange[0]) { fg = grip_forcerange[0]; clamped = true; }
+  if (fg >= grip_forcerange[1]) { fg = grip_forcerange[1]; clamped = true; }
   if (l < NV) {
-    const int b = M->dof_body[l];
+    const int b = dof_b;
     float f = 0.f;
     if (b < NRB) {
       // passive: spring + damper of the hinge
       // passive (spring + damper of the hinge), actuation and bias summed in fp64 and rounded once: the finger rows
       // are 1e-3 N m results of 1e-1 N m terms
-      double fd = -(double)M->jnt_stiffness[b] * (robot_q(s, l) - (double)M->jnt_springref[b]) - (double)M->dof_damping[l] * robot_v(s, l);
+      double fd = -(double)dof_stiffness * (robot_q(s, l) - (double)dof_springref) - (double)dof_damping * robot_v(s, l);
       if (l < 7) fd += (double)s.qfrc_smooth[l];
-      if (l == M->ten_dof[0]) fd += (double)M->ten_coef[0] * (double)fg;
-      if (l == M->ten_dof[1]) fd += (double)M->ten_coef[1] * (double)fg;
+      if (l == ten_dof[0]) fd += (double)ten_coef[0] * (double)fg;
+      if (l == ten_dof[1]) fd += (double)ten_coef[1] * (double)fg;
       f = (float)(fd - (double)s.qfrc_bias[l]);
     }
-    const bool act = body_is_active(M, s, b);
+    const bool act = prop_is_active(s, dof_pid);
     f = act ? (b < NRB ? f : f - s.qfrc_bias[l]) : 0.f;
     s.qfrc_smooth[l] = f;
     s.qacc_smooth[l] = f;
@@ -1200,23 +1279,26 @@ MRE_DEV unsigned smooth_forces(ModelP M, Sm& s, int l) {
 // qacc_smooth + M^-1 J' f by construction.)
 MRE_PHASE_FN void integrate_setup(ModelP M, Sm& s, int l, unsigned act_clamped) {
   const bool grip_clamped = (act_clamped >> (NU - 1)) & 1u;
-  const float h = M->timestep;
+  const float h = M->opt_rec.timestep, grip_bias2 = M->opt_rec.grip_biasprm[2];
   // (mj_advance: qacc_warmstart = qacc -- the same array here, see Sm)
   // MH = M - h*dF/dv restricted to M's pattern (diagonal terms only here)
   for (int e = l; e < NMR; e += 64) {
+    // the entry's record (MEntryRec): its dofs and the derivative terms of dof i -- the operands, the products are
+    // formed here as before
+    const auto* R = &M->m_rec[e];
+    const int i = R->i, j = R->j, ten = R->ten;
+    const float damping = R->damping, act_bias2 = R->act_bias2, ten_coef = R->ten_coef;
     float v = s.qM[e];
-    const int i = M->M_i[e];
-    if (i == M->M_j[e]) {
-      v += h * M->dof_damping[i];
-      if (i < 7 && ((act_clamped >> i) & 1u) == 0u) v -= h * M->act_bias[i][2];
+    if (i == j) {
+      v += h * damping;
+      if (i < 7 && ((act_clamped >> i) & 1u) == 0u) v -= h * act_bias2;
       if (!grip_clamped) {
-        if (i == M->ten_dof[0]) v -= h * M->grip_biasprm[2] * M->ten_coef[0] * M->ten_coef[0];
-        if (i == M->ten_dof[1]) v -= h * M->grip_biasprm[2] * M->ten_coef[1] * M->ten_coef[1];
+        if (ten >= 0) v -= h * grip_bias2 * ten_coef * ten_coef;   // (dof i is one of the tendon's two)
       }
     }
     mh_store(s)[e] = v;
 #ifdef MRE_NEWTON
-    if (i == M->M_j[e]) s.scratch[i] = (s.qM[e] - v) * s.qacc[i];   // h D_ii qacc_i
+    if (i == j) s.scratch[i] = (s.qM[e] - v) * s.qacc[i];   // h D_ii qacc_i
 #endif
   }
 #ifndef MRE_NEWTON
@@ -1233,10 +1315,26 @@ MRE_PHASE_FN void integrate_setup(ModelP M, Sm& s, int l, unsigned act_clamped) 
 // cubes' state rounded to float32 leaves it in exactly the two cube exits of the 256-env sample, and with the cubes'
 // state in double it does not (profiles/NOTES.md, round 4).
 MRE_PHASE_FN void integrate(ModelP M, Sm& s, int l, unsigned flags, bool polished, float* clo) {
-  const float h = M->timestep;
+  // the time step, the lane's dof record (first part: lane = dof) and body record (second part: lane = body)
+  const float h = M->opt_rec.timestep;
+  const auto* DR = &M->dof_rec[l < NV ? l : 0];
+  const int dof_b = DR->body, dof_pid = DR->propid;
+  const auto* BR = &M->body_rec[l < NB ? l : 0];
+  const int body_qa = BR->qposadr, body_da = BR->dofadr, body_pid = BR->propid;
   const bool freeze = (flags & F_FREEZE_ROBOT) != 0;
+  // the cubes' low-order words (HBM): the velocity word of a cube dof's lane, the seven pose words of a cube body's
+  // lane -- read here, together, instead of one by one between the stores that update them
+  float vl_in = 0.f, ql_in[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (clo != nullptr) {
+    if (l >= NRV && l < NV) vl_in = clo[(QFINE_CUBE_V - QFINE_CUBE_Q) + (l - NRV)];
+    if (l >= NRB && l < NB) {
+#pragma unroll
+      for (int k = 0; k < 7; k++) ql_in[k] = clo[7 * (l - NRB) + k];
+    }
+  }
+  keep_live(dof_pid); keep_live(body_pid); keep_live(body_qa); keep_live(body_da);
   if (l < NV) {
-    const int b = M->dof_body[l];
+    const int b = dof_b;
     if (b < NRB) {
       if (!freeze) {   // robot joint: the velocity advances in fp64 (double-float pair, robot_q)
 #ifdef MRE_NEWTON
@@ -1248,11 +1346,11 @@ MRE_PHASE_FN void integrate(ModelP M, Sm& s, int l, unsigned flags, bool polishe
         const float hi = (float)v;
         s.qvel[l] = hi; s.qlo[QFINE / 2 + l] = (float)(v - (double)hi);
       }
-    } else if (body_is_active(M, s, b)) {
+    } else if (prop_is_active(s, dof_pid)) {
       // free joints carry no damping: MH = M on cube blocks
       if (clo != nullptr) {
         float* const vl = clo + (QFINE_CUBE_V - QFINE_CUBE_Q) + (l - NRV);
-        const double v = (double)s.qvel[l] + (double)*vl + (double)h * (double)s.qacc[l];
+        const double v = (double)s.qvel[l] + (double)vl_in + (double)h * (double)s.qacc[l];
         const float hi = (float)v, lo = (float)(v - (double)hi);
         s.qvel[l] = hi; *vl = lo;
         s.scratch[l] = lo;   // (scratch[NRV ..]: free here; the body lanes below read the new low words from it)
@@ -1263,25 +1361,25 @@ MRE_PHASE_FN void integrate(ModelP M, Sm& s, int l, unsigned flags, bool polishe
   }
   MRE_SYNC();
   if (l >= 1 && l < NB) {
-    const int b = l, qa = M->body_qposadr[b], da = M->body_dofadr[b];
+    const int b = l, qa = body_qa, da = body_da;
     if (b < NRB) {
       if (!freeze) {
         const double q = robot_q(s, qa) + (double)h * robot_v(s, da);
         const float hi = (float)q;
         s.qpos[qa] = hi; s.qlo[qa] = (float)(q - (double)hi);
       }
-    } else if (body_is_active(M, s, b) && clo != nullptr) {
+    } else if (prop_is_active(s, body_pid) && clo != nullptr) {
       // mj_integratePos of a free joint on the double-float state: position, then q <- normalize(q (x) exp(h w / 2))
       float* const ql = clo + 7 * (b - NRB);
       double vv[6];
       for (int k = 0; k < 6; k++) vv[k] = (double)s.qvel[da + k] + (double)s.scratch[da + k];
       for (int k = 0; k < 3; k++) {
-        const double x = (double)s.qpos[qa + k] + (double)ql[k] + (double)h * vv[k];
+        const double x = (double)s.qpos[qa + k] + (double)ql_in[k] + (double)h * vv[k];
         const float hi = (float)x;
         s.qpos[qa + k] = hi; ql[k] = (float)(x - (double)hi);
       }
       double q0[4], qn[4];
-      for (int k = 0; k < 4; k++) q0[k] = (double)s.qpos[qa + 3 + k] + (double)ql[3 + k];
+      for (int k = 0; k < 4; k++) q0[k] = (double)s.qpos[qa + 3 + k] + (double)ql_in[3 + k];
       const double wn2 = vv[3] * vv[3] + vv[4] * vv[4] + vv[5] * vv[5];
       if (wn2 > 1e-60) {
         const double inv = rsq64(wn2), half = 0.5 * (double)h * wn2 * inv;
@@ -1302,7 +1400,7 @@ MRE_PHASE_FN void integrate(ModelP M, Sm& s, int l, unsigned flags, bool polishe
         const float hi = (float)x;
         s.qpos[qa + 3 + k] = hi; ql[3 + k] = (float)(x - (double)hi);
       }
-    } else if (body_is_active(M, s, b)) {
+    } else if (prop_is_active(s, body_pid)) {
       for (int k = 0; k < 3; k++) s.qpos[qa + k] += h * s.qvel[da + k];
       float w[3] = {s.qvel[da + 3], s.qvel[da + 4], s.qvel[da + 5]};
       const float ang = v3normalize(w) * h;

@@ -47,6 +47,12 @@ namespace mre {
 
 constexpr float kMinVal = 1e-15f;
 
+// A use of x that costs no instruction.  Placed where the branches of a phase meet, it keeps a load issued at the
+// phase's entry THERE: the optimiser otherwise sinks a load whose only user sits in one branch into that branch, where
+// it becomes a trip to memory of its own, waited for at once (model records, mre_dev.h).
+MRE_DEV void keep_live(float x) { asm volatile("" ::"v"(x)); }
+MRE_DEV void keep_live(int x) { asm volatile("" ::"v"(x)); }
+
 MRE_DEV void v3copy(float* r, const float* a) { r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; }
 MRE_DEV void v3zero(float* r) { r[0] = r[1] = r[2] = 0.f; }
 MRE_DEV void v3add(float* r, const float* a, const float* b) {

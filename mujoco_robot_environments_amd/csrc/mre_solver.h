@@ -354,11 +354,15 @@ constexpr int GRIP0 = GRIP_BODY0;
 MRE_PHASE_FN void assemble_constraints(ModelP M, Sm& s, int l) {
   // ---- joint limits: lane = robot body; at most one side can be violated
   int lim = 0, lim_side = 0;
-  if (l >= 1 && l < NRB && M->jnt_limited[l]) {
+  const auto* BR = &M->body_rec[l < NRB ? l : 0];   // (the joint's range and flag: one group of loads)
+  const int jnt_limited = BR->jnt_limited;
+  const float jnt_range[2] = {BR->jnt_range[0], BR->jnt_range[1]};
+  if (l >= 1 && l < NRB && jnt_limited) {
     const double q = robot_q(s, l - 1);   // (the full double-float angle, mre_kernels.hip: robot_q)
-    if (q - (double)M->jnt_range[l][0] < 0.0) { lim = 1; lim_side = -1; }
-    else if ((double)M->jnt_range[l][1] - q < 0.0) { lim = 1; lim_side = 1; }
+    if (q - (double)jnt_range[0] < 0.0) { lim = 1; lim_side = -1; }
+    else if ((double)jnt_range[1] - q < 0.0) { lim = 1; lim_side = 1; }
   }
+  keep_live(jnt_range[0]); keep_live(jnt_range[1]);
   // (rows in joint order: the row index of a violated limit is the number of violated limits on the lanes below)
   const unsigned long long limm = __ballot(lim != 0);
   const int lim_idx = __popcll(limm & ((1ull << l) - 1ull));
@@ -428,68 +432,91 @@ MRE_PHASE_FN void assemble_constraints(ModelP M, Sm& s, int l) {
   for (int i = l; i < nefc; i += 64) {
     int rs = HDR_NONE, pa = 0xF, pb = 0xF;
     float pos = 0.f, margin = 0.f, diag = 0.f, imp_pos = 0.f;
-    const float *solref, *solimp;
     bool fric_row = false;
     float R0scale = 1.0f;
+    // ---- the row's parameters (RowRec, mre_dev.h: solref, solimp, margin, gap, friction, diagonal weights), the range
+    // of a limit row's joint and the options the row reads, fetched HERE in one group of loads: their latency runs
+    // under the Jacobian work below instead of being paid, table by table, where each value is used
+    const int eqi = i < 6 ? i / 3 : 2;     // (rows 0..6: equality constraint of the row)
+    const int limb = (i >= 7 && i < 7 + nl) ? (s.lim_info[i - 7] & 0xFF) : 0;   // (limit rows: the joint's body)
+    const int rrec = i < 7 ? eqi : (i < 7 + nl ? ROWREC_JNT + limb : ROWREC_PAIR + s.con_pair[(i - 7 - nl) / 3]);
+    const auto* RR = &M->row_rec[rrec];
+    const float solref[2] = {RR->solref[0], RR->solref[1]};
+    const float solimp[5] = {RR->solimp[0], RR->solimp[1], RR->solimp[2], RR->solimp[3], RR->solimp[4]};
+    const float rec_margin = RR->margin, rec_gap = RR->gap, rec_friction = RR->friction, invw1 = RR->invw1, invw2 = RR->invw2;
+    const float lim_range[2] = {M->body_rec[limb].jnt_range[0], M->body_rec[limb].jnt_range[1]};
+    const float opt_timestep = M->opt_rec.timestep, opt_impratio = M->opt_rec.impratio;
+    const int opt_cone = M->opt_rec.cone;
     if (i < 7) {
       rs = i;
-      const int e = i < 6 ? i / 3 : 2;
-      solref = M->eq_solref[e]; solimp = M->eq_solimp[e];
+      const int e = eqi;
+      // the constraint's record (EqRec), whole, before the row's two kinds part ways
+      const auto* E = &M->eq_rec[e];
+      const int b1 = E->b1, b2 = E->b2;
+      const int root = E->root, pb1 = E->pb1, pb2 = E->pb2;   // (root: the arm link the linkage hangs off)
+      const float pc[5] = {E->data[0], E->data[1], E->data[2], E->data[3], E->data[4]};
+      const float q0_1 = E->qpos0_1, q0_2 = E->qpos0_2;
+      // (the dofs from the base to the root link, in the order of chain_dof[root])
+      const int nchain = E->root_chain_len;
+      int chain[MAXCHAIN];
+#pragma unroll
+      for (int c = 0; c < MAXCHAIN; c++) chain[c] = E->root_chain[c];
       if (e < 2) {
-        const int b1 = M->eq_obj[e][0], b2 = M->eq_obj[e][1], k = i % 3;
+        const int k = i % 3;
         // residual and finger-dof levers from connect_rows_local (arm link's frame, fp64): rotate to
         // the world.  Arm dofs move both anchors alike: their entry is axis x (p1 - p2), tiny.
-        int root = b1;
-        while (root >= GRIP0) root = M->body_parent[root];
         const float* loc = &s.qfrc_con[16 * e];
         const float* R = s.xmat[root];
         float cp[3];
         m3mulv(cp, R, loc);
         const float rk[3] = {R[3 * k], R[3 * k + 1], R[3 * k + 2]};   // e_k' R: world component k of a local vector
-        const int pb1 = M->body_parent[b1], pb2 = M->body_parent[b2];
         s.Jr[rs][b1 - 1] += v3dot(rk, loc + 4);
         if (pb1 >= GRIP0) s.Jr[rs][pb1 - 1] += v3dot(rk, loc + 7);
         s.Jr[rs][b2 - 1] += v3dot(rk, loc + 10);
         if (pb2 >= GRIP0) s.Jr[rs][pb2 - 1] += v3dot(rk, loc + 13);
         {
-          const int n = M->chain_len[root];
-          for (int c = 0; c < n; c++) {
-            const int j = M->chain_dof[root][c];
-            float t[3];
-            v3cross(t, s.cdof[j], cp);
-            s.Jr[rs][j] += sel3(t, k);
+          // (the loop visits the chain from the record in registers, without a trip to memory per dof)
+#pragma unroll
+          for (int c = 0; c < MAXCHAIN; c++) {
+            if (c < nchain) {
+              const int j = chain[c];
+              float t[3];
+              v3cross(t, s.cdof[j], cp);
+              s.Jr[rs][j] += sel3(t, k);
+            }
           }
         }
         pos = sel3(cp, k);
         imp_pos = v3norm(cp);
-        diag = M->body_invweight0[b1][0] + M->body_invweight0[b2][0];
+        diag = invw1 + invw2;
       } else {
-        const int b1 = M->eq_obj[e][0], b2 = M->eq_obj[e][1];
         const int d1 = b1 - 1, d2 = b2 - 1;
-        const float* pc = M->eq_data[e];
         // (the residual of two finger angles that track each other to 1e-5 rad: evaluated on the full angles)
-        const double dif64 = robot_q(s, d2) - (double)M->qpos0[d2];
-        pos = (float)(robot_q(s, d1) - (double)M->qpos0[d1] -
+        const double dif64 = robot_q(s, d2) - (double)q0_2;
+        pos = (float)(robot_q(s, d1) - (double)q0_1 -
                       ((double)pc[0] + dif64 * ((double)pc[1] + dif64 * ((double)pc[2] + dif64 * ((double)pc[3] + dif64 * (double)pc[4])))));
         const float dif = (float)dif64;
         const float deriv = pc[1] + dif * (2.f * pc[2] + dif * (3.f * pc[3] + dif * 4.f * pc[4]));
         s.Jr[rs][d1] += 1.f;
         s.Jr[rs][d2] -= deriv;
         imp_pos = pos;
-        diag = M->dof_invweight0[d1] + M->dof_invweight0[d2];
+        diag = invw1 + invw2;
       }
+      keep_live(root); keep_live(pb1); keep_live(pb2); keep_live(nchain); keep_live(q0_1); keep_live(q0_2);
+#pragma unroll
+      for (int c = 0; c < 5; c++) keep_live(pc[c]);
+#pragma unroll
+      for (int c = 0; c < MAXCHAIN; c++) keep_live(chain[c]);
     } else if (i < 7 + nl) {
       rs = i;
       const int info = s.lim_info[i - 7], b = info & 0xFF, hi = (info >> 8) & 1;
       const double q = robot_q(s, b - 1);
-      pos = (float)(hi ? ((double)M->jnt_range[b][1] - q) : (q - (double)M->jnt_range[b][0]));
+      pos = (float)(hi ? ((double)lim_range[1] - q) : (q - (double)lim_range[0]));
       s.Jr[rs][b - 1] = hi ? -1.f : 1.f;
       imp_pos = pos;
-      diag = M->dof_invweight0[b - 1];
-      solref = M->jnt_solref[b]; solimp = M->jnt_solimp[b];
+      diag = invw1;
     } else {
       const int c = (i - 7 - nl) / 3, r = (i - 7 - nl) % 3;
-      const int pr = s.con_pair[c];
       const int b1 = s.con_b1[c], b2 = s.con_b2[c];
       const float* ax = &s.con_frame[c][3 * r];
       const float* p = s.con_pos[c];
@@ -498,11 +525,11 @@ MRE_PHASE_FN void assemble_constraints(ModelP M, Sm& s, int l) {
       int slot = 0;
       float dg = 0.f;
       if (b1 > 0) {
-        if (b1 < NRB) { jac_robot(M, s, rs, b1, p, ax, -1.f); dg += M->body_invweight0[b1][0]; }
+        if (b1 < NRB) { jac_robot(M, s, rs, b1, p, ax, -1.f); dg += invw1; }
         else { pa = b1 - NRB; jac_prop(s, i, slot++, b1, p, ax, -1.f); dg += 1.0f / s.prop_mass[pa]; }
       }
       if (b2 > 0) {
-        if (b2 < NRB) { jac_robot(M, s, rs, b2, p, ax, 1.f); dg += M->body_invweight0[b2][0]; }
+        if (b2 < NRB) { jac_robot(M, s, rs, b2, p, ax, 1.f); dg += invw2; }
         else {
           const int pid = b2 - NRB;
           if (slot == 0) pa = pid; else pb = pid;
@@ -511,17 +538,16 @@ MRE_PHASE_FN void assemble_constraints(ModelP M, Sm& s, int l) {
         }
       }
       diag = dg;
-      solref = M->pair_solref[pr]; solimp = M->pair_solimp[pr];
-      margin = M->pair_margin[pr] - M->pair_gap[pr];
+      margin = rec_margin - rec_gap;
       imp_pos = s.con_dist[c];
       if (r == 0) pos = s.con_dist[c];
       else {
         fric_row = true;
         pos = 0.f;
         // R1 = R0/impratio ; R2 = R1 * mu0^2/mu1^2 (mu0 == mu1 for condim 3)
-        R0scale = 1.0f / fmaxf(M->impratio, kMinVal);
+        R0scale = 1.0f / fmaxf(opt_impratio, kMinVal);
       }
-      if (M->cone == 0) {
+      if (opt_cone == 0) {
         // Pyramidal cone (mj_instantiateContact / mj_makeImpedance): MuJoCo's four rows are the edges
         // n +- mu t_k, each with the contact's distance, margin and impedance, diagApprox = tran (1 + mu^2) and
         // one regulariser Rpy = 2 (mu^2 / impratio) R0.  Every edge is a combination of the three rows kept here:
@@ -529,11 +555,13 @@ MRE_PHASE_FN void assemble_constraints(ModelP M, Sm& s, int l) {
         // same B and impedance), so jar_e = jar_n +- mu jar_tk: the edges are never stored, the solvers evaluate
         // the pyramid's cost on the three rows (mre_newton.h: nw_pyramid; PGS: the edge updates of a contact
         // block).  All three rows carry Rpy.
-        const float fr = M->pair_friction[pr][0];
+        const float fr = rec_friction;
         diag = dg * (1.f + fr * fr);
-        R0scale = 2.f * fr * fr / fmaxf(M->impratio, kMinVal);
+        R0scale = 2.f * fr * fr / fmaxf(opt_impratio, kMinVal);
       }
     }
+    keep_live(lim_range[0]); keep_live(lim_range[1]); keep_live(invw1); keep_live(invw2); keep_live(rec_friction);
+    keep_live(rec_margin); keep_live(rec_gap); keep_live(opt_impratio); keep_live(opt_cone);
     s.hdr[i] = rs | (pa << 8) | (pb << 12);
     // impedance of the block's leading row, stiffness / damping from solref
     const float imp = impedance(solimp, imp_pos, margin);
@@ -541,22 +569,22 @@ MRE_PHASE_FN void assemble_constraints(ModelP M, Sm& s, int l) {
     const float dr = solref[1], dmax = clampf(solimp[1], 0.0001f, 0.9999f);
     float K, B;
     if (tc > 0.f) {
-      tc = fmaxf(tc, 2.f * M->timestep);
+      tc = fmaxf(tc, 2.f * opt_timestep);
       K = 1.0f / (dmax * dmax * tc * tc * dr * dr);
       B = 2.0f / (dmax * tc);
     } else { K = -tc / (dmax * dmax); B = -dr / dmax; }
     if (fric_row) K = 0.f;
     float R = fmaxf((1.f - imp) * diag / imp, kMinVal) * R0scale;
-    if (M->cone == 0) R = fmaxf(R, kMinVal);
+    if (opt_cone == 0) R = fmaxf(R, kMinVal);
     // reference acceleration (mj_referenceConstraint)
     const float vel = row_dot(s, i, s.qvel);
     const float efc_margin = fric_row ? 0.f : margin;
     const float aref = -B * vel - K * imp * (pos - efc_margin);
     rowR(s, i) = R; rowB(s, i) = aref;
 #ifdef MRE_NEWTON
-    if (i >= 7 + nl && (i - 7 - nl) % 3 == 0) s.con_fric[(i - 7 - nl) / 3] = M->pair_friction[s.con_pair[(i - 7 - nl) / 3]][0];
+    if (i >= 7 + nl && (i - 7 - nl) % 3 == 0) s.con_fric[(i - 7 - nl) / 3] = rec_friction;
 #else
-    if (i >= 7 + nl && (i - 7 - nl) % 3 == 0) s.blkrec[8 + (i - 7 - nl) / 3][15] = M->pair_friction[s.con_pair[(i - 7 - nl) / 3]][0];
+    if (i >= 7 + nl && (i - 7 - nl) % 3 == 0) s.blkrec[8 + (i - 7 - nl) / 3][15] = rec_friction;
 #endif
   }
   MRE_SYNC();
