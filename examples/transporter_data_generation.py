@@ -5,9 +5,9 @@ RearrangementEnv instances on one MI355X for ``dataset.max_steps`` pick / place 
 Observations are zero images of the reference shapes, or the batched overhead camera's images with --render; with
 --out the episodes of the first --log-envs envs (-1: all of them) are written as RLDS / TFDS shards
 (mujoco_robot_environments_amd/dataset.py) in place of envlogger's TFDSBackendWriter; with --render the frames are
-encoded on the device (csrc/mre_records.hip).
+encoded on the device (csrc/mre_records.hip), and --read-back K reads K episodes back there.
 
-    python examples/transporter_data_generation.py --num-envs 8192 --render --out /tmp/shards
+    python examples/transporter_data_generation.py --num-envs 8192 --render --out /tmp/shards --read-back 64
 """
 import argparse
 import os
@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--out", default=None, help="write the episodes as RLDS shards (TFRecord, the reference ds_config's feature "
                     "keys: mujoco_robot_environments_amd/dataset.py) into this directory")
     ap.add_argument("--log-envs", type=int, default=64, help="with --out: episodes of the first K envs are written (-1: all envs)")
+    ap.add_argument("--read-back", type=int, default=0, metavar="K", help="with --out: afterwards read K episodes back with the device "
+                    "reader (dataset.read_episodes_device) and compare the first one's first frame with what was rendered")
     ap.add_argument("--solver", choices=["Newton", "PGS"], default="Newton", help="constraint solver (the reference's MuJoCo runs Newton)")
     args = ap.parse_args()
     cfg = colour_separator_task_config()
@@ -58,6 +60,10 @@ def main():
         mask = np.arange(args.num_envs) < (args.num_envs if args.log_envs < 0 else args.log_envs)
         logger = BatchedEpisodeLogger(env, writer, mask)
         logger.reset(ts)
+        first_env = int(np.argmax(logger.mask)) if logger.mask.any() else None     # its episode is the first record
+        if args.read_back and first_env is not None:
+            first_frame = {k: (obs[k][first_env].cpu().numpy() if hasattr(obs[k], "cpu") else np.array(obs[k][first_env]))
+                           for k in ("overhead_camera/rgb", "overhead_camera/depth")}
     print(f"reset: {time.time() - t0:.1f} s; placement failed in {int(env.placement_failed.sum())} envs, "
           f"not settled in {int(env.not_settled.sum())}")
     # `alive`: the episode is still running.  The reference's step() raises when a scripted phase does not converge
@@ -114,6 +120,19 @@ def main():
         gb = int(info["splits"][0]["numBytes"]) / 1e9
         log_rate = (f" = {gb:.2f} GB of {int(mask.sum())} envs at {gb / max(t_log, 1e-9):.2f} GB/s, "
                     f"{logger.frames_encoded_on_device} frames encoded on the device")
+        if args.read_back and first_env is not None:
+            import itertools
+            from mujoco_robot_environments_amd.dataset import read_episodes_device
+            t1 = time.time()
+            frames, same = 0, None
+            for k, ep in enumerate(itertools.islice(read_episodes_device(args.out), args.read_back)):
+                o = ep["steps"]["observation"]
+                frames += int(o["overhead_camera/rgb"].shape[0])
+                if k == 0:
+                    same = all(o[key][0].cpu().numpy().tobytes() == first_frame[key].astype(o[key].cpu().numpy().dtype).tobytes()
+                               for key in first_frame)
+            print(f"read back on the device: {frames} frames of {min(args.read_back, int(mask.sum()))} episodes asked in "
+                  f"{time.time() - t1:.2f} s; the first episode's first frame equals the one rendered at reset(): {same}")
     done = ~env.sort_colours(peek=True)[0]
     n_pairs = len(episodes)
     print(f"{int(done.sum())}/{args.num_envs} envs have every cube in its colour's target after {n_pairs} pairs "

@@ -291,6 +291,33 @@ int mre_varint_pack_rows(void* stream, const uint8_t* src, size_t row_stride, si
 int mre_crc32c_rows(void* stream, const uint8_t* src, size_t row_stride, size_t row_bytes,
                     const int32_t* rows_idx, int src_rows, int rows, uint32_t* crc, void* workspace,
                     size_t workspace_bytes);
+/* The reader's side: mre_varint_unpack_rows is the inverse of mre_varint_pack_rows for rows as a shard holds them.  A
+ * record stores a step field as ONE list over all steps, so row r is a whole list: the packed bytes
+ * src[src_off[r] .. + src_len[r]) of one device buffer of src_bytes bytes (the file), nvalues[r] values expected, written
+ * as uint8 to out[out_off[r] .. + nvalues[r]).  The four descriptors are device int64 [rows]; rows may differ in length
+ * and sit at any byte offset; their out ranges must not overlap (not checked).  max_src_len is the host's bound on
+ * src_len[] (1 .. 2^31): it sizes the grid and the workspace, mre_varint_unpack_workspace_bytes(rows, max_src_len)
+ * bytes (0 = bad arguments).  Enqueued on `stream` like the calls above; nothing synchronises; MRE_ERR_ARG with nothing
+ * launched when an argument the host can check is bad.
+ *
+ * The bytes and the descriptors are outside input and are never followed: status[r] (device uint32 [rows]) is 0 for a
+ * row decoded in full, otherwise a set of the MRE_UNPACK_* bits, and the call still returns MRE_OK -- the data is bad,
+ * not the arguments.  Whatever they hold, no byte outside src[0 .. src_bytes) is read, no byte outside a row's own out
+ * range is written (a row with more values than nvalues[r] is clipped), and the other rows are decoded correctly.
+ * Only what TFDS and this library's writer emit for a uint8 tensor is decoded: one or two bytes per value, the second
+ * 0 or 1.  Legal protobuf that neither emits -- a varint of three bytes or more, a non-canonical zero such as 80 80 00
+ * among them -- is flagged, not decoded (80 00 decodes to 0 unflagged); such lists stay with the host reader. */
+#define MRE_UNPACK_LONG 1        /* two consecutive bytes with the high bit set: a varint longer than two bytes */
+#define MRE_UNPACK_OVERFLOW 2    /* a second byte above 1: the value does not fit a byte */
+#define MRE_UNPACK_TRUNCATED 4   /* the row ends in a byte with the high bit set */
+#define MRE_UNPACK_COUNT 8       /* the row holds a number of values other than nvalues[r] */
+#define MRE_UNPACK_DESC 16       /* the descriptor points outside src or out, or src_len[r] > max_src_len: nothing of
+                                  * the row is read or written */
+size_t mre_varint_unpack_workspace_bytes(int rows, size_t max_src_len);
+int mre_varint_unpack_rows(void* stream, const uint8_t* src, size_t src_bytes, const int64_t* src_off,
+                           const int64_t* src_len, const int64_t* nvalues, const int64_t* out_off, int rows,
+                           size_t max_src_len, uint8_t* out, size_t out_capacity, uint32_t* status, void* workspace,
+                           size_t workspace_bytes);
 /* CRC-32C of A || B from the CRCs of A and B and the length of B (host arithmetic, no data is read):
  * crc_a * x^(8 len_b) mod P xor crc_b over the reflected Castagnoli polynomial. */
 uint32_t mre_crc32c_combine(uint32_t crc_a, uint32_t crc_b, size_t len_b);

@@ -1738,6 +1738,43 @@ extern "C" int mre_crc32c_rows(void* stream, const uint8_t* src, size_t row_stri
   return MRE_OK;
 }
 
+static size_t unpack_segments(size_t max_src_len) { return (max_src_len + REC_UNPACK_SEG - 1) / REC_UNPACK_SEG; }
+
+extern "C" size_t mre_varint_unpack_workspace_bytes(int rows, size_t max_src_len) {
+  if (rows <= 0 || max_src_len == 0 || max_src_len > REC_MAX_PACKED_BYTES) return 0;
+  return (size_t)rows * unpack_segments(max_src_len) * sizeof(uint32_t);   // start bytes per segment, then their scan
+}
+
+extern "C" int mre_varint_unpack_rows(void* stream, const uint8_t* src, size_t src_bytes, const int64_t* src_off,
+                                      const int64_t* src_len, const int64_t* nvalues, const int64_t* out_off, int rows,
+                                      size_t max_src_len, uint8_t* out, size_t out_capacity, uint32_t* status,
+                                      void* workspace, size_t workspace_bytes) {
+  const std::string w("mre_varint_unpack_rows");
+  if (!src || !src_off || !src_len || !nvalues || !out_off || !out || !status || !workspace || rows <= 0 ||
+      src_bytes == 0 || out_capacity == 0)
+    return fail(MRE_ERR_ARG, w + ": null argument, empty buffer or empty row set");
+  if (max_src_len == 0 || max_src_len > REC_MAX_PACKED_BYTES) return fail(MRE_ERR_ARG, w + ": max_src_len outside 1 .. 2^31");
+  const size_t nseg = unpack_segments(max_src_len);
+  if ((size_t)rows * nseg > 0x7FFFFFFFull) return fail(MRE_ERR_ARG, w + ": rows x segments above 2^31 - 1");
+  if (workspace_bytes < mre_varint_unpack_workspace_bytes(rows, max_src_len) || ((uintptr_t)workspace & 3))
+    return fail(MRE_ERR_ARG, w + ": workspace smaller than mre_varint_unpack_workspace_bytes() or not 4-byte aligned");
+  if ((((uintptr_t)src_off | (uintptr_t)src_len | (uintptr_t)nvalues | (uintptr_t)out_off) & 7) || ((uintptr_t)status & 3))
+    return fail(MRE_ERR_ARG, w + ": descriptors must be 8-byte aligned, status 4-byte aligned");
+  if (!is_device_ptr(src) || !is_device_ptr(src_off) || !is_device_ptr(src_len) || !is_device_ptr(nvalues) ||
+      !is_device_ptr(out_off) || !is_device_ptr(out) || !is_device_ptr(status) || !is_device_ptr(workspace))
+    return fail(MRE_ERR_ARG, w + ": src, the descriptors, out, status and workspace must be device pointers");
+  UnpackArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = src; a.src_bytes = src_bytes;
+  a.src_off = (const long long*)src_off; a.src_len = (const long long*)src_len;
+  a.nvalues = (const long long*)nvalues; a.out_off = (const long long*)out_off;
+  a.max_src_len = max_src_len; a.rows = (uint32_t)rows; a.nseg = (uint32_t)nseg;
+  a.out = out; a.out_capacity = out_capacity; a.status = status; a.segoff = (uint32_t*)workspace;
+  mre_launch_varint_unpack(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
 extern "C" int mre_wait_stream(mre_env* e, void* stream) {
   if (!e) return fail(MRE_ERR_ARG, "null handle");
   HIPCHK(hipSetDevice(e->device));

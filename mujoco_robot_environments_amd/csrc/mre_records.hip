@@ -1,4 +1,5 @@
-// Episode-record encoding on the device: the two per-byte stages of dataset.py's shard writer.
+// Episode-record encoding on the device: the two per-byte stages of dataset.py's shard writer, and (further down) the
+// inverse of the first for its reader.
 //
 //   * packed varints of uint8 rows (TFDS stores a uint8 tensor as an int64_list: one varint per pixel byte;
 //     v < 128 -> v, v >= 128 -> v, 1).  A row is cut into segments of REC_PACK_SEG input bytes, one workgroup each:
@@ -310,6 +311,187 @@ __global__ __launch_bounds__(NT) void k_crc32c_fold(RecArgs a, uint32_t seg_byte
     a.crc[r] = s_red[0] ^ s_red[1] ^ s_red[2] ^ s_red[3] ^ mulmod(0xFFFFFFFFu, xpow8(n)) ^ 0xFFFFFFFFu;
 }
 
+// ---------------------------------------------------------------- the inverse: packed varints -> uint8 rows
+// A uint8 value is one byte v < 128, or two bytes v | 0x80, v >> 7.  So byte i of a row starts a value iff i == 0 or byte
+// i - 1 has its high bit clear: a local test with one byte of look-behind, across dwords, waves and segments.  The value
+// is (b[i] & 0x7f) | (b[i] & 0x80 ? b[i + 1] << 7 : 0), its index the number of start bytes in front of it:
+//     k_unpack_desc     status[r] = 0, or MRE_UNPACK_DESC for a descriptor outside src / out (such a row is skipped by
+//                       every kernel below: nothing of it is read or written)
+//     k_varint_ucount   start bytes per segment of REC_UNPACK_SEG packed bytes; the malformed-input bits
+//     k_varint_uscan    per row: exclusive scan of the counts -> each segment's first value index; the count bit
+//     k_varint_unpack   the segment's values are put together in LDS (positions from ballots over the wave) at the byte
+//                       phase of their destination, and leave as aligned dwords with head and tail bytes
+// The bytes are outside input: every load is bounded by the row's own descriptor, which k_unpack_desc's rule holds inside
+// src; every store by the row's nvalues (a row with too many start bytes is clipped and flagged).  Encodings this writer
+// and TFDS never emit are flagged rather than decoded: a varint of three bytes or more (also a non-canonical zero such
+// as 80 80 00), a second byte above 1.  80 00 decodes to 0 unflagged.
+static_assert(REC_UNPACK_SEG == REC_PACK_SEG, "load_quarter spreads REC_PACK_SEG bytes over the workgroup");
+
+struct UnpackRow {
+  const uint8_t* src;
+  uint8_t* out;
+  uint32_t len;               // packed bytes (<= REC_MAX_PACKED_BYTES)
+  unsigned long long nvalues;
+};
+
+__device__ inline bool unpack_row(const UnpackArgs& a, uint32_t r, UnpackRow* d) {
+  const long long so = a.src_off[r], sl = a.src_len[r], nv = a.nvalues[r], oo = a.out_off[r];
+  if (so < 0 || sl < 0 || nv < 0 || oo < 0) return false;
+  if ((unsigned long long)sl > a.max_src_len) return false;
+  if ((unsigned long long)so > a.src_bytes || (unsigned long long)sl > a.src_bytes - (unsigned long long)so) return false;
+  if ((unsigned long long)oo > a.out_capacity || (unsigned long long)nv > a.out_capacity - (unsigned long long)oo) return false;
+  d->src = a.src + so;
+  d->out = a.out + oo;
+  d->len = (uint32_t)sl;
+  d->nvalues = (unsigned long long)nv;
+  return true;
+}
+
+__global__ __launch_bounds__(NT) void k_unpack_desc(UnpackArgs a) {
+  const uint32_t r = blockIdx.x * NT + threadIdx.x;
+  if (r >= a.rows) return;
+  UnpackRow d;
+  a.status[r] = unpack_row(a, r, &d) ? 0u : REC_UNPACK_DESC;
+}
+
+// the segment's dwords as load_quarter lays them out, and for each the mask (bit 7 of every byte) of the bytes that start
+// a value.  seg = the segment's first byte, pos = its index in the row, nin = its bytes.  err collects the malformed bits.
+__device__ inline void load_starts(const uint8_t* seg, uint32_t pos, uint32_t nin, int wave, int lane, uint32_t w[4],
+                                   uint32_t st[4], uint32_t* err) {
+  load_quarter(seg, nin, wave, lane, w);
+  uint32_t e = 0;
+  for (int j = 0; j < 4; j++) {
+    const uint32_t b0 = 4u * (uint32_t)(wave * 256 + j * 64 + lane);
+    uint32_t prev = __shfl_up(w[j], 1) >> 24;            // the byte in front of this dword: the lane below holds it,
+    if (lane == 0) prev = (b0 < nin && pos + b0 > 0) ? (seg + b0)[-1] : 0u;   // or memory does (inside the row: pos + b0 > 0;
+                                                                              // b0 - 1 as an unsigned index would wrap at b0 = 0)
+    const uint32_t nb = b0 >= nin ? 0u : (nin - b0 < 4u ? nin - b0 : 4u);
+    const uint32_t vm = nb == 4u ? 0x80808080u : (0x80808080u & ((1u << (8u * nb)) - 1u));
+    const uint32_t h = w[j] & 0x80808080u;               // bytes past nin are zero
+    const uint32_t ph = (h << 8) | (prev & 0x80u);       // high bit of each byte's predecessor
+    st[j] = ~ph & vm;
+    if (h & ph) e |= REC_UNPACK_LONG;
+    const uint32_t second = ((ph & ~h & vm) >> 7) * 0xFFu;   // the bytes that are a value's second byte
+    if (w[j] & second & 0xFEFEFEFEu) e |= REC_UNPACK_OVERFLOW;
+  }
+  *err = e;
+}
+
+__global__ __launch_bounds__(NT) void k_varint_ucount(UnpackArgs a) {
+  __shared__ uint32_t s_sum[NT / 64];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const uint32_t r = blockIdx.x / a.nseg, s = blockIdx.x % a.nseg;
+  UnpackRow d;
+  if (!unpack_row(a, r, &d)) return;
+  const unsigned long long pos64 = (unsigned long long)s * REC_UNPACK_SEG;
+  if (pos64 >= d.len) return;                 // a shorter row than the longest
+  const uint32_t pos = (uint32_t)pos64, left = d.len - pos;
+  const uint32_t nin = left < REC_UNPACK_SEG ? left : REC_UNPACK_SEG;
+  uint32_t w[4], st[4], err;
+  load_starts(d.src + pos, pos, nin, wave, lane, w, st, &err);
+  if (left <= REC_UNPACK_SEG) {               // the row's last byte: a value may not be open behind it
+    const uint32_t last = nin - 1;
+    for (int j = 0; j < 4; j++)
+      if ((last & ~3u) == 4u * (uint32_t)(wave * 256 + j * 64 + lane) && ((w[j] >> (8u * (last & 3u))) & 0x80u))
+        err |= REC_UNPACK_TRUNCATED;
+  }
+  uint32_t c = 0;
+  for (int j = 0; j < 4; j++) c += __popc(st[j]);
+  for (int k = 32; k >= 1; k >>= 1) {
+    c += __shfl_xor(c, k);
+    err |= __shfl_xor(err, k);
+  }
+  if (lane == 0) {
+    s_sum[wave] = c;
+    if (err) atomicOr(&a.status[r], err);
+  }
+  __syncthreads();
+  if (tid == 0) a.segoff[(size_t)r * a.nseg + s] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+}
+
+// one workgroup per row: counts -> each segment's first value index (in place); the total against nvalues
+__global__ __launch_bounds__(NT) void k_varint_uscan(UnpackArgs a) {
+  __shared__ uint32_t s_buf[NT];
+  const int tid = threadIdx.x;
+  const uint32_t r = blockIdx.x;
+  UnpackRow d;
+  if (!unpack_row(a, r, &d)) return;
+  const uint32_t nseg = (uint32_t)(((unsigned long long)d.len + REC_UNPACK_SEG - 1) / REC_UNPACK_SEG);   // <= a.nseg
+  uint32_t* seg = a.segoff + (size_t)r * a.nseg;
+  uint32_t carry = 0;                          // <= len < 2^32
+  for (uint32_t s0 = 0; s0 < nseg; s0 += NT) {
+    const uint32_t s = s0 + tid;
+    const uint32_t c = s < nseg ? seg[s] : 0u;
+    uint32_t tot;
+    const uint32_t ex = block_exscan(c, s_buf, &tot);
+    if (s < nseg) seg[s] = carry + ex;
+    carry += tot;
+  }
+  if (tid == 0 && (unsigned long long)carry != d.nvalues) atomicOr(&a.status[r], REC_UNPACK_COUNT);
+}
+
+__global__ __launch_bounds__(NT) void k_varint_unpack(UnpackArgs a) {
+  __shared__ uint32_t s_stage[REC_UNPACK_SEG / 4 + 1];   // + 1: the values sit at the byte phase of their destination
+  __shared__ uint32_t s_sum[NT / 64];
+  uint8_t* sb = (uint8_t*)s_stage;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const uint32_t r = blockIdx.x / a.nseg, s = blockIdx.x % a.nseg;
+  UnpackRow d;
+  if (!unpack_row(a, r, &d)) return;
+  const unsigned long long pos64 = (unsigned long long)s * REC_UNPACK_SEG;
+  if (pos64 >= d.len) return;
+  const uint32_t pos = (uint32_t)pos64, left = d.len - pos;
+  const uint32_t nin = left < REC_UNPACK_SEG ? left : REC_UNPACK_SEG;
+  const uint8_t* seg = d.src + pos;
+  const uint32_t first = a.segoff[(size_t)r * a.nseg + s];   // index in the row of the segment's first value
+  uint8_t* dst = d.out + first;
+  const uint32_t shift = (uint32_t)((uintptr_t)dst & 3);
+
+  uint32_t w[4], st[4], pre[4], err;
+  load_starts(seg, pos, nin, wave, lane, w, st, &err);
+  const unsigned long long below = (1ull << lane) - 1ull;
+  uint32_t run = 0;   // start bytes in this wave's quarter, in front of dword j
+  for (int j = 0; j < 4; j++) {
+    const uint32_t c = __popc(st[j]);   // 0..4
+    const unsigned long long b0 = __ballot(c & 1u), b1 = __ballot(c & 2u), b2 = __ballot(c & 4u);
+    pre[j] = run + __popcll(b0 & below) + 2 * __popcll(b1 & below) + 4 * __popcll(b2 & below);
+    run += __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
+  }
+  if (lane == 0) s_sum[wave] = run;
+  __syncthreads();
+  uint32_t wbase = 0;
+  for (int v = 0; v < wave; v++) wbase += s_sum[v];
+  const uint32_t count = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];   // <= nin
+  for (int j = 0; j < 4; j++) {
+    const uint32_t b0 = 4u * (uint32_t)(wave * 256 + j * 64 + lane);
+    uint32_t next = __shfl_down(w[j], 1) & 0xFFu;          // the byte behind this dword: the lane above holds it,
+    if (lane == 63) next = (b0 + 4u < left) ? seg[b0 + 4] : 0u;   // or memory does (inside the row: pos + b0 + 4 < len)
+    const uint32_t ext = (w[j] >> 8) | (next << 24);       // byte b of ext = the byte behind byte b of w[j]
+    uint32_t p = wbase + pre[j];
+    for (uint32_t b = 0; b < 4; b++) {
+      if (!((st[j] >> (8 * b)) & 0x80u)) continue;
+      const uint32_t v = (w[j] >> (8 * b)) & 0xFFu;
+      const uint32_t hi = (v & 0x80u) ? ((ext >> (8 * b)) & 1u) << 7 : 0u;
+      if (p < REC_UNPACK_SEG) sb[shift + p] = (uint8_t)((v & 0x7Fu) | hi);
+      p++;
+    }
+  }
+  __syncthreads();
+
+  // out: clipped to the row's nvalues; head bytes up to a dword boundary of the destination, dwords, tail bytes
+  const unsigned long long room = d.nvalues > first ? d.nvalues - first : 0ull;
+  const uint32_t nout = (unsigned long long)count < room ? count : (uint32_t)room;
+  uint32_t head = (4u - shift) & 3u;
+  if (head > nout) head = nout;
+  if ((uint32_t)tid < head) dst[tid] = sb[shift + tid];
+  const uint32_t nd = (nout - head) >> 2;
+  const uint32_t* lw = s_stage + ((shift + head) >> 2);   // shift + head is 0 or 4 when nd > 0
+  uint32_t* dw = (uint32_t*)(dst + head);
+  for (uint32_t k = tid; k < nd; k += NT) dw[k] = lw[k];
+  const uint32_t tail = (nout - head) & 3u;
+  if ((uint32_t)tid < tail) dst[head + 4 * nd + tid] = sb[shift + head + 4 * nd + tid];
+}
+
 }  // namespace
 
 extern "C" void mre_launch_varint_size(const RecArgs* a, hipStream_t stream) {
@@ -321,6 +503,13 @@ extern "C" void mre_launch_varint_size(const RecArgs* a, hipStream_t stream) {
 extern "C" void mre_launch_varint_pack(const RecArgs* a, hipStream_t stream) {
   hipLaunchKernelGGL(k_varint_pack, dim3(a->rows * a->nseg), dim3(NT), 0, stream, *a);
   hipLaunchKernelGGL(k_crc32c_fold, dim3(a->rows), dim3(NT), 0, stream, *a, 0u);
+}
+
+extern "C" void mre_launch_varint_unpack(const UnpackArgs* a, hipStream_t stream) {
+  hipLaunchKernelGGL(k_unpack_desc, dim3((a->rows + NT - 1) / NT), dim3(NT), 0, stream, *a);
+  hipLaunchKernelGGL(k_varint_ucount, dim3(a->rows * a->nseg), dim3(NT), 0, stream, *a);
+  hipLaunchKernelGGL(k_varint_uscan, dim3(a->rows), dim3(NT), 0, stream, *a);
+  hipLaunchKernelGGL(k_varint_unpack, dim3(a->rows * a->nseg), dim3(NT), 0, stream, *a);
 }
 
 extern "C" void mre_launch_crc32c_rows(const RecArgs* a, hipStream_t stream) {

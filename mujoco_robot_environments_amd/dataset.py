@@ -36,7 +36,10 @@ reading them again (the record's CRC is combined from the pieces' CRCs).  numpy 
 (``write_episode``), which is also what the device path is tested against, byte for byte.
 
 ``read_episodes`` parses a directory back BY ITS features.json (it is a generic reader of this format, not a mirror
-of the writer), and tests/test_dataset.py round-trips through it.
+of the writer), and tests/test_dataset.py round-trips through it.  ``read_episodes_device`` is the same reader with
+the image leaves decoded on the device (``scan_records`` + ``locate_example`` find the bytes on the host from the
+framing alone; ``records.varint_unpack_rows`` / ``crc32c_rows`` do the per-byte work), held to ``read_episodes`` leaf
+for leaf in tests/test_gpu_record_reader.py.
 """
 from __future__ import annotations
 
@@ -164,6 +167,29 @@ def read_records(path: str) -> Iterator[bytes]:
             yield payload
 
 
+def scan_records(path: str) -> Iterator[tuple]:
+    """(payload offset, payload length, stored masked CRC-32C of the payload) of every record of a TFRecord file, from
+    its framing alone: the length header is checked against its CRC on the spot, the payload is skipped, not read.
+    A file that ends inside a record, or a header that fails its CRC, raises ValueError."""
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        pos = 0
+        while pos < size:
+            head = f.read(12)
+            if len(head) < 12:
+                raise ValueError(f"{path}: cut short inside the length header of the record at byte {pos}")
+            (n,) = struct.unpack("<Q", head[:8])
+            (c1,) = struct.unpack("<I", head[8:])
+            if c1 != _masked_crc(head[:8]):
+                raise ValueError(f"{path}: bad length CRC in the record at byte {pos}")
+            if pos + 12 + n + 4 > size:
+                raise ValueError(f"{path}: cut short inside the record at byte {pos} ({n} payload bytes announced)")
+            f.seek(pos + 12 + n)
+            (c2,) = struct.unpack("<I", f.read(4))
+            yield pos + 12, n, c2
+            pos += 12 + n + 4
+
+
 # ------------------------------------------------------------------ tf.train.Example wire format
 def _varint(n: int) -> bytes:
     out = bytearray()
@@ -284,6 +310,77 @@ def decode_example(payload: bytes) -> Dict[str, object]:
                         elif f4 == 3:
                             val = np.concatenate([_unpack_varints(v) for _, v in _fields(lst)] or [np.zeros(0, np.int64)])
             out[key] = val
+    return out
+
+
+_LIST_KINDS = {1: "bytes", 2: "float", 3: "int64"}
+
+
+def _headers(b, lo: int, hi: int):
+    """(field, wire type, start, end) of every field of the message b[lo:hi], from its headers alone: a length-delimited
+    field's body is b[start:end]; a varint or fixed32 field is stepped over.  Lengths are held inside [lo, hi)."""
+    i = lo
+    try:
+        while i < hi:
+            key, i = _read_varint(b, i)
+            f, wt = key >> 3, key & 7
+            if wt == 2:
+                n, i = _read_varint(b, i)
+                if i + n > hi:
+                    raise ValueError(f"field {f} at byte {i}: {n} bytes announced, {hi - i} left")
+                yield f, wt, i, i + n
+                i += n
+            elif wt == 0:
+                start = i
+                _, i = _read_varint(b, i)
+                yield f, wt, start, i
+            elif wt == 5:
+                yield f, wt, i, i + 4
+                i += 4
+            else:
+                raise ValueError("unsupported wire type")
+            if i > hi:
+                raise ValueError(f"field {f} runs past the end of its message")
+    except IndexError:
+        raise ValueError("a varint runs past the end of the payload") from None
+
+
+def locate_example(payload) -> Dict[str, tuple]:
+    """Where every feature's data lies in a serialised tf.train.Example: {key: (kind, offset, length)} with kind
+    "bytes" / "float" / "int64", and payload[offset : offset + length] the packed data of the list (float: little-endian
+    float32; int64: packed varints; bytes: the list's whole body, elements not located).  Framing only: it walks the map
+    entries as ``decode_example`` does, on a memoryview and by offsets, and looks at no byte beyond the headers.  It
+    accepts less than ``decode_example``: a list given as unpacked elements, or as more than one packed chunk, raises
+    ValueError, as does a length that runs past the end or an unsupported wire type."""
+    b = memoryview(payload).cast("B")
+    out: Dict[str, tuple] = {}
+    for f, wt, lo, hi in _headers(b, 0, len(b)):
+        if f != 1 or wt != 2:
+            continue
+        for _, wt2, lo2, hi2 in _headers(b, lo, hi):             # map<string, Feature> entries
+            if wt2 != 2:
+                raise ValueError("Features: a map entry that is not length-delimited")
+            key, where = None, None
+            for f3, wt3, lo3, hi3 in _headers(b, lo2, hi2):
+                if f3 == 1 and wt3 == 2:
+                    key = bytes(b[lo3:hi3]).decode()
+                elif f3 == 2 and wt3 == 2:
+                    for f4, wt4, lo4, hi4 in _headers(b, lo3, hi3):    # Feature: one of the three lists
+                        if wt4 != 2 or f4 not in _LIST_KINDS:
+                            raise ValueError(f"Feature: field {f4} with wire type {wt4}")
+                        kind = _LIST_KINDS[f4]
+                        if kind == "bytes":
+                            where = (kind, lo4, hi4 - lo4)
+                            continue
+                        chunks = list(_headers(b, lo4, hi4))
+                        if any(f5 != 1 or wt5 != 2 for f5, wt5, _, _ in chunks):
+                            raise ValueError(f"'{key}': {kind}_list with unpacked elements")
+                        if len(chunks) > 1:
+                            raise ValueError(f"'{key}': {kind}_list in {len(chunks)} packed chunks")
+                        where = (kind, chunks[0][2], chunks[0][3] - chunks[0][2]) if chunks else (kind, lo4, 0)
+            if key is None or where is None:
+                raise ValueError("Features: a map entry without key or value")
+            out[key] = where
     return out
 
 
@@ -574,6 +671,186 @@ class _HostArena:
         t = self._block[self._used:self._used + n]
         self._used += (n + 63) & ~63
         return t
+
+    def reset(self) -> None:
+        """Everything taken so far is free again (the caller knows that no copy still uses it)."""
+        self._used = 0
+
+
+def _is_image_leaf(shape, dtype: str, seq: bool) -> bool:
+    return seq and len(shape) >= 2 and dtype in ("uint8", "float32")
+
+
+class ReadTimer:
+    """Device events around the reader's unpack and CRC launches (read_episodes_device(timer=...)); tools/bench_shards.py."""
+
+    def __init__(self):
+        self.events: list = []
+        self.packed_bytes = self.unpacked_bytes = self.crc_bytes = 0
+
+    def stamp(self) -> None:
+        import torch
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        self.events.append(e)
+
+    def kernel_ms(self):
+        """(unpack ms, CRC ms): the stamps come in fours per shard -- around the unpack call, around the CRC calls."""
+        import torch
+        torch.cuda.synchronize()
+        ev = self.events
+        return (float(sum(a.elapsed_time(b) for a, b in zip(ev[0::4], ev[1::4]))),
+                float(sum(a.elapsed_time(b) for a, b in zip(ev[2::4], ev[3::4]))))
+
+
+def read_episodes_device(data_directory: str, name: Optional[str] = None, split_name: str = "train", device=None,
+                         verify: bool = True, timer: Optional[ReadTimer] = None) -> Iterator[dict]:
+    """``read_episodes`` with the image leaves decoded on the device: the same tree, dtypes and shapes, where a tensor
+    leaf of rank >= 2 inside the step sequence with dtype uint8 or float32 is a CUDA tensor (uint8 [T, H, W, 3],
+    float32 [T, H, W]) and everything else is numpy, decoded on the host from its located bytes.  Driven by
+    features.json like ``read_episodes``; the HIP path has no host fallback (no GPU, no reader).
+
+    Per shard: ``scan_records`` finds the records from the framing; the file goes to the device once through pinned
+    memory, each payload to a 16-byte aligned offset (the CRC kernel loads aligned rows as 16-byte words);
+    ``locate_example`` finds every feature's bytes; ALL uint8 image lists of the shard are unpacked by one
+    ``records.varint_unpack_rows`` call; a float32 image is the payload's bytes as they are (a byte-slice copy, then a
+    view: its offset in the payload is not a multiple of 4).  verify=True: the CRC-32C of every payload is computed on
+    the device (``records.crc32c_rows``) and compared with the stored one.  One synchronise per shard, for the statuses
+    and the CRCs.  A CRC mismatch, a non-zero unpack status or a record count other than dataset_info.json's raises
+    ValueError naming the file, the record and the key; the shard's records before the bad one are yielded, none after.
+    ``timer`` (a ReadTimer) puts device events around the unpack and the CRC launches and counts their bytes."""
+    import torch
+    from . import records as R
+    with open(os.path.join(data_directory, "features.json")) as f:
+        feat = json.load(f)
+    with open(os.path.join(data_directory, "dataset_info.json")) as f:
+        info = json.load(f)
+    name = name or info["name"]
+    split = next(sp for sp in info["splits"] if sp["name"] == split_name)
+    n = len(split["shardLengths"])
+    leaves = list(feature_leaves(feat))
+    paths = list(_leaf_paths(feat))
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    arena = None
+    for k in range(n):
+        p = os.path.join(data_directory, f"{name}-{split_name}.{info['fileFormat']}-{k:05d}-of-{n:05d}")
+        recs = list(scan_records(p))
+        if len(recs) != int(split["shardLengths"][k]):
+            raise ValueError(f"{p}: {len(recs)} records, dataset_info.json says {split['shardLengths'][k]}")
+        if not recs:
+            continue
+        size = os.path.getsize(p)
+        if arena is None or arena.block_bytes < size:
+            arena = _HostArena(1 << max(size - 1, 1).bit_length())
+        arena.reset()                                      # the previous shard's copies ended with its synchronise
+        h_file = arena.take(size)
+        with open(p, "rb") as f:
+            if f.readinto(h_file.numpy()) != size:
+                raise ValueError(f"{p}: changed while it was read")
+        host = memoryview(h_file.numpy())
+        base, total = [], 0                                # payload r lies at d_file[base[r] : base[r] + length]
+        for _, length, _ in recs:
+            base.append(total)
+            total += (length + 15) & ~15
+        with torch.cuda.device(dev):
+            d_file = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+            for (off, length, _), b in zip(recs, base):
+                if length:
+                    d_file[b:b + length].copy_(h_file[off:off + length], non_blocking=True)
+            # the host's share: framing, the small leaves, the rows of the one unpack call
+            episodes, rows, row_of = [], [], []            # rows: (src_off, src_len, nvalues, out_off)
+            n_out = 0
+            for r, ((off, length, _), b) in enumerate(zip(recs, base)):
+                pay = host[off:off + length]
+                try:
+                    where = locate_example(pay)
+                    small, T = {}, None
+                    for key, shape, dtype, seq in leaves:
+                        kind, o, ln = where[key]
+                        per = int(np.prod(shape, dtype=np.int64))
+                        if _is_image_leaf(shape, dtype, seq) and kind == ("int64" if dtype == "uint8" else "float"):
+                            if dtype == "float32":
+                                if ln % (4 * per):
+                                    raise ValueError(f"'{key}': {ln} bytes are no whole number of float32 {shape} frames")
+                                T = ln // (4 * per) if T is None else T
+                            continue
+                        v = (_unpack_varints(pay[o:o + ln]) if kind == "int64" else
+                             np.frombuffer(pay[o:o + ln], "<f4") if kind == "float" else None)
+                        if v is None:
+                            raise ValueError(f"'{key}': a bytes list where features.json has a {dtype} tensor")
+                        small[key] = v
+                        if seq and T is None:
+                            T = v.size // per
+                    if T is None:      # uint8 image leaves only: a value ends at every byte with the high bit clear
+                        key, shape = next((ky, sh) for ky, sh, dt, sq in leaves if sq)
+                        _, o, ln = where[key]
+                        T = int(np.count_nonzero(np.frombuffer(pay[o:o + ln], np.uint8) < 0x80)) // int(np.prod(shape))
+                except (ValueError, KeyError) as e:
+                    raise ValueError(f"{p}: record {r}: {e}") from None
+                image = {}
+                for key, shape, dtype, seq in leaves:
+                    if key in small:
+                        continue
+                    _, o, ln = where[key]
+                    if dtype == "uint8":
+                        nv = T * int(np.prod(shape, dtype=np.int64))
+                        rows.append((b + o, ln, nv, n_out))
+                        row_of.append((r, key))
+                        image[key] = (n_out, nv)
+                        n_out += (nv + 15) & ~15
+                    else:
+                        if ln != 4 * T * int(np.prod(shape, dtype=np.int64)):
+                            raise ValueError(f"{p}: record {r}: '{key}': {ln} bytes for {T} steps of float32 {shape}")
+                        image[key] = d_file[b + o:b + o + ln].clone().view(torch.float32)
+                episodes.append((small, image, T))
+            status = None
+            if timer is not None:
+                timer.stamp()
+            if rows:
+                desc = np.asarray(rows, np.int64).T
+                d_out = torch.empty(max(n_out, 1), dtype=torch.uint8, device=dev)
+                _, status = R.varint_unpack_rows(d_file, desc[0], desc[1], desc[2], desc[3], out=d_out)
+            if timer is not None:
+                timer.stamp()
+                timer.stamp()
+                timer.packed_bytes += int(sum(x[1] for x in rows))
+                timer.unpacked_bytes += int(sum(x[2] for x in rows))
+            crcs = None
+            if verify:
+                crcs = torch.cat([R.crc32c_rows(d_file[b:b + length].view(1, -1)) if length else
+                                  torch.zeros(1, dtype=torch.int32, device=dev) for (_, length, _), b in zip(recs, base)])
+                if timer is not None:
+                    timer.crc_bytes += int(sum(length for _, length, _ in recs))
+            if timer is not None:
+                timer.stamp()
+            parts = [t for t in (status, crcs) if t is not None]
+            back = torch.cat(parts).cpu().numpy() if parts else np.zeros(0, np.int32)   # the shard's one synchronise
+        status_h = back[:len(rows)] if status is not None else np.zeros(0, np.int32)
+        crc_h = back[len(status_h):].view(np.uint32)
+        bad = {}                                           # record -> message, the first per record
+        for (r, key), st in zip(row_of, status_h):
+            if st and r not in bad:
+                bad[r] = f"'{key}': malformed packed varints (unpack status {int(st):#x})"
+        if verify:
+            for r, (_, _, stored) in enumerate(recs):
+                if _mask(int(crc_h[r])) != stored:
+                    bad[r] = "bad payload CRC (computed on the device; it covers every key of the record)"
+        for r, (small, image, T) in enumerate(episodes):
+            if r in bad:
+                raise ValueError(f"{p}: record {r}: {bad[r]}")
+            out: dict = {}
+            for (key, shape, dtype, seq), path in zip(leaves, paths):
+                if key in small:
+                    v = small[key]
+                    v = v.reshape((-1,) + shape) if seq else v.reshape(shape)
+                    v = v.astype(_NP_DTYPE[dtype])
+                elif dtype == "uint8":
+                    o, nv = image[key]
+                    v = d_out[o:o + nv].view((T,) + shape)
+                else:
+                    v = image[key].view((T,) + shape)
+                _nest(out, key, path, v)
+            yield out
 
 
 class BatchedEpisodeLogger:

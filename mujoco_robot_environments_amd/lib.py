@@ -36,7 +36,10 @@ EXPORTS = [
     "mre_set_fallback", "mre_get_fallback_stats", "mre_get_queue_info", "mre_set_solver", "mre_get_solver", "mre_wait_stream", "mre_osc_compute", "mre_get_contacts", "mre_get_settle_steps", "mre_get_launch_info", "mre_prop_place", "mre_sort_colours", "mre_crc32c", "mre_osc_configure_env", "mre_set_env_ids", "mre_set_render_colours", "mre_render",
     "mre_get_state_f64", "mre_set_state_f64", "mre_get_time", "mre_pack_final_state",
     "mre_records_workspace_bytes", "mre_varint_pack_rows", "mre_crc32c_rows", "mre_crc32c_combine",
+    "mre_varint_unpack_workspace_bytes", "mre_varint_unpack_rows",
 ]
+# status bits of mre_varint_unpack_rows (include/mre.h)
+MRE_UNPACK_LONG, MRE_UNPACK_OVERFLOW, MRE_UNPACK_TRUNCATED, MRE_UNPACK_COUNT, MRE_UNPACK_DESC = 1, 2, 4, 8, 16
 
 
 class MreError(RuntimeError):
@@ -176,9 +179,12 @@ def lib() -> C.CDLL:
     L.mre_records_workspace_bytes.argtypes = [ci, sz]
     L.mre_varint_pack_rows.argtypes = [vp, fp, sz, sz, fp, ci, ci, fp, sz, fp, fp, fp, fp, sz]
     L.mre_crc32c_rows.argtypes = [vp, fp, sz, sz, fp, ci, ci, fp, fp, sz]
+    L.mre_varint_unpack_workspace_bytes.restype = sz
+    L.mre_varint_unpack_workspace_bytes.argtypes = [ci, sz]
+    L.mre_varint_unpack_rows.argtypes = [vp, fp, sz, fp, fp, fp, fp, ci, sz, fp, sz, fp, fp, sz]
     for name in EXPORTS:
         if name not in ("mre_last_error", "mre_stream", "mre_crc32c", "mre_crc32c_combine",
-                        "mre_records_workspace_bytes"):
+                        "mre_records_workspace_bytes", "mre_varint_unpack_workspace_bytes"):
             getattr(L, name).restype = ci
     _LIB = L
     return L
