@@ -126,6 +126,13 @@ int mre_sort_colours(mre_env*, uint64_t seed, const int32_t* call_counts, const 
  * contacts[N][MRE_MAX_CONTACTS][3] = (geom1, geom2, dist), host or device pointers. */
 #define MRE_MAX_CONTACTS 32
 int mre_get_contacts(mre_env*, int32_t* count, float* contacts);
+/* The whole contact record (physics.data.contact[i].pos / .frame / .dist / .geom1 / .geom2) of the same launch:
+ * contacts[N][MRE_MAX_CONTACTS][15] = pos[3], frame[9] (normal from geom1 to geom2, then the two tangents), dist,
+ * geom1, geom2; rows past the count are zero.  active_only = 0: every detected contact (dist < margin), the list of
+ * mre_get_contacts.  active_only = 1: the list the next step's solve would be given (dist < margin - gap; the narrow
+ * phase runs with that threshold, as it does inside a step).  count[N]: rows filled; negative: the list was cut
+ * (more than MRE_MAX_CONTACTS contacts, or the kernel's contact capacity exceeded) and holds the first -count. */
+int mre_get_contacts_full(mre_env*, int active_only, int32_t* count, float* contacts);
 /* global id of env 0 of this handle (rank r of a sharded batch: r * num_envs); random
  * draws are keyed by global id so results do not depend on the sharding */
 int mre_set_env_id_offset(mre_env*, long long offset);

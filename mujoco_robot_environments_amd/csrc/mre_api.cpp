@@ -108,6 +108,7 @@ struct mre_env {
   uint32_t* sv_status = nullptr;
   uint8_t* sv_converged = nullptr;
   float* contacts = nullptr;     // device [N][1 + 3 * CONTACT_EXPORT] (detect launches), allocated on first use
+  float* contacts_full = nullptr;  // device [N][CONTACT_EXPORT][12] (mre_get_contacts_full), allocated on first use
   int* settle_steps = nullptr;   // device [N]
   // Launch info and the per-launch inputs the host decides (dispatch order, large flags) live in MAPPED pinned host
   // memory that the step kernels store to / load from directly: no copy command sits in a group's launch chain
@@ -1406,7 +1407,7 @@ extern "C" int mre_destroy(mre_env* e) {
                   e->grip_closed, e->converged, e->mask, e->sites, e->status, e->stats, e->d_osc, e->d_osc_env, e->order,
                   e->geoms, e->prop_rgb, e->bg_depth, e->bg_rgb, e->bg_seg,
                   e->d_large, e->mask_r, e->qfine, e->sv_qfine, e->nstep, e->sv_nstep, e->sv_qpos, e->sv_qvel, e->sv_qacc_ws, e->sv_ctrl,
-                  e->sv_status, e->auto_order, e->sv_converged, e->contacts, e->settle_steps,
+                  e->sv_status, e->auto_order, e->sv_converged, e->contacts, e->contacts_full, e->settle_steps,
                   e->d_env_ids, e->ps_attempts, e->ps_prop, e->ps_tick, e->ps_which, e->ps_bounds, e->ps_pose, e->ps_zones,
                   e->ps_pick};
   for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -2251,12 +2252,14 @@ static void fill_search(mre_env* e, SearchArgs& sa) {
 // physics.forward() + physics.data.contact on the current poses: one zero-step launch that runs the
 // kinematics and the narrow phase and exports every DETECTED contact (dist < margin), per env
 // [count, (geom1, geom2, dist) x CONTACT_EXPORT]; count < 0: the list was cut at -count.
-static int detect_contacts(mre_env* e, const uint8_t* dmask) {
+static int detect_contacts(mre_env* e, const uint8_t* dmask, bool full = false, bool active_only = false) {
   const size_t N = (size_t)e->N, row = 1 + 3 * CONTACT_EXPORT;
   if (!e->contacts) HIPCHK(hipMalloc(&e->contacts, N * row * 4));
+  if (full && !e->contacts_full) HIPCHK(hipMalloc(&e->contacts_full, N * CONTACT_EXPORT * 12 * 4));
   StepArgs a;
   fill_args(e, a);
-  a.nsteps = 0; a.flags = F_DETECT; a.trace = nullptr; a.env_mask = dmask; a.contacts = e->contacts;
+  a.nsteps = 0; a.flags = F_DETECT | (active_only ? F_DETECT_ACTIVE : 0u); a.trace = nullptr; a.env_mask = dmask;
+  a.contacts = e->contacts; a.contacts_full = full ? e->contacts_full : nullptr;
   a.sites = nullptr; a.geoms = nullptr;
   launch_compact(e, a, e->stream);
   HIPCHK(hipGetLastError());
@@ -2278,6 +2281,37 @@ extern "C" int mre_get_contacts(mre_env* e, int32_t* count, float* contacts) {
   for (size_t i = 0; i < N; i++) {
     hc[i] = (int32_t)h[i * row];
     memcpy(&ho[i * 3 * CONTACT_EXPORT], &h[i * row + 1], 3 * CONTACT_EXPORT * 4);
+  }
+  if ((rc = copy_out(e, count, hc.data(), N * 4))) return rc;
+  return copy_out(e, contacts, ho.data(), ho.size() * 4);
+}
+
+// The whole mjContact record of the same zero-step launch: rows of 15 = pos[3], frame[9], dist, geom1, geom2.
+// active_only: the launch runs collide(.., detect = false), the call every step makes -- its early-outs see
+// margin - gap, not margin, so this list is what the next solve would be given, not a filtered copy of the other.
+extern "C" int mre_get_contacts_full(mre_env* e, int active_only, int32_t* count, float* contacts) {
+  if (!e || !count || !contacts) return fail(MRE_ERR_ARG, "mre_get_contacts_full: null");
+  DRAIN(e);
+  HIPCHK(hipSetDevice(e->device));
+  int rc = detect_contacts(e, nullptr, true, active_only != 0);
+  if (rc) return rc;
+  const size_t N = (size_t)e->N, row = 1 + 3 * CONTACT_EXPORT, W = 15;
+  std::vector<float> h(N * row), hf(N * CONTACT_EXPORT * 12);
+  if ((rc = copy_out(e, h.data(), e->contacts, h.size() * 4))) return rc;
+  if ((rc = copy_out(e, hf.data(), e->contacts_full, hf.size() * 4))) return rc;
+  std::vector<int32_t> hc(N);
+  std::vector<float> ho(N * CONTACT_EXPORT * W, 0.f);
+  for (size_t i = 0; i < N; i++) {
+    const int32_t c = (int32_t)h[i * row];
+    const bool cut = c < 0 || c > CONTACT_EXPORT;   // capacity overflow, or more contacts than rows
+    const int n = cut ? CONTACT_EXPORT : c;
+    hc[i] = cut ? -n : n;
+    for (int k = 0; k < n; k++) {
+      float* o = &ho[(i * CONTACT_EXPORT + k) * W];
+      memcpy(o, &hf[(i * CONTACT_EXPORT + k) * 12], 12 * 4);
+      const float* t = &h[i * row + 1 + 3 * k];
+      o[12] = t[2]; o[13] = t[0]; o[14] = t[1];
+    }
   }
   if ((rc = copy_out(e, count, hc.data(), N * 4))) return rc;
   return copy_out(e, contacts, ho.data(), ho.size() * 4);

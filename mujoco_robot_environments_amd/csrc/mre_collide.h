@@ -220,7 +220,8 @@ MRE_DEV int box_box(const float* p1, const float* R1, const float* s1, const flo
   return nc;
 }
 
-// plane (geom1, normal = +z of its frame) vs box: corners within margin, at most 4
+// plane (geom1, normal = +z of its frame) vs box: corners that point down (mjc_PlaneBox: "pick bottom 4") within
+// margin, at most 4 -- the same corners whether the caller's margin is the pair's or margin - gap
 MRE_DEV int plane_box(const float* pp, const float* Rp, const float* pb, const float* Rb,
                       const float* sb, float margin, float* normal, float* buf) {
   float n[3] = {Rp[2], Rp[5], Rp[8]};
@@ -230,6 +231,7 @@ MRE_DEV int plane_box(const float* pp, const float* Rp, const float* pb, const f
     float loc[3] = {(c & 1) ? sb[0] : -sb[0], (c & 2) ? sb[1] : -sb[1], (c & 4) ? sb[2] : -sb[2]};
     float w[3], wd[3];
     m3mulv(w, Rb, loc);
+    if (v3dot(w, n) > 0.f) continue;
     v3add(w, w, pb);
     v3sub(wd, w, pp);
     const float ds = v3dot(wd, n);
@@ -274,19 +276,20 @@ MRE_DEV int cyl_box(const float* pb, const float* Rb, const float* sb, const flo
     if (l2 > 1e-6f) tryd(a[1] / l2, -a[0] / l2, 0.f);
   }
   {
-    // closest points of the axis segment and the box (golden section on the convex f(t) = dist^2(c + t a, box))
+    // closest points of the axis segment and the box: the minimum of the convex f(t) = dist^2(c + t a, box), found by
+    // bisection on the sign of f'(t) = 2 sum_k u_k sign(c_k + t a_k) a_k over the coordinates outside the box (u_k > 0).
+    // (mro_cylbox runs a golden section on f itself in fp64.  In fp32 that resolves t only to sqrt(eps) * dist -- where
+    // the axis runs along a box edge f is flat in t, the search stops microns outside the edge's extent, and the
+    // direction comes out tilted by 2e-4 rad: enough to be taken for a rim contact at the cylinder's END below.)
     float lo = -h, hi = h;
-    const float g = 0.61803399f;
-    float t1 = hi - g * (hi - lo), t2 = lo + g * (hi - lo);
     for (int it = 0; it < 26; it++) {
-      float f1 = 0.f, f2 = 0.f;
+      const float t = 0.5f * (lo + hi);
+      float g = 0.f;
       for (int k = 0; k < 3; k++) {
-        const float u1 = fabsf(c[k] + t1 * a[k]) - sb[k], u2 = fabsf(c[k] + t2 * a[k]) - sb[k];
-        if (u1 > 0.f) f1 += u1 * u1;
-        if (u2 > 0.f) f2 += u2 * u2;
+        const float q = c[k] + t * a[k], u = fabsf(q) - sb[k];
+        if (u > 0.f) g += (q > 0.f ? u : -u) * a[k];
       }
-      if (f1 <= f2) { hi = t2; t2 = t1; t1 = hi - g * (hi - lo); }
-      else { lo = t1; t1 = t2; t2 = lo + g * (hi - lo); }
+      if (g > 0.f) hi = t; else lo = t;
     }
     const float t = 0.5f * (lo + hi);
     float v[3];

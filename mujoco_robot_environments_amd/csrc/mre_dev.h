@@ -258,9 +258,10 @@ struct OscConfig {
 // F_OSC_EVAL (zero-step launch): evaluate the controller on the current state and store the command
 // (OSC.compute_control_output + MinMax.compute_control_output) in ctrl without stepping
 enum StepFlags : unsigned { F_NO_CONSTRAINTS = 1u, F_FREEZE_ROBOT = 2u, F_CONV_CONTINUE = 4u, F_CONV_OPEN = 8u,
-                            F_OSC_EVAL = 16u, F_DETECT = 32u, F_SETTLE_EXIT = 64u };
+                            F_OSC_EVAL = 16u, F_DETECT = 32u, F_SETTLE_EXIT = 64u, F_DETECT_ACTIVE = 128u };
 // F_DETECT (zero-step launch): narrow phase on the current poses, every detected contact (dist < margin)
 //   exported to `contacts` -- physics.forward() + physics.data.contact of the reference's PropPlacer
+// F_DETECT_ACTIVE (with F_DETECT): the list the next solve would get instead (dist < margin - gap: collide(.., detect = false))
 // F_SETTLE_EXIT: an env leaves the step loop once its cubes have settled (max |qvel| < 1e-3, max |qacc| <
 //   1e-2, time > min_settle_steps * dt: environment/prop_initializer.py:240-258); steps taken -> settle_steps
 enum CtrlMode : int { CTRL_HELD = 0, CTRL_SEQ = 1, CTRL_OSC = 2 };
@@ -299,6 +300,7 @@ struct StepArgs {
   float* geoms;              // [N][NG][16] or null: world pose of every geom for the renderer
                              //  (pos3, rotation 9 row-major geom->world, half sizes 3, type)
   float* contacts;           // [N][1 + 3 * CONTACT_EXPORT] or null (F_DETECT): count, then (geom1, geom2, dist) each
+  float* contacts_full;      // [N][CONTACT_EXPORT][12] or null (F_DETECT): pos[3], frame[9] of the same contacts (mre_get_contacts_full)
   int* settle_steps;         // [N] or null (F_SETTLE_EXIT): physics steps the env took in this launch
   int min_settle_steps;
   // capacity fallback (mre_api.cpp: launch_step): the launch is split between the compact and the large kernel by

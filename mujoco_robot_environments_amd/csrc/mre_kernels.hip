@@ -1858,13 +1858,18 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
   if (a.nsteps == 0 && (a.flags & F_DETECT) != 0 && a.contacts != nullptr) {
     // physics.forward() + physics.data.contact: kinematics, then every detected contact
     position_stage(M, s, l);
-    collide(M, s, l, true);
+    collide(M, s, l, (a.flags & F_DETECT_ACTIVE) == 0);
     float* o = a.contacts + (size_t)env * (1 + 3 * CONTACT_EXPORT);
     const int n = s.ncon < CONTACT_EXPORT ? s.ncon : CONTACT_EXPORT;
     if (l == 0) o[0] = s.overflow ? -(float)s.ncon : (float)s.ncon;   // negative: the list is cut
     if (l < n) {
       const int pr = s.con_pair[l];
       o[1 + 3 * l] = (float)M->pair_g1[pr]; o[2 + 3 * l] = (float)M->pair_g2[pr]; o[3 + 3 * l] = s.con_dist[l];
+      if (a.contacts_full != nullptr) {   // the rest of the mjContact record (mre_get_contacts_full)
+        float* f = a.contacts_full + ((size_t)env * CONTACT_EXPORT + l) * 12;
+        for (int k = 0; k < 3; k++) f[k] = s.con_pos[l][k];
+        for (int k = 0; k < 9; k++) f[3 + k] = s.con_frame[l][k];
+      }
     }
     MRE_SYNC();
     if (l == 0) s.overflow = 0;   // a cut detection list is reported in the count, not as a status bit

@@ -33,7 +33,7 @@ EXPORTS = [
     "mre_set_trace", "mre_osc_set_target", "mre_osc_configure", "mre_gripper_set",
     "mre_run_controller", "mre_get_sites", "mre_get_status", "mre_get_solver_stats",
     "mre_profile_enable", "mre_profile_read", "mre_set_env_id_offset", "mre_set_env_order",
-    "mre_set_fallback", "mre_get_fallback_stats", "mre_get_queue_info", "mre_set_solver", "mre_get_solver", "mre_wait_stream", "mre_osc_compute", "mre_get_contacts", "mre_get_settle_steps", "mre_get_launch_info", "mre_prop_place", "mre_sort_colours", "mre_crc32c", "mre_osc_configure_env", "mre_set_env_ids", "mre_set_render_colours", "mre_render",
+    "mre_set_fallback", "mre_get_fallback_stats", "mre_get_queue_info", "mre_set_solver", "mre_get_solver", "mre_wait_stream", "mre_osc_compute", "mre_get_contacts", "mre_get_contacts_full", "mre_get_settle_steps", "mre_get_launch_info", "mre_prop_place", "mre_sort_colours", "mre_crc32c", "mre_osc_configure_env", "mre_set_env_ids", "mre_set_render_colours", "mre_render",
     "mre_get_state_f64", "mre_set_state_f64", "mre_get_time", "mre_pack_final_state",
     "mre_records_workspace_bytes", "mre_varint_pack_rows", "mre_crc32c_rows", "mre_crc32c_combine",
     "mre_varint_unpack_workspace_bytes", "mre_varint_unpack_rows",
@@ -161,6 +161,7 @@ def lib() -> C.CDLL:
     L.mre_wait_stream.argtypes = [vp, vp]
     L.mre_osc_compute.argtypes = [vp, fp, fp]
     L.mre_get_contacts.argtypes = [vp, fp, fp]
+    L.mre_get_contacts_full.argtypes = [vp, ci, fp, fp]
     L.mre_get_settle_steps.argtypes = [vp, fp]
     L.mre_get_launch_info.argtypes = [vp, fp]
     L.mre_prop_place.argtypes = [vp, C.c_uint64, fp, fp, fp, ci, C.c_float, fp, fp]

@@ -334,10 +334,17 @@ class BatchedPhysics:
         check(_lib.lib().mre_get_sites(self._h, _ptr(tcp), _ptr(eef), _ptr(props)), "mre_get_sites")
         return tcp, eef, props
 
-    def contacts(self):
+    def contacts(self, full: bool = False, active_only: bool = False):
         """physics.data.contact of every env on the current poses: (count [N] (negative: list cut),
-        contacts [N, 32, 3] = geom1, geom2, dist) -- every DETECTED contact (dist < margin)."""
+        contacts [N, 32, 3] = geom1, geom2, dist) -- every DETECTED contact (dist < margin).
+        full: contacts [N, 32, 15] = pos[3], frame[9], dist, geom1, geom2 instead (mre_get_contacts_full);
+        active_only (with full): the contacts the next solve would be given (dist < margin - gap)."""
         cnt = np.empty(self.num_envs, np.int32)
+        if full:
+            con = np.empty((self.num_envs, 32, 15), np.float32)
+            check(_lib.lib().mre_get_contacts_full(self._h, int(active_only), _ptr(cnt), _ptr(con)), "mre_get_contacts_full")
+            return cnt, con
+        assert not active_only, "active_only needs full=True"
         con = np.empty((self.num_envs, 32, 3), np.float32)
         check(_lib.lib().mre_get_contacts(self._h, _ptr(cnt), _ptr(con)), "mre_get_contacts")
         return cnt, con

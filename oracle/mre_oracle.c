@@ -1036,7 +1036,10 @@ static void collision(const mro_model* m, mro_data* d) {
       v3sub(df, d->geom_xpos[g2], d->geom_xpos[g1]);
       double cd = v3dot(df, n);
       if (cd - d->geom_rbound[g2] > margin) continue;
-      /* mjc_PlaneBox: corners below margin, at most 4 */
+      /* mjc_PlaneBox ("test all corners, pick bottom 4"): corners that point down (offset from the centre against the
+       * normal) and lie below margin, at most 4.  Without the first condition a tilted cube inside the margin with
+       * all eight corners lists its first four in corner order, whichever way they point, and the solver (which
+       * keeps dist < margin - gap of THIS list) never sees the corners that actually penetrate. */
       int cnt = 0;
       const double* bm = d->geom_xmat[g2];
       const double* s = d->geom_size[g2];
@@ -1044,6 +1047,7 @@ static void collision(const mro_model* m, mro_data* d) {
         double loc[3] = {(c & 1 ? s[0] : -s[0]), (c & 2 ? s[1] : -s[1]), (c & 4 ? s[2] : -s[2])};
         double w[3];
         m3mulv(w, bm, loc);
+        if (v3dot(w, n) > 0) continue;
         v3add(w, w, d->geom_xpos[g2]);
         double wd[3];
         v3sub(wd, w, d->geom_xpos[g1]);
