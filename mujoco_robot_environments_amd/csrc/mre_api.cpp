@@ -1,6 +1,6 @@
 // mre_api.cpp -- host side of the C ABI declared in include/mre.h.
 // Owns the device buffers and the HIP stream of a batch of environments,
-// converts the model blob into the fp32 DevModel the kernels read, and
+// uploads the fp32 DevModel that mre_model.cpp builds from the model blob, and
 // enqueues kernels.  No torch types; plain pointers and sizes only.
 #include <hip/hip_runtime.h>
 #include <chrono>
@@ -15,6 +15,7 @@
 
 #include "../../include/mre.h"
 #include "mre_dev.h"
+#include "mre_model.h"
 #include "mre_records.h"
 
 using namespace mre;
@@ -64,6 +65,7 @@ struct mre_env {
   hipStream_t stream = nullptr;
   DevModel* dM = nullptr;
   DevModel hM;
+  int solver = MRE_SOLVER_PGS;   // mjtSolver (0 = PGS, 2 = Newton): selects the kernel instantiation (mre_set_solver)
   float *qpos = nullptr, *qvel = nullptr, *qacc_ws = nullptr, *ctrl = nullptr;
   float* qfine = nullptr;   // [N][QFINE_ROW] low-order words of the state: robot joints, then cube poses and velocities (StepArgs::qfine)
   int *nstep = nullptr, *sv_nstep = nullptr;   // [N] physics steps since the last reset (physics.data.time)
@@ -127,7 +129,6 @@ struct mre_env {
   // pose-search / sort_colours scratch (device, allocated on first use)
   int *ps_attempts = nullptr, *ps_prop = nullptr, *ps_tick = nullptr, *ps_which = nullptr;
   double *ps_bounds = nullptr, *ps_pose = nullptr, *ps_zones = nullptr, *ps_pick = nullptr;
-  int prop_geom0 = 12;           // geom id of cube 0 (cubes are the last NPROP geoms)
   int last_settle_max = 0;
   long long n_reruns = 0, n_promotions = 0, n_demotions = 0;
   // ---- pipelined env groups (launch_step): the envs are cut into contiguous groups, each with its own stream
@@ -241,12 +242,12 @@ struct mre_env {
 
 // solver-specific instantiations of the step kernel (opt_solver of the model, mre_set_solver)
 static void launch_compact(const mre_env* e, const StepArgs& a, hipStream_t st, bool settle = false) {
-  const bool newton = e->hM.solver == MRE_SOLVER_NEWTON;
+  const bool newton = e->solver == MRE_SOLVER_NEWTON;
   if (settle) { if (newton) mre_launch_settle_newton(&a, st); else mre_launch_settle(&a, st); }
   else { if (newton) mre_launch_step_newton(&a, st); else mre_launch_step(&a, st); }
 }
 static void launch_large(const mre_env* e, const StepArgs& a, hipStream_t st) {
-  if (e->hM.solver == MRE_SOLVER_NEWTON) mre_launch_step_large_newton(&a, st); else mre_launch_step_large(&a, st);
+  if (e->solver == MRE_SOLVER_NEWTON) mre_launch_step_large_newton(&a, st); else mre_launch_step_large(&a, st);
 }
 
 // Launch the step kernel, optionally bracketed by HIP events on the handle's stream.
@@ -287,7 +288,7 @@ static int profile_events(mre_env* e, hipEvent_t* e0, hipEvent_t* e1) {
 // (20.4 M vs 22.3 M env-steps/s, profiles/NOTES.md): a re-run repeats a whole launch of 50 ticks on the large kernel
 // behind the group's stream, residency on the large kernel costs a quarter of the slots of the envs that are on it.  The 7/8 rule stays.
 static inline int compact_nrrow_max(const mre_env* e) {
-  return e->hM.solver == MRE_SOLVER_NEWTON ? NRROW_MAX_COMPACT_NEWTON : NRROW_MAX_COMPACT_PGS;
+  return e->solver == MRE_SOLVER_NEWTON ? NRROW_MAX_COMPACT_NEWTON : NRROW_MAX_COMPACT_PGS;
 }
 static inline bool near_compact_caps(const mre_env* e, int hw_ncon, int hw_nefc, int hw_nrrow, int hw_npp) {
   return 8 * hw_ncon > 7 * NCON_MAX || 8 * hw_nefc > 7 * NEFC_MAX || 8 * hw_nrrow > 7 * compact_nrrow_max(e) || 8 * hw_npp > 7 * NPP_MAX;
@@ -561,7 +562,7 @@ static int launch_group_enqueue(mre_env* e, mre_env::Group& G, const StepArgs& a
     //  that serialises dispatches makes of the two streams; the launch then leaves after its bounded wait and the one
     //  behind the compact kernel does the large kernel's whole share)
     hipStream_t const st_large = e->queue_test_serial ? G.st : G.st2;
-    if (e->hM.solver == MRE_SOLVER_NEWTON) mre_launch_step_queue_large_newton(&al, lw, st_large);
+    if (e->solver == MRE_SOLVER_NEWTON) mre_launch_step_queue_large_newton(&al, lw, st_large);
     else mre_launch_step_queue_large(&al, lw, st_large);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(G.ev_join, st_large));
@@ -575,7 +576,7 @@ static int launch_group_enqueue(mre_env* e, mre_env::Group& G, const StepArgs& a
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)e->q_gen, ac.q_gen_expect, 1, G.st));
     // 3. the compact kernel
     const int nwaves = G.n < e->queue_waves ? G.n : e->queue_waves;
-    if (e->hM.solver == MRE_SOLVER_NEWTON) mre_launch_step_queue_newton(&ac, nwaves, G.st);
+    if (e->solver == MRE_SOLVER_NEWTON) mre_launch_step_queue_newton(&ac, nwaves, G.st);
     else mre_launch_step_queue(&ac, nwaves, G.st);
     HIPCHK(hipGetLastError());
     // Behind the compact kernel, the large kernel once more, not waiting: nothing to do when the two ran side by side
@@ -585,7 +586,7 @@ static int launch_group_enqueue(mre_env* e, mre_env::Group& G, const StepArgs& a
     //  kernel gone, they all run at once)
     al.q_wait = 0;
     const int sweep = G.n < 3 * e->queue_large_waves_max ? G.n : 3 * e->queue_large_waves_max;
-    if (e->hM.solver == MRE_SOLVER_NEWTON) mre_launch_step_queue_large_newton(&al, sweep, G.st);
+    if (e->solver == MRE_SOLVER_NEWTON) mre_launch_step_queue_large_newton(&al, sweep, G.st);
     else mre_launch_step_queue_large(&al, sweep, G.st);
     e->n_queue_launches++;
   } else {
@@ -770,422 +771,6 @@ static int launch_step(mre_env* e, const StepArgs& a, bool settle = false, bool 
   return MRE_OK;
 }
 
-// ------------------------------------------------------------------ blob parsing
-namespace {
-struct Blob {
-  const unsigned char* p;
-  size_t n;
-  bool find(const char* name, uint32_t* code, uint32_t* count, uint64_t* off) const {
-    uint32_t ne;
-    memcpy(&ne, p + 8, 4);
-    const unsigned char* t = p + 16;
-    for (uint32_t k = 0; k < ne; k++, t += 48)
-      if (strncmp((const char*)t, name, 32) == 0) {
-        memcpy(code, t + 32, 4); memcpy(count, t + 36, 4); memcpy(off, t + 40, 8);
-        return *off + (size_t)(*count) * (*code ? 8 : 4) <= n;
-      }
-    return false;
-  }
-  bool ints(const char* name, int* dst, int expect) const {
-    uint32_t c, cnt; uint64_t off;
-    if (!find(name, &c, &cnt, &off) || c != 0 || (int)cnt != expect) return false;
-    memcpy(dst, p + off, 4 * (size_t)cnt);
-    return true;
-  }
-  bool flts(const char* name, float* dst, int expect) const {
-    uint32_t c, cnt; uint64_t off;
-    if (!find(name, &c, &cnt, &off) || c != 1 || (int)cnt != expect) return false;
-    for (uint32_t k = 0; k < cnt; k++) {
-      double v;
-      memcpy(&v, p + off + 8 * (size_t)k, 8);
-      dst[k] = (float)v;
-    }
-    return true;
-  }
-};
-}  // namespace
-
-#define RI(name, dst, n) if (!b.ints(name, (int*)(dst), n)) return fail(MRE_ERR_MODEL, std::string("model entry ") + name)
-#define RF(name, dst, n) if (!b.flts(name, (float*)(dst), n)) return fail(MRE_ERR_MODEL, std::string("model entry ") + name)
-
-// The per-lane records of mre_dev.h (BodyRec .. OptRec): filled from the tables, then every field is compared with the
-// table entry it packs -- a record that disagrees with its table would change results silently.
-static bool same_bits(const void* a, const void* b, size_t n) { return memcmp(a, b, n) == 0; }
-static int pack_records(DevModel& m) {
-  if (m.ten_dof[0] == m.ten_dof[1] || m.ten_dof[0] < 0 || m.ten_dof[0] >= NRV || m.ten_dof[1] < 0 || m.ten_dof[1] >= NRV)
-    return fail(MRE_ERR_MODEL, "the gripper tendon must couple two different robot dofs");
-  for (int e = 0; e < NEQ; e++)
-    for (int k = 0; k < 2; k++)
-      if (m.eq_obj[e][k] < 1 || m.eq_obj[e][k] >= NRB) return fail(MRE_ERR_MODEL, "equality constraints must couple robot bodies");
-  if (m.tcp_site < 0 || m.tcp_site >= NSITE || m.eef_site < 0 || m.eef_site >= NSITE) return fail(MRE_ERR_MODEL, "tcp_site / eef_site name no site");
-  // (the phases take a finger body's place in the tree from its number: even bodies hang off the arm's last link, odd ones off the body below)
-  for (int b = 1; b < NRB; b++)
-    if (m.body_parent[b] != ROBOT_DOF_PARENT[b - 1] + 1) return fail(MRE_ERR_MODEL, "robot body tree differs from the one the kernels are unrolled for (mre_dev.h)");
-  for (int d = 0; d < NV; d++)
-    if (m.dof_body[d] != (d < NRV ? d + 1 : NRB + (d - NRV) / 6)) return fail(MRE_ERR_MODEL, "dof layout differs from the compiled kernels");
-  auto ten_of = [&](int d) { return d == m.ten_dof[0] ? 0 : (d == m.ten_dof[1] ? 1 : -1); };
-  for (int b = 0; b < NB; b++) {
-    BodyRec& r = m.body_rec[b];
-    memset(&r, 0, sizeof(r));
-    for (int c = 0; c < 4; c++) { r.quat[c] = m.body_quat[b][c]; r.iquat[c] = m.body_iquat[b][c]; }
-    for (int c = 0; c < 3; c++) { r.pos[c] = m.body_pos[b][c]; r.ipos[c] = m.body_ipos[b][c]; r.jnt_pos[c] = m.jnt_pos[b][c];
-                                  r.jnt_axis[c] = m.jnt_axis[b][c]; r.inertia[c] = m.body_inertia[b][c]; }
-    for (int c = 0; c < 2; c++) { r.jnt_range[c] = m.jnt_range[b][c]; r.invweight0[c] = m.body_invweight0[b][c]; }
-    r.mass = m.body_mass[b]; r.qposadr = m.body_qposadr[b]; r.dofadr = m.body_dofadr[b]; r.propid = m.body_propid[b];
-    r.qpos0 = (r.qposadr >= 0 && r.qposadr < NQ) ? m.qpos0[r.qposadr] : 0.f;
-    r.jnt_stiffness = m.jnt_stiffness[b]; r.jnt_springref = m.jnt_springref[b];
-    r.parent = m.body_parent[b]; r.jnt_limited = m.jnt_limited[b];
-  }
-  for (int d = 0; d < NV; d++) {
-    DofRec& r = m.dof_rec[d];
-    memset(&r, 0, sizeof(r));
-    const int b = m.dof_body[d];
-    if (b < 0 || b >= NB) return fail(MRE_ERR_MODEL, "dof_bodyid names a body that does not exist");
-    r.body = b; r.propid = m.body_propid[b]; r.dofadr = m.body_dofadr[b]; r.ten = ten_of(d);
-    r.armature = m.dof_armature[d]; r.damping = m.dof_damping[d]; r.invweight0 = m.dof_invweight0[d];
-    r.ten_coef = r.ten >= 0 ? m.ten_coef[r.ten] : 0.f;
-    r.jnt_stiffness = m.jnt_stiffness[b]; r.jnt_springref = m.jnt_springref[b];
-    if (d < 7) {   // arm actuator d drives dof d (checked in build_model)
-      r.act_gain = m.act_gain[d]; r.act_bias0 = m.act_bias[d][0]; r.act_bias1 = m.act_bias[d][1]; r.act_bias2 = m.act_bias[d][2];
-      r.act_ctrl_lo = m.act_ctrlrange[d][0]; r.act_ctrl_hi = m.act_ctrlrange[d][1];
-      r.act_force_lo = m.act_forcerange[d][0]; r.act_force_hi = m.act_forcerange[d][1];
-      r.act_forcelimited = m.act_forcelimited[d];
-    }
-  }
-  for (int e = 0; e < NMR; e++) {
-    MEntryRec& r = m.m_rec[e];
-    memset(&r, 0, sizeof(r));
-    r.i = m.M_i[e]; r.j = m.M_j[e];
-    r.armature = m.dof_armature[r.i]; r.damping = m.dof_damping[r.i];
-    r.act_bias2 = r.i < 7 ? m.act_bias[r.i][2] : 0.f;
-    r.ten = ten_of(r.i); r.ten_coef = r.ten >= 0 ? m.ten_coef[r.ten] : 0.f;
-  }
-  for (int k = 0; k < NROWREC; k++) memset(&m.row_rec[k], 0, sizeof(RowRec));
-  for (int e = 0; e < NEQ; e++) {
-    RowRec& r = m.row_rec[e];
-    const int b1 = m.eq_obj[e][0], b2 = m.eq_obj[e][1];
-    for (int c = 0; c < 2; c++) r.solref[c] = m.eq_solref[e][c];
-    for (int c = 0; c < 5; c++) r.solimp[c] = m.eq_solimp[e][c];
-    // (the kernels treat equalities 0 and 1 as the `connect` rows of the finger linkage, 2 as the joint coupling)
-    r.invw1 = e < 2 ? m.body_invweight0[b1][0] : m.dof_invweight0[b1 - 1];
-    r.invw2 = e < 2 ? m.body_invweight0[b2][0] : m.dof_invweight0[b2 - 1];
-    EqRec& q = m.eq_rec[e];
-    memset(&q, 0, sizeof(q));
-    q.type = m.eq_type[e]; q.b1 = b1; q.b2 = b2; q.pb1 = m.body_parent[b1]; q.pb2 = m.body_parent[b2];
-    q.root = b1;
-    while (q.root >= GRIP_BODY0) q.root = m.body_parent[q.root];
-    for (int c = 0; c < 8; c++) q.data[c] = m.eq_data[e][c];
-    q.qpos0_1 = m.qpos0[b1 - 1]; q.qpos0_2 = m.qpos0[b2 - 1];
-    q.root_chain_len = m.chain_len[q.root];
-    for (int c = 0; c < MAXCHAIN; c++) q.root_chain[c] = m.chain_dof[q.root][c];
-  }
-  for (int b = 1; b < NRB; b++) {
-    RowRec& r = m.row_rec[ROWREC_JNT + b];
-    for (int c = 0; c < 2; c++) r.solref[c] = m.jnt_solref[b][c];
-    for (int c = 0; c < 5; c++) r.solimp[c] = m.jnt_solimp[b][c];
-    r.invw1 = m.dof_invweight0[b - 1];
-  }
-  for (int k = 0; k < NPAIR; k++) {
-    if (m.pair_g1[k] < 0) continue;
-    RowRec& r = m.row_rec[ROWREC_PAIR + k];
-    const int b1 = m.pair_rec[k].b1, b2 = m.pair_rec[k].b2;
-    for (int c = 0; c < 2; c++) r.solref[c] = m.pair_solref[k][c];
-    for (int c = 0; c < 5; c++) r.solimp[c] = m.pair_solimp[k][c];
-    r.margin = m.pair_margin[k]; r.gap = m.pair_gap[k]; r.friction = m.pair_friction[k][0];
-    r.invw1 = (b1 > 0 && b1 < NRB) ? m.body_invweight0[b1][0] : 0.f;
-    r.invw2 = (b2 > 0 && b2 < NRB) ? m.body_invweight0[b2][0] : 0.f;
-  }
-  for (int k = 0; k < NSITE; k++) {
-    SiteRec& r = m.site_rec[k];
-    memset(&r, 0, sizeof(r));
-    if (m.site_body[k] < 0 || m.site_body[k] >= NB) return fail(MRE_ERR_MODEL, "site_bodyid names a body that does not exist");
-    r.body = m.site_body[k];
-    for (int c = 0; c < 3; c++) r.pos[c] = m.site_pos[k][c];
-    for (int c = 0; c < 4; c++) r.quat[c] = m.site_quat[k][c];
-  }
-  {
-    OptRec& o = m.opt_rec;
-    memset(&o, 0, sizeof(o));
-    o.timestep = m.timestep; o.impratio = m.impratio; o.tolerance = m.tolerance; o.iterations = m.iterations;
-    for (int c = 0; c < 3; c++) { o.gravity[c] = m.gravity[c]; o.grip_biasprm[c] = m.grip_biasprm[c]; }
-    o.cone = m.cone;
-    for (int c = 0; c < 2; c++) { o.ten_coef[c] = m.ten_coef[c]; o.ten_dof[c] = m.ten_dof[c]; o.grip_forcerange[c] = m.grip_forcerange[c];
-                                  o.grip_ctrlrange[c] = m.act_ctrlrange[NU - 1][c]; }
-    o.grip_gainprm = m.grip_gainprm; o.robot_mass = m.robot_mass; o.M0_diag_robot_sum = m.M0_diag_robot_sum;
-    o.tcp_site = m.tcp_site; o.eef_site = m.eef_site;
-    for (int c = 0; c < 3; c++) o.tcp_pos[c] = m.site_pos[m.tcp_site][c];
-  }
-
-  // ---- verification: every field against the table entry it packs (bit patterns: a NaN compares equal to itself)
-  bool ok = true;
-#define SAME(a, b) ok = ok && sizeof(a) == sizeof(b) && same_bits(&(a), &(b), sizeof(a))
-  for (int b = 0; b < NB && ok; b++) {
-    const BodyRec& r = m.body_rec[b];
-    SAME(r.quat, m.body_quat[b]); SAME(r.pos, m.body_pos[b]); SAME(r.mass, m.body_mass[b]); SAME(r.jnt_pos, m.jnt_pos[b]);
-    SAME(r.jnt_axis, m.jnt_axis[b]); SAME(r.qposadr, m.body_qposadr[b]); SAME(r.ipos, m.body_ipos[b]);
-    SAME(r.propid, m.body_propid[b]); SAME(r.iquat, m.body_iquat[b]); SAME(r.inertia, m.body_inertia[b]);
-    SAME(r.dofadr, m.body_dofadr[b]); SAME(r.jnt_range, m.jnt_range[b]); SAME(r.invweight0, m.body_invweight0[b]);
-    SAME(r.jnt_stiffness, m.jnt_stiffness[b]); SAME(r.jnt_springref, m.jnt_springref[b]); SAME(r.parent, m.body_parent[b]);
-    SAME(r.jnt_limited, m.jnt_limited[b]);
-    if (b >= 1) SAME(r.qpos0, m.qpos0[m.body_qposadr[b]]);
-  }
-  for (int d = 0; d < NV && ok; d++) {
-    const DofRec& r = m.dof_rec[d];
-    const int b = m.dof_body[d];
-    SAME(r.body, m.dof_body[d]); SAME(r.propid, m.body_propid[b]); SAME(r.dofadr, m.body_dofadr[b]);
-    ok = ok && r.ten == (d == m.ten_dof[0] ? 0 : (d == m.ten_dof[1] ? 1 : -1));
-    SAME(r.armature, m.dof_armature[d]); SAME(r.damping, m.dof_damping[d]); SAME(r.invweight0, m.dof_invweight0[d]);
-    if (r.ten >= 0) SAME(r.ten_coef, m.ten_coef[r.ten]);
-    SAME(r.jnt_stiffness, m.jnt_stiffness[b]); SAME(r.jnt_springref, m.jnt_springref[b]);
-    if (d < 7) {
-      SAME(r.act_gain, m.act_gain[d]); SAME(r.act_bias0, m.act_bias[d][0]); SAME(r.act_bias1, m.act_bias[d][1]);
-      SAME(r.act_bias2, m.act_bias[d][2]); SAME(r.act_ctrl_lo, m.act_ctrlrange[d][0]); SAME(r.act_ctrl_hi, m.act_ctrlrange[d][1]);
-      SAME(r.act_force_lo, m.act_forcerange[d][0]); SAME(r.act_force_hi, m.act_forcerange[d][1]);
-      SAME(r.act_forcelimited, m.act_forcelimited[d]);
-    }
-  }
-  for (int e = 0; e < NMR && ok; e++) {
-    const MEntryRec& r = m.m_rec[e];
-    SAME(r.i, m.M_i[e]); SAME(r.j, m.M_j[e]);
-    const int i = m.M_i[e];
-    SAME(r.armature, m.dof_armature[i]); SAME(r.damping, m.dof_damping[i]);
-    if (i < 7) SAME(r.act_bias2, m.act_bias[i][2]);
-    ok = ok && r.ten == (i == m.ten_dof[0] ? 0 : (i == m.ten_dof[1] ? 1 : -1));
-    if (r.ten >= 0) SAME(r.ten_coef, m.ten_coef[r.ten]);
-  }
-  for (int e = 0; e < NEQ && ok; e++) {
-    const RowRec& r = m.row_rec[e];
-    const EqRec& q = m.eq_rec[e];
-    const int b1 = m.eq_obj[e][0], b2 = m.eq_obj[e][1];
-    SAME(r.solref, m.eq_solref[e]); SAME(r.solimp, m.eq_solimp[e]);
-    if (e < 2) { SAME(r.invw1, m.body_invweight0[b1][0]); SAME(r.invw2, m.body_invweight0[b2][0]); }
-    else { SAME(r.invw1, m.dof_invweight0[b1 - 1]); SAME(r.invw2, m.dof_invweight0[b2 - 1]); }
-    SAME(q.type, m.eq_type[e]); SAME(q.b1, m.eq_obj[e][0]); SAME(q.b2, m.eq_obj[e][1]);
-    SAME(q.pb1, m.body_parent[b1]); SAME(q.pb2, m.body_parent[b2]); SAME(q.data, m.eq_data[e]);
-    SAME(q.qpos0_1, m.qpos0[b1 - 1]); SAME(q.qpos0_2, m.qpos0[b2 - 1]);
-    int root = b1;
-    while (root >= GRIP_BODY0) root = m.body_parent[root];
-    ok = ok && q.root == root;
-    SAME(q.root_chain_len, m.chain_len[root]);
-    for (int c = 0; c < MAXCHAIN; c++) SAME(q.root_chain[c], m.chain_dof[root][c]);
-  }
-  for (int b = 1; b < NRB && ok; b++) {
-    const RowRec& r = m.row_rec[ROWREC_JNT + b];
-    SAME(r.solref, m.jnt_solref[b]); SAME(r.solimp, m.jnt_solimp[b]); SAME(r.invw1, m.dof_invweight0[b - 1]);
-  }
-  for (int k = 0; k < NPAIR && ok; k++) {
-    if (m.pair_g1[k] < 0) continue;
-    const RowRec& r = m.row_rec[ROWREC_PAIR + k];
-    const int b1 = m.geom_body[m.pair_g1[k]], b2 = m.geom_body[m.pair_g2[k]];
-    SAME(r.solref, m.pair_solref[k]); SAME(r.solimp, m.pair_solimp[k]); SAME(r.margin, m.pair_margin[k]);
-    SAME(r.gap, m.pair_gap[k]); SAME(r.friction, m.pair_friction[k][0]);
-    if (b1 > 0 && b1 < NRB) SAME(r.invw1, m.body_invweight0[b1][0]);
-    if (b2 > 0 && b2 < NRB) SAME(r.invw2, m.body_invweight0[b2][0]);
-  }
-  for (int k = 0; k < NSITE && ok; k++) {
-    const SiteRec& r = m.site_rec[k];
-    SAME(r.body, m.site_body[k]); SAME(r.pos, m.site_pos[k]); SAME(r.quat, m.site_quat[k]);
-  }
-  {
-    const OptRec& o = m.opt_rec;
-    SAME(o.timestep, m.timestep); SAME(o.impratio, m.impratio); SAME(o.tolerance, m.tolerance); SAME(o.iterations, m.iterations);
-    SAME(o.gravity, m.gravity); SAME(o.cone, m.cone); SAME(o.ten_coef, m.ten_coef); SAME(o.ten_dof, m.ten_dof);
-    SAME(o.grip_gainprm, m.grip_gainprm); SAME(o.grip_biasprm, m.grip_biasprm); SAME(o.grip_forcerange, m.grip_forcerange);
-    SAME(o.grip_ctrlrange, m.act_ctrlrange[NU - 1]); SAME(o.robot_mass, m.robot_mass);
-    SAME(o.M0_diag_robot_sum, m.M0_diag_robot_sum); SAME(o.tcp_site, m.tcp_site); SAME(o.eef_site, m.eef_site);
-    SAME(o.tcp_pos, m.site_pos[m.tcp_site]);
-  }
-#undef SAME
-  if (!ok) return fail(MRE_ERR_MODEL, "a packed model record differs from the table it was filled from");
-  return MRE_OK;
-}
-
-static int build_model(const void* blob, size_t nbytes, DevModel& m) {
-  if (nbytes < 16) return fail(MRE_ERR_MODEL, "blob too small");
-  Blob b{(const unsigned char*)blob, nbytes};
-  uint32_t magic;
-  memcpy(&magic, b.p, 4);
-  if (magic != 0x4D524542u) return fail(MRE_ERR_MODEL, "bad blob magic");
-  memset(&m, 0, sizeof(m));
-  int nbody, nv, nq, nM, ngeom, nsite, npair, neq, nprop, nu;
-  RI("nbody", &nbody, 1); RI("nv", &nv, 1); RI("nq", &nq, 1); RI("nM", &nM, 1); RI("ngeom", &ngeom, 1);
-  RI("nsite", &nsite, 1); RI("npair", &npair, 1); RI("neq", &neq, 1); RI("nprop", &nprop, 1);
-  RI("nu", &nu, 1);
-  if (nbody != NB || nv != NV || nq != NQ || ngeom != NG || nsite != NSITE || npair > NPAIR ||
-      neq != NEQ || nprop != NPROP || nu != NU)
-    return fail(MRE_ERR_MODEL, "scene dimensions differ from the compiled kernels");
-  RI("body_parentid", m.body_parent, NB); RI("body_jnttype", m.body_jnttype, NB);
-  RI("body_dofadr", m.body_dofadr, NB); RI("body_qposadr", m.body_qposadr, NB);
-  RI("body_propid", m.body_propid, NB);
-  RF("body_pos", m.body_pos, NB * 3); RF("body_quat", m.body_quat, NB * 4);
-  RF("body_ipos", m.body_ipos, NB * 3); RF("body_iquat", m.body_iquat, NB * 4);
-  RF("body_mass", m.body_mass, NB); RF("body_inertia", m.body_inertia, NB * 3);
-  RF("body_invweight0", m.body_invweight0, NB * 2);
-  RF("jnt_pos", m.jnt_pos, NB * 3); RF("jnt_axis", m.jnt_axis, NB * 3); RF("jnt_range", m.jnt_range, NB * 2);
-  RF("jnt_stiffness", m.jnt_stiffness, NB); RF("jnt_springref", m.jnt_springref, NB);
-  RF("jnt_solref", m.jnt_solref, NB * 2); RF("jnt_solimp", m.jnt_solimp, NB * 5);
-  RI("jnt_limited", m.jnt_limited, NB);
-  RI("dof_bodyid", m.dof_body, NV); RI("dof_parentid", m.dof_parent, NV); RI("dof_Madr", m.dof_Madr, NV);
-  m.dof_Madr[NV] = nM;
-  RF("dof_armature", m.dof_armature, NV); RF("dof_damping", m.dof_damping, NV);
-  RF("dof_invweight0", m.dof_invweight0, NV); RF("qpos0", m.qpos0, NQ);
-  RI("geom_type", m.geom_type, NG); RI("geom_bodyid", m.geom_body, NG); RI("geom_propid", m.geom_propid, NG);
-  RF("geom_size", m.geom_size, NG * 3); RF("geom_pos", m.geom_pos, NG * 3);
-  RF("geom_quat", m.geom_quat, NG * 4); RF("geom_rbound", m.geom_rbound, NG);
-  {
-    std::vector<int> pg(2 * npair);
-    RI("pair_geom", pg.data(), 2 * npair);
-    for (int k = 0; k < NPAIR; k++) { m.pair_g1[k] = -1; m.pair_g2[k] = -1; }
-    for (int k = 0; k < npair; k++) { m.pair_g1[k] = pg[2 * k]; m.pair_g2[k] = pg[2 * k + 1]; }
-  }
-  RI("pair_single", m.pair_single, npair);
-  RF("pair_friction", m.pair_friction, npair * 3); RF("pair_solref", m.pair_solref, npair * 2);
-  RF("pair_solimp", m.pair_solimp, npair * 5); RF("pair_margin", m.pair_margin, npair);
-  RF("pair_gap", m.pair_gap, npair);
-  for (int k = 0; k < NPAIR; k++) {
-    PairRec& r = m.pair_rec[k];
-    memset(&r, 0, sizeof(r));
-    r.g1 = m.pair_g1[k]; r.g2 = m.pair_g2[k];
-    if (r.g1 < 0) { r.g2 = -1; r.b1 = r.b2 = 0; r.pid1 = r.pid2 = -1; continue; }
-    if (r.g1 >= NG || r.g2 < 0 || r.g2 >= NG) return fail(MRE_ERR_MODEL, "pair table names a geom that does not exist");
-    r.b1 = m.geom_body[r.g1]; r.b2 = m.geom_body[r.g2];
-    r.pid1 = m.geom_propid[r.g1]; r.pid2 = m.geom_propid[r.g2];
-    r.type1 = m.geom_type[r.g1]; r.single = (m.pair_single[k] & 0xFF) | (m.geom_type[r.g2] << 8);
-    if (m.geom_type[r.g1] == 2 || (m.geom_type[r.g2] == 2 && m.geom_type[r.g1] != 1))
-      return fail(MRE_ERR_MODEL, "cylinder pairs: only box (geom 1) - cylinder (geom 2) is implemented");
-    for (int c = 0; c < 3; c++) { r.pos1[c] = m.geom_pos[r.g1][c]; r.pos2[c] = m.geom_pos[r.g2][c];
-                                  r.size1[c] = m.geom_size[r.g1][c]; r.size2[c] = m.geom_size[r.g2][c]; }
-    for (int c = 0; c < 4; c++) { r.quat1[c] = m.geom_quat[r.g1][c]; r.quat2[c] = m.geom_quat[r.g2][c]; }
-    r.rb1 = m.geom_rbound[r.g1]; r.rb2 = m.geom_rbound[r.g2];
-    r.margin = m.pair_margin[k]; r.gap = m.pair_gap[k];
-  }
-  RI("site_bodyid", m.site_body, NSITE); RF("site_pos", m.site_pos, NSITE * 3);
-  RF("site_quat", m.site_quat, NSITE * 4);
-  RI("eef_site", &m.eef_site, 1); RI("tcp_site", &m.tcp_site, 1);
-  RI("eq_type", m.eq_type, NEQ); RI("eq_obj", m.eq_obj, NEQ * 2); RF("eq_data", m.eq_data, NEQ * 8);
-  RF("eq_solref", m.eq_solref, NEQ * 2); RF("eq_solimp", m.eq_solimp, NEQ * 5);
-  RI("ten_dof", m.ten_dof, 2); RF("ten_coef", m.ten_coef, 2);
-  RI("act_dof", m.act_dof, NU); RF("act_ctrlrange", m.act_ctrlrange, NU * 2);
-  RF("grip_gainprm", &m.grip_gainprm, 1); RF("grip_biasprm", m.grip_biasprm, 3);
-  RF("grip_forcerange", m.grip_forcerange, 2);
-  // arm actuators: motors (gain 1, no bias, unlimited force) unless the blob says otherwise
-  for (int a = 0; a < NU; a++) { m.act_gain[a] = 1.f; m.act_forcelimited[a] = 0; }
-  { uint32_t c, cnt; uint64_t off;
-    if (b.find("act_gainprm", &c, &cnt, &off)) {
-      RF("act_gainprm", m.act_gain, NU); RF("act_biasprm", m.act_bias, NU * 3);
-      RF("act_forcerange", m.act_forcerange, NU * 2); RI("act_forcelimited", m.act_forcelimited, NU);
-    } }
-  RF("opt_timestep", &m.timestep, 1); RF("opt_gravity", m.gravity, 3); RF("opt_impratio", &m.impratio, 1);
-  RF("opt_tolerance", &m.tolerance, 1); RI("opt_iterations", &m.iterations, 1);
-  m.solver = MRE_SOLVER_PGS;  // older blobs carry no opt_solver
-  { uint32_t c, cnt; uint64_t off; if (b.find("opt_solver", &c, &cnt, &off)) RI("opt_solver", &m.solver, 1); }
-  if (m.solver != MRE_SOLVER_PGS && m.solver != MRE_SOLVER_NEWTON) return fail(MRE_ERR_MODEL, "opt_solver must be 0 (PGS) or 2 (Newton)");
-  { uint32_t c, cnt; uint64_t off; int cone = 1;  // mjtCone; older blobs carry no opt_cone (elliptic)
-    if (b.find("opt_cone", &c, &cnt, &off)) RI("opt_cone", &cone, 1);
-    if (cone != 0 && cone != 1) return fail(MRE_ERR_MODEL, "opt_cone must be 0 (pyramidal) or 1 (elliptic)");
-    m.cone = cone; }
-  RF("home_qpos", m.home_qpos, 7);
-  float M0d[NV];
-  RF("M0_diag", M0d, NV);
-
-  // ---- verify the topology the kernels assume: robot = bodies 1..15 with one hinge
-  // each (dof = body-1), cubes = bodies 16..19 with free joints (dofs 15+6p)
-  for (int bb = 1; bb < NB; bb++) {
-    bool ok = bb < NRB ? (m.body_jnttype[bb] == 1 && m.body_dofadr[bb] == bb - 1 && m.body_qposadr[bb] == bb - 1 &&
-                          m.body_propid[bb] < 0 && m.body_parent[bb] < bb)
-                       : (m.body_jnttype[bb] == 2 && m.body_dofadr[bb] == NRV + 6 * (bb - NRB) &&
-                          m.body_qposadr[bb] == NRV + 7 * (bb - NRB) && m.body_propid[bb] == bb - NRB &&
-                          m.body_parent[bb] == 0);
-    if (!ok) return fail(MRE_ERR_MODEL, "body layout differs from the compiled kernels");
-  }
-  if (m.dof_Madr[NRV] != NMR) return fail(MRE_ERR_MODEL, "robot mass-matrix size differs");
-  for (int a = 0; a < 7; a++)
-    if (m.act_dof[a] != a) return fail(MRE_ERR_MODEL, "arm actuators must drive dofs 0..6");
-
-  // ---- derived tables
-  m.body_level[0] = 0;
-  for (int bb = 1; bb < NB; bb++) m.body_level[bb] = m.body_level[m.body_parent[bb]] + 1;
-  for (int bb = 0; bb < NB; bb++) {
-    if (m.body_level[bb] > MAXCHAIN) return fail(MRE_ERR_MODEL, "tree deeper than MAXCHAIN");
-    m.body_desc_mask[bb] = 0;
-  }
-  for (int c = 1; c < NB; c++)
-    for (int a = c; a > 0; a = m.body_parent[a]) m.body_desc_mask[a] |= (1u << c);
-  m.robot_mass = 0;
-  for (int bb = 1; bb < NRB; bb++) {
-    m.robot_mass += m.body_mass[bb];
-    int chain[MAXCHAIN], n = 0;
-    for (int d = m.body_dofadr[bb]; d >= 0; d = m.dof_parent[d]) {
-      if (n >= MAXCHAIN) return fail(MRE_ERR_MODEL, "dof chain too long");
-      chain[n++] = d;
-    }
-    m.chain_len[bb] = n;
-    for (int k = 0; k < n; k++) m.chain_dof[bb][k] = chain[n - 1 - k];
-  }
-  for (int i = 0; i < NRV; i++) {
-    int adr = m.dof_Madr[i];
-    for (int j = i; j >= 0; j = m.dof_parent[j], adr++) { m.M_i[adr] = i; m.M_j[adr] = j; }
-    if (adr != m.dof_Madr[i + 1]) return fail(MRE_ERR_MODEL, "dof_Madr inconsistent");
-  }
-  for (int i = 0; i < NRV; i++)
-    if (m.dof_parent[i] != ROBOT_DOF_PARENT[i] || m.dof_Madr[i] != robot_dof_madr(i))
-      return fail(MRE_ERR_MODEL, "robot dof tree differs from the one the kernels are unrolled for (mre_dev.h)");
-  // tables of the level-parallel robot solve
-  {
-    int depth[NRV];
-    m.sol_maxdepth = 0;
-    for (int i = 0; i < NRV; i++) {
-      depth[i] = m.dof_parent[i] < 0 ? 0 : depth[m.dof_parent[i]] + 1;  // parents precede children
-      m.sol_depth[i] = depth[i];
-      if (depth[i] > m.sol_maxdepth) m.sol_maxdepth = depth[i];
-    }
-    m.sol_depth[NRV] = -1;
-    for (int i = 0; i <= NRV; i++) {
-      uint16_t desc[14], anc[8];
-      for (auto& v : desc) v = 0xFFFF;
-      for (auto& v : anc) v = 0xFFFF;
-      if (i < NRV) {
-        int nd = 0, na = 0;
-        for (int c = NRV - 1; c > i; c--) {  // descendants of i, descending
-          bool is_desc = false;
-          for (int j = m.dof_parent[c]; j >= 0; j = m.dof_parent[j]) if (j == i) is_desc = true;
-          if (!is_desc) continue;
-          if (nd >= 14) return fail(MRE_ERR_MODEL, "solve table: too many descendants");
-          desc[nd++] = (uint16_t)(c | ((m.dof_Madr[c] + depth[c] - depth[i]) << 8));
-        }
-        for (int a = m.dof_Madr[i] + 1; a < m.dof_Madr[i + 1]; a++) {
-          if (na >= 8) return fail(MRE_ERR_MODEL, "solve table: too many ancestors");
-          int j = i;
-          for (int k = 0; k < a - m.dof_Madr[i]; k++) j = m.dof_parent[j];
-          anc[na++] = (uint16_t)(j | (a << 8));
-        }
-      }
-      for (int k = 0; k < 7; k++) m.sol_desc[i][k] = desc[2 * k] | ((uint32_t)desc[2 * k + 1] << 16);
-      for (int k = 0; k < 4; k++) m.sol_anc[i][k] = anc[2 * k] | ((uint32_t)anc[2 * k + 1] << 16);
-    }
-  }
-  for (int k = 0; k < NRV; k++) {
-    int anc[MAXCHAIN + 1], n = 0;
-    for (int j = m.dof_parent[k]; j >= 0; j = m.dof_parent[j]) anc[++n] = j;  // 1-based positions
-    int cnt = 0;
-    for (int p = 1; p <= n; p++)
-      for (int q = p; q <= n; q++) {
-        if (cnt >= MAXFAC) return fail(MRE_ERR_MODEL, "factor table overflow");
-        m.fac_dst[k][cnt] = (uint8_t)(m.dof_Madr[anc[p]] + (q - p));
-        m.fac_a[k][cnt] = (uint8_t)p;
-        m.fac_b[k][cnt] = (uint8_t)q;
-        cnt++;
-      }
-    m.fac_n[k] = cnt;
-  }
-  m.M0_diag_robot_sum = 0;
-  for (int i = 0; i < NRV; i++) m.M0_diag_robot_sum += M0d[i];
-  for (int p = 0; p < NPROP; p++) {  // same parking grid as the oracle's reset
-    m.park_pos[p][0] = 2.0f + 0.5f * p; m.park_pos[p][1] = 2.0f; m.park_pos[p][2] = -5.0f;
-  }
-  return pack_records(m);
-}
-
 // ------------------------------------------------------------------- lifecycle
 extern "C" const char* mre_last_error(void) { return g_err.c_str(); }
 
@@ -1348,15 +933,10 @@ extern "C" int mre_create(const void* blob, size_t nbytes, int num_envs, int dev
   if (!blob || !out || num_envs <= 0) return fail(MRE_ERR_ARG, "mre_create: bad argument");
   *out = nullptr;
   mre_env* e = new mre_env();
-  int rc = build_model(blob, nbytes, e->hM);
-  if (rc != MRE_OK) { delete e; return rc; }
-  if (const char* it = getenv("MRE_DEBUG_ITERS")) e->hM.iterations = atoi(it);  // profiling knob only
-  e->prop_geom0 = -1;
-  for (int g = 0; g < NG; g++) if (e->hM.geom_propid[g] == 0) e->prop_geom0 = g;
-  if (e->prop_geom0 != PROP_GEOM0 || e->hM.geom_type[1] != 1 || e->hM.geom_body[1] != 0) {
-    delete e;
-    return fail(MRE_ERR_MODEL, "mre_create: expected geom 1 = the table (static box) and one geom per cube slot");
-  }
+  const std::string err = build_model(blob, nbytes, e->hM, e->solver);
+  if (!err.empty()) { delete e; return fail(MRE_ERR_MODEL, err); }
+  if (const char* it = getenv("MRE_DEBUG_ITERS")) e->hM.opt_rec.iterations = atoi(it);  // profiling knob only
+  int rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     delete e;
@@ -1792,14 +1372,13 @@ extern "C" int mre_set_solver(mre_env* e, int solver) {
     return fail(MRE_ERR_ARG, "mre_set_solver: solver is 0 (PGS) or 2 (Newton)");
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream));
-  e->hM.solver = solver;
-  HIPCHK(hipMemcpy(e->dM, &e->hM, sizeof(DevModel), hipMemcpyHostToDevice));
+  e->solver = solver;   // host-side only: it picks the kernel instantiation, no kernel reads it
   return MRE_OK;
 }
 
 extern "C" int mre_get_solver(mre_env* e) {
   if (!e) return fail(MRE_ERR_ARG, "null handle");
-  return e->hM.solver;
+  return e->solver;
 }
 
 // {queue launches so far, waves of a queue launch, control ticks per queue launch (the library's choice), enabled,
@@ -1893,7 +1472,7 @@ extern "C" int mre_get_time(mre_env* e, double* time) {
   std::vector<int> hn((size_t)e->N);
   int rc = copy_out(e, hn.data(), e->nstep, (size_t)e->N * 4);
   if (rc) return rc;
-  for (int i = 0; i < e->N; i++) time[i] = (double)hn[i] * (double)e->hM.timestep;
+  for (int i = 0; i < e->N; i++) time[i] = (double)hn[i] * (double)e->hM.opt_rec.timestep;
   return MRE_OK;
 }
 extern "C" int mre_get_ctrl(mre_env* e, float* ctrl) {
@@ -2407,7 +1986,7 @@ extern "C" int mre_place_props(mre_env* e, const uint8_t* mask, uint64_t seed, c
     fill_args(e, a);
     a.trace = nullptr;
     // _max_settle_physics_time = 2 s; min time = settle_steps * dt (0.3 s in the reference)
-    a.nsteps = (int)std::lround(2.0 / e->hM.timestep);
+    a.nsteps = (int)std::lround(2.0 / e->hM.opt_rec.timestep);
     if (a.nsteps < settle_steps) a.nsteps = settle_steps;
     a.flags = F_FREEZE_ROBOT | F_SETTLE_EXIT; a.env_mask = e->mask;
     a.settle_steps = e->settle_steps; a.min_settle_steps = settle_steps;
@@ -2434,7 +2013,7 @@ extern "C" int mre_place_props(mre_env* e, const uint8_t* mask, uint64_t seed, c
     // in every one of ten rounds; with Newton all settle in the first).  Placing again cannot help: stop, flag them
     // (only where that diagnosis can hold: PGS, a batch large enough that "none of them" is not chance, first round;
     //  a lone env keeps its ten attempts like the reference's)
-    const bool give_up = settled_now == 0 && round == 0 && N >= 64 && e->hM.solver != MRE_SOLVER_NEWTON;
+    const bool give_up = settled_now == 0 && round == 0 && N >= 64 && e->solver != MRE_SOLVER_NEWTON;
     bool left = false;
     for (size_t i = 0; i < N; i++) left = left || todo[i];
     if (left) {

@@ -1764,7 +1764,7 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
       newton_solve(M, s, l);
       polished = nw_robot_polish(M, s, l);
 #else
-      if (M->cone == 0) solve_constraints_pyramidal(M, s, l);
+      if (M->opt_rec.cone == 0) solve_constraints_pyramidal(M, s, l);
       else solve_constraints(M, s, l);
 #endif
       MRE_STAMP(6);
@@ -1805,7 +1805,7 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
           }
           v = (float)h;
         }
-        if (l == NQ + 2 && constrained && M->cone != 0) {
+        if (l == NQ + 2 && constrained && M->opt_rec.cone != 0) {
           // what the step's solve left behind, per row (22-bit hash; the oracle: mro_state_hash): a limit row pushing or
           // not, a contact open / sticking / sliding (|f_t| on the cone's boundary).  A solution that sits on one of
           // those boundaries within rounding is as legitimate a fork of two arithmetics as a contact that closes a
@@ -1902,8 +1902,8 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
   }
   if (a.sites != nullptr && q_last) {
     float* o = a.sites + (size_t)env * 16;
-    if (l < 3) o[l] = s.site_xpos[M->tcp_site][l];
-    if (l >= 3 && l < 6) o[l] = s.site_xpos[M->eef_site][l - 3];
+    if (l < 3) o[l] = s.site_xpos[M->opt_rec.tcp_site][l];
+    if (l >= 3 && l < 6) o[l] = s.site_xpos[M->opt_rec.eef_site][l - 3];
     if (l == 6) {
       float q[4];
       mat2q(q, s.site_xmat[0]);

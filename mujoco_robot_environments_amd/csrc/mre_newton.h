@@ -326,8 +326,8 @@ MRE_DEV NwLane nw_lane(ModelP M, const Sm& s, int l) {
   c.lk = (l >= NRV && l < NV) ? (l - NRV) % 6 : 0;
   c.lact = l < NRV || (c.lp >= 0 && c.lp < s.nprops);
   c.mdiag = c.lp >= 0 ? (c.lk < 3 ? s.prop_mass[c.lp] : s.prop_inertia[c.lp][c.lk - 3]) : 0.f;
-  c.mu_scale = __builtin_amdgcn_rsqf(fmaxf(M->impratio, kMinVal));
-  float msum = M->M0_diag_robot_sum;
+  c.mu_scale = __builtin_amdgcn_rsqf(fmaxf(M->opt_rec.impratio, kMinVal));
+  float msum = M->opt_rec.M0_diag_robot_sum;
   for (int p = 0; p < s.nprops; p++)
     msum += 3.f * s.prop_mass[p] + s.prop_inertia[p][0] + s.prop_inertia[p][1] + s.prop_inertia[p][2];
   c.scale = 1.0f / msum;
@@ -649,7 +649,7 @@ MRE_DEV float nw_search_move_impl(ModelP M, Sm& s, int l) {
   MRE_DBG_T0();
   const NwLane c = nw_lane(M, s, l);
   const int nefc = s.nefc, ncon = s.ncon, nscalar = 7 + s.nl;
-  const float tol = M->tolerance, mu_scale = c.mu_scale;
+  const float tol = M->opt_rec.tolerance, mu_scale = c.mu_scale;
   const bool on = l < NV && c.lact;
   const float fs = on ? s.qfrc_smooth[l] : 0.f, as = on ? s.qacc_smooth[l] : 0.f;
   float qa = on ? s.qacc[l] : 0.f, Ma = on ? s.nw_Ma[l] : 0.f;
@@ -828,14 +828,14 @@ MRE_DEV void newton_solve(ModelP M, Sm& s, int l, unsigned long long* stamp_acc,
 #define NW_STAMP(k) do {} while (0)
 MRE_DEV void newton_solve(ModelP M, Sm& s, int l) {
 #endif
-  const float tol = M->tolerance;
-  const int max_iter = M->iterations;
+  const float tol = M->opt_rec.tolerance;
+  const int max_iter = M->opt_rec.iterations;
   const int nscalar = 7 + s.nl, ncon = s.ncon;
-  float msum = M->M0_diag_robot_sum;
+  float msum = M->opt_rec.M0_diag_robot_sum;
   for (int p = 0; p < s.nprops; p++)
     msum += 3.f * s.prop_mass[p] + s.prop_inertia[p][0] + s.prop_inertia[p][1] + s.prop_inertia[p][2];
   const float scale = 1.0f / msum;
-  const bool pyr = M->cone == 0;
+  const bool pyr = M->opt_rec.cone == 0;
   if (pyr) nw_setup_pyramidal(M, s, l);
   else nw_setup(M, s, l);
   NW_STAMP(0);
@@ -974,7 +974,7 @@ MRE_PHASE_FN bool nw_robot_polish(ModelP M, Sm& s, int l) {
 #pragma unroll
       for (int t = 0; t < 9; t++) o[t] = 0.0;
       o[9] = (double)rs;
-      if (M->cone == 0) {
+      if (M->opt_rec.cone == 0) {
         // pyramidal cone: nw_pyramid in fp64
         const double e[4] = {j[0] + fr * j[1], j[0] - fr * j[1], j[0] + fr * j[2], j[0] - fr * j[2]};
         double a[4], n[4];

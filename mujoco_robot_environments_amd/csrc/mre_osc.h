@@ -86,7 +86,7 @@ MRE_DEV void sym_pinv6_serial(const float* A_in, float* out, float* V, float* w,
 
 // position / orientation error of the controller site w.r.t. the target
 MRE_DEV void osc_errors(ModelP M, const Sm& s, const float* tgt, float* ep, float* eo) {
-  const int st = M->eef_site;
+  const int st = M->opt_rec.eef_site;
   v3sub(ep, tgt, s.site_xpos[st]);
   float q[4], qc[4], qe[4];
   (void)st;
@@ -107,7 +107,7 @@ MRE_DEV bool osc_converged(ModelP M, const Sm& s, const OscConfig* cp, const flo
 // writes s.ctrl[0..6]; tgt = [pos3 quat4 vel3 angvel3] (uniform pointer into LDS)
 MRE_PHASE_FN void osc_compute(ModelP M, Sm& s, OscSm& o, const OscConfig* cp, const float* tgt, int l) {
   const OscConfig& c = *cp;
-  const int st = M->eef_site;
+  const int st = M->opt_rec.eef_site;
   // J (lane = r*7+a) and dense arm mass block (lane = i*7+j)
   if (l < 42) {
     const int r = l / 7, a = l % 7;

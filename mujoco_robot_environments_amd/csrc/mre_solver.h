@@ -864,13 +864,13 @@ MRE_DEV void solve_constraints_impl(ModelP M, Sm& s, int l) {
   MRE_SYNC();
   // ---- PGS sweeps over the island schedule
   const int nva = NRV + 6 * s.nprops;
-  float msum = M->M0_diag_robot_sum;
+  float msum = M->opt_rec.M0_diag_robot_sum;
   for (int p = 0; p < s.nprops; p++)
     msum += 3.f * s.prop_mass[p] + s.prop_inertia[p][0] + s.prop_inertia[p][1] + s.prop_inertia[p][2];
   const float scale = 1.0f / ((msum / nva) * nva);
   // (wave-uniform by construction; said so, the step counters of the sweep live in scalar registers)
-  const int nsched = __builtin_amdgcn_readfirstlane(s.nsched), max_iter = M->iterations, nscalar = 7 + nl;
-  const float tol = M->tolerance;
+  const int nsched = __builtin_amdgcn_readfirstlane(s.nsched), max_iter = M->opt_rec.iterations, nscalar = 7 + nl;
+  const float tol = M->opt_rec.tolerance;
   // Operand table: the schedule's descriptor words expanded once per solve into LDS byte offsets,
   // so that a sweep step costs one 8-byte read per lane instead of a decode.  It lives in the
   // body-frame arrays and region R1, which nothing reads between the controller and the next
