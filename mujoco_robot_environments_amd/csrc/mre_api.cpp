@@ -1,9 +1,8 @@
 // mre_api.cpp -- host side of the C ABI declared in include/mre.h.
 // Owns the device buffers and the HIP stream of a batch of environments,
 // uploads the fp32 DevModel that mre_model.cpp builds from the model blob, and
-// enqueues kernels.  No torch types; plain pointers and sizes only.
+// enqueues kernels; how stepping launches are issued is mre_sched.cpp's.  No torch types; plain pointers and sizes only.
 #include <hip/hip_runtime.h>
-#include <chrono>
 
 #include <cmath>
 #include <cstdio>
@@ -13,762 +12,17 @@
 #include <algorithm>
 #include <vector>
 
-#include "../../include/mre.h"
-#include "mre_dev.h"
+#include "mre_env.h"
+#include "mre_launch.h"
 #include "mre_model.h"
 #include "mre_records.h"
 
 using namespace mre;
 
-extern "C" void mre_launch_step(const StepArgs* args, hipStream_t stream);
-extern "C" void mre_launch_settle(const StepArgs* args, hipStream_t stream);
-extern "C" void mre_launch_step_large(const StepArgs* args, hipStream_t stream);
-extern "C" void mre_launch_step_newton(const StepArgs* args, hipStream_t stream);
-extern "C" void mre_launch_settle_newton(const StepArgs* args, hipStream_t stream);
-extern "C" void mre_launch_step_queue(const StepArgs* args, int nwaves, hipStream_t stream);
-extern "C" void mre_launch_step_queue_newton(const StepArgs* args, int nwaves, hipStream_t stream);
-extern "C" void mre_launch_step_queue_large(const StepArgs* args, int nwaves, hipStream_t stream);
-extern "C" void mre_launch_step_queue_large_newton(const StepArgs* args, int nwaves, hipStream_t stream);
-extern "C" int mre_queue_waves_per_cu(void);
-extern "C" int mre_queue_waves_per_cu_newton(void);
-extern "C" void mre_launch_step_large_newton(const StepArgs* args, hipStream_t stream);
-extern "C" void mre_launch_render(const RenderArgs* args, int row_groups, hipStream_t stream);
-extern "C" void mre_launch_pack_final(int N, const float* qpos, const float* qvel, const uint32_t* status, float* out,
-                                      hipStream_t stream);
-extern "C" void mre_launch_restore_rows(const uint8_t* sel, int env0, int N, float* qpos, const float* sv_qpos, float* qvel,
-                                        const float* sv_qvel, float* qacc_ws, const float* sv_qacc_ws, float* qfine,
-                                        const float* sv_qfine, float* ctrl, const float* sv_ctrl, int* nstep,
-                                        const int* sv_nstep, uint32_t* status, const uint32_t* sv_status,
-                                        uint8_t* converged, const uint8_t* sv_converged, uint8_t* pending,
-                                        hipStream_t stream);
-extern "C" void mre_launch_pose_search(const SearchArgs* args, hipStream_t stream);
-extern "C" void mre_launch_sort_select(const SortArgs* args, hipStream_t stream);
-extern "C" void mre_launch_reset(const DevModel* M, int N, float* qpos, float* qvel, float* qacc_ws, float* qfine,
-                                 float* ctrl, uint32_t* status, int* nstep, const uint8_t* mask,
-                                 hipStream_t stream);
-
-
 static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) {
+int mre::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
-}
-#define HIPCHK(x)                                                                       \
-  do {                                                                                  \
-    hipError_t e_ = (x);                                                                \
-    if (e_ != hipSuccess)                                                               \
-      return fail(MRE_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));         \
-  } while (0)
-
-struct mre_env {
-  int N = 0, device = 0;
-  hipStream_t stream = nullptr;
-  DevModel* dM = nullptr;
-  DevModel hM;
-  int solver = MRE_SOLVER_PGS;   // mjtSolver (0 = PGS, 2 = Newton): selects the kernel instantiation (mre_set_solver)
-  float *qpos = nullptr, *qvel = nullptr, *qacc_ws = nullptr, *ctrl = nullptr;
-  float* qfine = nullptr;   // [N][QFINE_ROW] low-order words of the state: robot joints, then cube poses and velocities (StepArgs::qfine)
-  int *nstep = nullptr, *sv_nstep = nullptr;   // [N] physics steps since the last reset (physics.data.time)
-  int* nprops = nullptr;
-  float* prop_size = nullptr;
-  float* osc_target = nullptr;
-  uint8_t* grip_closed = nullptr;
-  uint8_t* converged = nullptr;
-  uint8_t* mask = nullptr;
-  float* sites = nullptr;
-  uint32_t* status = nullptr;
-  int* stats = nullptr;
-  OscConfig osc;
-  OscConfig* d_osc = nullptr;
-  OscConfig* d_osc_env = nullptr;
-  float* geoms = nullptr;        // [N][NG][16] geom poses for the renderer (allocated on first use)
-  // cached image of the static geoms (ground, table) for the last camera: depth | rgb | seg
-  float* bg_depth = nullptr; uint8_t* bg_rgb = nullptr; uint8_t* bg_seg = nullptr;
-  float bg_key[16] = {0}; int bg_h = 0, bg_w = 0; bool bg_valid = false;
-  uint8_t* prop_rgb = nullptr;   // [N][NPROP][3]
-  float geom_rgb[NG][3];  // [N] per-env controller parameters (mre_osc_configure_env) or null
-  float* trace = nullptr;
-  int trace_nenv = 0, trace_max = 0, trace_pos = 0;
-  long long env_id_offset = 0;
-  std::vector<long long> env_ids;  // explicit global ids (mre_set_env_ids) or empty = offset + index
-  int* order = nullptr;       // dispatch permutation (heavy-first), device
-  bool use_order = false;     // caller-supplied permutation (mre_set_env_order)
-  int* auto_order = nullptr;  // permutation maintained by launch_step: longest Gauss-Seidel schedule first
-  int* h_auto_order = nullptr;  // pinned host staging
-  bool have_auto_order = false;
-  bool profiling = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-  size_t events_used = 0;
-  // ---- capacity fallback (see launch_step): per-env kernel choice, pre-launch state copies
-  bool fallback = true;
-  bool large_only = false;
-  bool compact_only = false;  // mre_set_fallback(0)  // mre_set_fallback(2): every env on the large kernel (reference run for the fallback)
-  hipStream_t stream2 = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_order = nullptr;
-  uint8_t *d_large = nullptr, *mask_r = nullptr;
-  float *sv_qpos = nullptr, *sv_qvel = nullptr, *sv_qacc_ws = nullptr, *sv_ctrl = nullptr, *sv_qfine = nullptr;
-  uint32_t* sv_status = nullptr;
-  uint8_t* sv_converged = nullptr;
-  float* contacts = nullptr;     // device [N][1 + 3 * CONTACT_EXPORT] (detect launches), allocated on first use
-  float* contacts_full = nullptr;  // device [N][CONTACT_EXPORT][12] (mre_get_contacts_full), allocated on first use
-  int* settle_steps = nullptr;   // device [N]
-  // Launch info and the per-launch inputs the host decides (dispatch order, large flags) live in MAPPED pinned host
-  // memory that the step kernels store to / load from directly: no copy command sits in a group's launch chain
-  // (round 3: one shader blit of 16 KB behind every group launch, 0.08 .. 3.9 ms each behind 2048 resident waves, and
-  // two more in front of the next one).  d_* = the device-side address of the same bytes.
-  int* h_launch_info = nullptr;  // [RING][N][4]: a group's launches in flight write one buffer each (ring slot)
-  int* d_launch_info = nullptr;
-  int* h_info_last = nullptr;    // the buffer (one of the two, per group region) that holds each env's latest record
-  uint8_t* d_pending = nullptr;  // device [N]: env overflowed the compact kernel, waits for its re-run (StepArgs::pending)
-  uint8_t* h_large_stage = nullptr;  // mapped [NSTAGE][N]: the large flags a pipelined launch reads (Group::cur)
-  uint8_t* d_large_stage = nullptr;
-  bool d_large_stale = false;        // the pipelined path changed h_large: d_large (synchronous launches) is behind
-  std::vector<uint8_t> h_large, h_rerun;
-  int n_large = 0;
-  long long* d_env_ids = nullptr; // device copy of env_ids (pose search), null = offset + index
-  // pose-search / sort_colours scratch (device, allocated on first use)
-  int *ps_attempts = nullptr, *ps_prop = nullptr, *ps_tick = nullptr, *ps_which = nullptr;
-  double *ps_bounds = nullptr, *ps_pose = nullptr, *ps_zones = nullptr, *ps_pick = nullptr;
-  int last_settle_max = 0;
-  long long n_reruns = 0, n_promotions = 0, n_demotions = 0;
-  // ---- pipelined env groups (launch_step): the envs are cut into contiguous groups, each with its own stream
-  // pair; a stepping call enqueues every group's launch and returns.  The tail of one group's launch (its slowest
-  // envs) then overlaps the other groups' next launches instead of leaving the GPU idle.
-  // A group's launch info is read -- and its fallback decisions taken -- LATE: with the default ring of two, launch
-  // t + 1 of a group is enqueued behind launch t without the host in between (reading t's info first put the read-back,
-  // the host's wake-up and the enqueue, 100 - 200 us, between every two launches of a chain whose launches last 800 us:
-  // the kernel trace of the Newton bench), and t's info is processed when launch t + 2 is issued (or at the next call
-  // that touches the state: drain()).  An env that overflows the compact kernel in launch t is therefore skipped by the
-  // launches already enqueued behind it on the device (StepArgs::pending) and re-run for every one of them on the large
-  // kernel (process_oldest).  MRE_RING = 3 / 4 keeps up to two / three launches enqueued behind the one being read.
-  struct Group {
-    int lo = 0, n = 0;
-    hipStream_t st = nullptr, st2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    struct Out {           // a launch whose info has not been processed yet
-      StepArgs args;       // (a re-run uses them)
-      hipEvent_t ev_info = nullptr;
-      int stage = 0;       // the staged record (order + large flags) the launch reads
-    } out[4];              // ring of RING entries: out[head] is the oldest one
-    int head = 0, nout = 0;
-    int cur = 0;           // staged record new launches read: the latest complete one of NSTAGE
-                           // (a record is rewritten only when no outstanding launch reads it)
-    hipEvent_t p0 = nullptr, p1 = nullptr;   // profiling bracket of the launch being enqueued
-    int* h_order = nullptr;  // mapped [NSTAGE][N] (entries [lo, lo + n) are the group's): its envs slowest first
-    int* d_order = nullptr;
-  };
-  std::vector<Group> groups;
-  int* h_grp_order = nullptr;   // mapped [NSTAGE][N]: per group, its envs slowest first (Group::h_order of `groups`)
-  int* d_grp_order = nullptr;
-  // Queue launches (StepArgs::q_head, k_step_queue): a rollout of several control ticks over more envs than the GPU holds
-  // waves.  The groups above give every env a wave of its own per launch, and a group's next launch waits for the
-  // group's slowest env: measured on the benchmark (tests/diagnostics/duration_trace.py, schedule_sim.py) the mean env
-  // takes 0.35 - 0.39 ms per tick, the slowest env OF A TICK 0.86 - 1.0 ms (a different env every tick: an impact, a few
-  // more Newton iterations), and the tick period sits at that maximum, 25 % above what the wave slots could deliver.
-  // A queue launch has no per-tick barrier: all envs form one group (`qgroup`), the launch covers queue_ticks control
-  // ticks, and its persistent waves take the env that is furthest behind -- a slow tick of one env delays nobody else.
-  // The ring, the staged records, the capacity fallback and the re-runs are those of a group.  Per-tick callers
-  // (mre_step, one-tick rollouts) keep the groups; the two never have launches outstanding at the same time.
-  Group qgroup;
-  bool queue_ok = true;         // MRE_QUEUE=0: never
-  int queue_ticks = 200;        // control ticks per queue launch at most when the cut is the library's (MRE_QUEUE_TICKS, <= QUEUE_TICKS_MAX):
-                                // measured 50 / 100 / 200 on the benchmark: 25.0 / 25.6 / 26.1 M env-steps/s (a launch ends with idle slots once)
-  int queue_waves = 0;          // waves the GPU holds of the queue kernel (CUs x workgroups per CU; the smaller of the two solvers' kernels)
-  int queue_shards = 16;        // ready lists per launch (MRE_QUEUE_SHARDS, <= QUEUE_SHARDS_MAX): see queue_pop
-  int queue_lshards = 8;        // ... of the large kernel (MRE_QUEUE_LSHARDS, <= QUEUE_LSHARDS_MAX)
-  bool queue_test_serial = false;
-  // waves of the large kernel beyond the envs flagged large (MRE_QUEUE_SPARE_LARGE): they wait for hand-overs, and each
-  // holds the LDS of 1.3 compact waves while it does -- measured on the benchmark (2 hand-overs per 200 ticks): 8 / 32 / 96
-  // spare waves = 26.3 / 25.9 / 24.8 M env-steps/s.  Hand-overs beyond the spare waves queue up behind them.
-  int queue_spare_large = 8;
-  // mre_run_controller's queue launches are shorter than a rollout's: a scripted phase moves hundreds of envs towards
-  // the compact capacities at once (the grasp closes), and the host's 7/8 rule moves them at launch boundaries, before
-  // they overflow -- measured on bench.py's pick_place leg: 50 / 100 / 200 ticks = 24.7 / 25.0 / 22.8 M (no queue: 21.8 M)
-  int queue_run_ticks = 100;
-  // A window shorter than this is stepped the old way when the cut is the library's (MRE_QUEUE_MIN_TICKS).  A queue launch
-  // pays ~0.8 ms once (set-up, the ragged end of its last tick) and 7.6 us per item (take + acquire 4.1, release + list
-  // 3.5: measured with s_memtime stamps) and wins by not waiting for each tick's slowest env.  On the driver's window
-  // (20 ticks after 5, the lightest regime: a tick's slowest env is 1.5x the mean, against 2.5-3x later) the two cancel:
-  // 30.3 M env-steps/s as one queue launch, 31.3 M as per-tick launches, same run; from ~30 ticks on the queue wins
-  // everywhere measured (+19 % over 200 ticks).  A caller that asks for launches of k >= 2 ticks gets queue launches of k.
-  int queue_min_ticks = 32;
-  // ... and between 8 ticks and that, by what the per-tick launches themselves have measured: the spread of a tick's
-  // durations (p99 env / mean env of one-tick group launches, smoothed; 1.28 in the lightest regime, 1.9-2.0 with the arms
-  // on the table).  Below queue_tail_min the per-tick launches lose little to their slowest env and the window stays with
-  // them; above it, or when nothing has been measured since the last reset, a window of >= 8 ticks is a queue launch (20
-  // ticks in the heavy regime: 19.5 M env-steps/s against 16.1 M per tick).
-  float tick_tail = 0.f;
-  bool tick_tail_valid = false;
-  float queue_tail_min = 1.45f;
-  unsigned tail_samples = 0;
-  std::vector<int> tail_scratch;
-  int queue_large_waves_max = 0;  // 2 per compute unit (the unit of the balance in launch_group_enqueue; no longer a cap)
-  int* h_qlist = nullptr;       // pinned [RING + 1][N + 32]: counts per large shard [16], then the shards' lists of envs flagged large (+ 1)
-  int* q_ws = nullptr;          // device: q_head[48][256] q_tail[48][256] q_done[16] q_acc[N][4] q_buf[QUEUE_TICKS_MAX][stride] (StepArgs)
-  int* q_gen = nullptr;         // device, one word: StepArgs::q_gen
-  int* h_q_err = nullptr;       // mapped: StepArgs::q_err
-  int* h_qgrp_order = nullptr;  // mapped [NSTAGE][N]: qgroup's own staged dispatch orders
-  long n_queue_launches = 0;
-  long long n_handovers = 0;    // envs a queue launch moved to the large kernel itself
-  int queue_last_handovers = 0; // ... in the launch processed last (the next launch keeps that many spare large waves)
-  // Depth of a group's ring of unprocessed launches: capacity RING = 4, depth in use `ring` = 2 (MRE_RING = 2 .. 4).
-  // Rounds 3 / 4 ran two with one library call per tick: a group that finished early sat idle until Python came back and
-  // the host had served the slower groups (rocprofv3 kernel trace of the round-4 bench: 167 / 106 us between a launch's
-  // end and the next start on the two high-priority streams, all four groups in flight 56 % of the span).  Round 5: the
-  // caller hands over all the ticks of a window in ONE call (mre_rollout_ticks) and the loop that enqueues them runs
-  // here.  A ring of four was built and measured with it: all four groups in flight 81 % of the span, idle gap 17 - 23 us
-  // -- and 1.5 - 2 % SLOWER than a ring of two under the same single call (21.6 vs 22.0 M env-steps/s default, 19.1 vs
-  // 19.4 M in the heavy regime, three runs each on one box): what a launch reads from the host -- its longest-first
-  // dispatch order above all -- is as many launches old as the ring is deep, and the fresher order is worth more than
-  // the shorter gap.  Two stays the default.
-  static constexpr int RING = 4;
-  int ring = 2;
-  static constexpr int NSTAGE = RING + 1;   // <= RING outstanding launches + the record being written
-  static_assert(sizeof(Group::out) / sizeof(Group::Out) == RING, "Group::out is the ring");
-  hipEvent_t ev_main = nullptr; // orders the group streams after the handle's stream
-  float* seq_copy[RING + 1] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // own copies of the last RING + 1 ctrl_seq arguments (re-runs read them later)
-  size_t seq_cap = 0;
-  unsigned seq_calls = 0;
-  double dbg_wait_s = 0, dbg_call_s = 0; long dbg_calls = 0;   // MRE_DEBUG_TIMING
-  // a caller that reads or writes the state after EVERY stepping call (a per-tick loop with host-side targets)
-  // gains nothing from the groups and pays their launches: after two such calls in a row the stepping calls
-  // go back to one launch of the whole batch, until two stepping calls arrive back to back again
-  int calls_since_drain = 0, sync_streak = 0;
-  // a pipelined launch failed half-way (a HIP error between the enqueue of a group's kernels and the record of its
-  // event): launches of the group that were in flight may have skipped envs waiting for a re-run, and their saved rows
-  // are gone -- the state is no longer the state of any rollout.  Every later call says so instead of stepping on.
-  bool broken = false;
-};
-
-// solver-specific instantiations of the step kernel (opt_solver of the model, mre_set_solver)
-static void launch_compact(const mre_env* e, const StepArgs& a, hipStream_t st, bool settle = false) {
-  const bool newton = e->solver == MRE_SOLVER_NEWTON;
-  if (settle) { if (newton) mre_launch_settle_newton(&a, st); else mre_launch_settle(&a, st); }
-  else { if (newton) mre_launch_step_newton(&a, st); else mre_launch_step(&a, st); }
-}
-static void launch_large(const mre_env* e, const StepArgs& a, hipStream_t st) {
-  if (e->solver == MRE_SOLVER_NEWTON) mre_launch_step_large_newton(&a, st); else mre_launch_step_large(&a, st);
-}
-
-// Launch the step kernel, optionally bracketed by HIP events on the handle's stream.
-//
-// Capacity fallback.  The compact kernel (8 workgroups/CU) holds at most NCON_MAX / NEFC_MAX /
-// NRROW_MAX / NPP_MAX constraints per env; a grasp or a pile needs more.  Every launch therefore
-//   1. has every env copy its state rows (qpos, qvel, warm start, finger low words, ctrl, status) aside as
-//      the step kernel loads them (StepArgs::sv_*),
-//   2. runs the envs currently marked "large" on the large-capacity kernel (second stream; an env takes
-//      part in the kernel that matches its flag, StepArgs::large / want_large) next to the compact kernel
-//      for all others,
-//   3. reads back per-env launch info (overflow flag + high-water marks of the launch),
-//   4. restores the envs that overflowed on the compact kernel to their saved rows, marks them
-//      large and runs them again on the large kernel -- so no result ever depends on the compact
-//      capacities; it also moves envs whose high-water marks came within 1/8 of a compact capacity
-//      (no re-run needed at a launch boundary) and demotes large envs that fell below 5/8.
-// Only an overflow of the LARGE capacities is reported (MRE_ST_CONTACT_OVERFLOW).
-static int profile_events(mre_env* e, hipEvent_t* e0, hipEvent_t* e1) {
-  *e0 = *e1 = nullptr;
-  if (!e->profiling) return MRE_OK;
-  if (e->events_used == e->events.size()) {
-    hipEvent_t x, y;
-    HIPCHK(hipEventCreate(&x)); HIPCHK(hipEventCreate(&y));
-    e->events.emplace_back(x, y);
-  }
-  *e0 = e->events[e->events_used].first; *e1 = e->events[e->events_used].second;
-  e->events_used++;
-  return MRE_OK;
-}
-
-// An env whose high-water marks came within 1/8 of a compact capacity is moved to the large kernel at a launch boundary
-// (no re-run).  Round 5 measured the one place where this rule looks wasteful: a closed grasp is EXACTLY 57 robot rows
-// (7 equality rows, two limits, 2 pads x 2 boxes x 4 contact points x 3) of the 62 the compact kernel holds, and 7/8 of 62
-// is 54 -- every grasping env moves to the large kernel (bench.py's pick_place leg: 1825 promotions per 4096-env pair, 38 %
-// of the batch at 6 instead of 8 workgroups per CU through the close / lift / home phases).  Moving an env only when one
-// more contact would no longer fit (hw_nrrow + 3 > NRROW_MAX) cut the promotions to 1150 but raised the re-runs from 24
-// to 278 -- the swing home adds a finger-cube or cube-cube contact within one 50-tick launch -- and the leg ran 8 % SLOWER
-// (20.4 M vs 22.3 M env-steps/s, profiles/NOTES.md): a re-run repeats a whole launch of 50 ticks on the large kernel
-// behind the group's stream, residency on the large kernel costs a quarter of the slots of the envs that are on it.  The 7/8 rule stays.
-static inline int compact_nrrow_max(const mre_env* e) {
-  return e->solver == MRE_SOLVER_NEWTON ? NRROW_MAX_COMPACT_NEWTON : NRROW_MAX_COMPACT_PGS;
-}
-static inline bool near_compact_caps(const mre_env* e, int hw_ncon, int hw_nefc, int hw_nrrow, int hw_npp) {
-  return 8 * hw_ncon > 7 * NCON_MAX || 8 * hw_nefc > 7 * NEFC_MAX || 8 * hw_nrrow > 7 * compact_nrrow_max(e) || 8 * hw_npp > 7 * NPP_MAX;
-}
-
-// Dispatch order of a group: its envs by the duration in their launch-info record, longest first (counting sort over 256
-// buckets, stable; results do not depend on it).
-static void sort_longest_first(const mre_env::Group& G, const int* info, int kmax, int* order_stage) {
-  int count[258] = {0};
-  auto bucket = [&](int i) {
-    const int* li = info + 4 * (size_t)i;
-    return (int)((long long)(li[0] < 0 ? 0 : (li[1] >> 16)) * 255 / kmax);
-  };
-  for (int i = G.lo; i < G.lo + G.n; i++) count[255 - bucket(i) + 1]++;
-  for (int k = 1; k <= 256; k++) count[k] += count[k - 1];
-  for (int i = G.lo; i < G.lo + G.n; i++) order_stage[G.lo + count[255 - bucket(i)]++] = i;
-}
-
-// Read the launch info of a group's OLDEST outstanding launch and act on it (see launch_step): promotions /
-// demotions, dispatch order of the group's next launch, re-run of the envs that overflowed the compact kernel --
-// for that launch and for the younger outstanding one, which skipped them.
-static int process_oldest(mre_env* e, mre_env::Group& G) {
-  if (G.nout == 0) return MRE_OK;
-  const int slot = G.head;
-  mre_env::Group::Out& O = G.out[slot];
-  {
-    const auto w0 = std::chrono::steady_clock::now();
-    HIPCHK(hipEventSynchronize(O.ev_info));
-    e->dbg_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
-  }
-  if (e->h_q_err && *e->h_q_err != 0) {
-    e->broken = true;
-    return fail(MRE_ERR_HIP, "queue launch: an env listed as ready never arrived (internal error)");
-  }
-  const int* const info = e->h_launch_info + (size_t)slot * 4 * (size_t)e->N;
-  // a staged record nobody reads: not the current one, not the younger outstanding launch's
-  int fs = 0;
-  {
-    bool used[mre_env::NSTAGE] = {false};
-    used[G.cur] = true;
-    for (int k = 1; k < G.nout; k++) used[G.out[(slot + k) % mre_env::RING].stage] = true;   // the younger outstanding launches'
-    while (used[fs]) fs++;
-  }
-  int* const order_stage = G.h_order + (size_t)fs * (size_t)e->N;
-  int nrerun = 0;
-  bool changed = false;
-  int kmax = 0;
-  const long long handovers0 = e->n_handovers;
-  for (int i = G.lo; i < G.lo + G.n; i++) {
-    const int* li = info + 4 * (size_t)i;
-    e->h_rerun[i] = 0;
-    if (li[0] < 0) continue;   // not part of the launch, or skipped while it waited for a re-run
-    const int hw_ncon = li[1] & 0xFFFF, hw_nefc = li[2], hw_nrrow = li[3] & 0xFFFF, hw_npp = li[3] >> 16;
-    if ((li[1] >> 16) > kmax) kmax = li[1] >> 16;
-    if ((li[0] & 4) != 0 && !e->h_large[i]) {
-      // handed over to the large kernel inside a queue launch: it finished the launch there, and stays
-      e->h_large[i] = 1; changed = true; e->n_large++; e->n_promotions++; e->n_handovers++;
-    } else if (li[0] == 1) {
-      // overflowed the COMPACT kernel (whatever the host's flag says by now: a promotion decided one launch ago
-      // takes effect one launch later)
-      e->h_rerun[i] = 1; nrerun++;
-      if (!e->h_large[i]) { e->h_large[i] = 1; changed = true; e->n_large++; e->n_promotions++; }
-    } else if (!e->h_large[i]) {
-      if (!e->compact_only && near_compact_caps(e, hw_ncon, hw_nefc, hw_nrrow, hw_npp)) {
-        e->h_large[i] = 1; changed = true; e->n_large++; e->n_promotions++;
-      }
-    } else if (!e->large_only && li[0] == 0 && 8 * hw_ncon <= 5 * NCON_MAX && 8 * hw_nefc <= 5 * NEFC_MAX &&
-               8 * hw_nrrow <= 5 * compact_nrrow_max(e) && 8 * hw_npp <= 5 * NPP_MAX) {
-      e->h_large[i] = 0; changed = true; e->n_large--; e->n_demotions++;
-    }
-  }
-  if (&G == &e->qgroup) e->queue_last_handovers = (int)(e->n_handovers - handovers0);
-  else if (O.args.nsteps == O.args.control_steps && (e->tail_samples++ & 3u) == 0u && G.n >= 256) {
-    // spread of this tick's durations over the group's envs (mre_env::tick_tail)
-    std::vector<int>& d = e->tail_scratch;
-    d.clear();
-    long long sum = 0;
-    for (int i = G.lo; i < G.lo + G.n; i++) {
-      const int* li = info + 4 * (size_t)i;
-      if (li[0] >= 0) { d.push_back(li[1] >> 16); sum += li[1] >> 16; }
-    }
-    if (d.size() >= 256 && sum > 0) {
-      const size_t k = d.size() - 1 - d.size() / 100;
-      std::nth_element(d.begin(), d.begin() + k, d.end());
-      const float ratio = (float)d[k] * (float)d.size() / (float)sum;
-      e->tick_tail = e->tick_tail_valid ? 0.9f * e->tick_tail + 0.1f * ratio : ratio;
-      e->tick_tail_valid = true;
-    }
-  }
-  // (what is decided here takes effect with the NEXT launch enqueued for the group -- the one after the younger
-  //  outstanding launch -- which reads the staged record straight from mapped host memory)
-  if (kmax > 0) {   // longest processing time first within the group (counting sort, stable)
-    sort_longest_first(G, info, kmax, order_stage);
-  } else {
-    memcpy(order_stage + G.lo, G.h_order + (size_t)G.cur * (size_t)e->N + G.lo, (size_t)G.n * 4);
-  }
-  if (nrerun > 0) {
-    HIPCHK(hipMemcpyAsync(e->mask_r + G.lo, e->h_rerun.data() + G.lo, (size_t)G.n, hipMemcpyHostToDevice, G.st));
-    mre_launch_restore_rows(e->mask_r, G.lo, G.n, e->qpos, e->sv_qpos, e->qvel, e->sv_qvel, e->qacc_ws, e->sv_qacc_ws,
-                            e->qfine, e->sv_qfine, e->ctrl, e->sv_ctrl, e->nstep, e->sv_nstep, e->status, e->sv_status,
-                            e->converged, e->sv_converged, e->d_pending, G.st);
-    // the launch that overflowed, then the younger outstanding launches (which left these envs alone)
-    for (int k = 0; k < G.nout; k++) {
-      StepArgs ar = G.out[(slot + k) % mre_env::RING].args;
-      ar.env_mask = e->mask_r; ar.launch_info = nullptr; ar.large = nullptr; ar.sv_qpos = nullptr; ar.pending = nullptr;
-      ar.q_head = nullptr;   // (one wave per env for the whole launch, whatever the launch itself was)
-      launch_large(e, ar, G.st);
-      HIPCHK(hipGetLastError());
-    }
-    e->n_reruns += nrerun;
-  }
-  memcpy(e->h_large_stage + (size_t)fs * (size_t)e->N + G.lo, e->h_large.data() + G.lo, (size_t)G.n);
-  G.cur = fs;
-  if (changed) e->d_large_stale = true;
-  if (nrerun > 0) HIPCHK(hipStreamSynchronize(G.st));   // (h_rerun is pageable: the staged bytes must outlive the upload)
-  // the latest record of every env of the group (mre_get_launch_info)
-  for (int i = G.lo; i < G.lo + G.n; i++) {
-    const int* li = info + 4 * (size_t)i;
-    if (li[0] != -2) memcpy(e->h_info_last + 4 * (size_t)i, li, 16);
-  }
-  G.head = (G.head + 1) % mre_env::RING;
-  G.nout--;
-  return MRE_OK;
-}
-
-static int drain_group(mre_env* e, mre_env::Group& G, bool sync_idle = false) {
-  if (G.nout == 0 && !sync_idle) return MRE_OK;
-  while (G.nout > 0) {
-    int rc = process_oldest(e, G);
-    if (rc) return rc;
-  }
-  HIPCHK(hipStreamSynchronize(G.st));
-  return MRE_OK;
-}
-// Complete every pending group launch: every entry point that reads or writes device state starts here.
-static int drain(mre_env* e, bool api_call = false) {
-  if (e->broken) return fail(MRE_ERR_HIP, "an earlier stepping call failed while its launches were being enqueued: the "
-                                          "state of this handle is undefined (mre_destroy it, create a new one)");
-  if (api_call) {
-    if (e->calls_since_drain == 1) e->sync_streak++;
-    else if (e->calls_since_drain > 1) e->sync_streak = 0;
-    e->calls_since_drain = 0;
-  }
-  bool any = e->qgroup.nout > 0;
-  for (auto& G : e->groups) any = any || G.nout > 0;
-  if (!any) return MRE_OK;
-  HIPCHK(hipSetDevice(e->device));
-  for (auto& G : e->groups) {
-    int rc = drain_group(e, G, true);
-    if (rc) return rc;
-  }
-  return drain_group(e, e->qgroup, true);
-}
-#define DRAIN(e) do { int rc_ = drain(e, true); if (rc_) return rc_; } while (0)
-#define DRAIN_PENDING(e) do { int rc_ = drain(e, false); if (rc_) return rc_; } while (0)
-
-// a launch under the capacity fallback: split by the envs' flags, state rows copied aside, launch info reported
-static void guard_args(mre_env* e, StepArgs& a) {
-  a.large = e->d_large; a.launch_info = e->d_launch_info;
-  a.sv_qpos = e->sv_qpos; a.sv_qvel = e->sv_qvel; a.sv_qacc_ws = e->sv_qacc_ws; a.sv_qfine = e->sv_qfine;
-  a.sv_ctrl = e->sv_ctrl; a.sv_status = e->sv_status; a.sv_converged = e->sv_converged; a.sv_nstep = e->sv_nstep;
-}
-
-// One group's part of a stepping call: finish its previous launch, enqueue the new one, do not wait.
-static int launch_group_enqueue(mre_env* e, mre_env::Group& G, const StepArgs& a_full, bool queue);
-static int launch_group(mre_env* e, mre_env::Group& G, const StepArgs& a_full, bool queue = false) {
-  // at most ring - 1 launches stay unprocessed behind the one enqueued here -- and none behind a long one: a launch of many
-  // ticks (a chunk of mre_run_controller: 50 ticks) makes the 0.1 ms the host costs the chain irrelevant, while an env
-  // that overflows would have to be re-run for two such launches instead of one
-  const int keep = a_full.nsteps <= 50 ? e->ring - 1 : 0;
-  while (G.nout > keep) {
-    int rc = process_oldest(e, G);
-    if (rc) return rc;
-  }
-  int rc = launch_group_enqueue(e, G, a_full, queue);
-  if (rc) {
-    // something failed after part of the launch was enqueued: nothing may stay in flight behind an event that was
-    // never recorded (a later drain() would wait for it)
-    (void)hipStreamSynchronize(G.st);
-    (void)hipStreamSynchronize(G.st2);
-    G.nout = 0; G.head = 0;
-    (void)hipMemset(e->d_pending + G.lo, 0, (size_t)G.n);
-    e->broken = true;
-  }
-  return rc;
-}
-static int launch_group_enqueue(mre_env* e, mre_env::Group& G, const StepArgs& a_full, bool queue) {
-  int rc;
-  StepArgs a = a_full;
-  const size_t N = (size_t)e->N;
-  // first launch of a burst (nothing of the group in flight): other entry points may have changed the flags since --
-  // and the envs' latest durations may come from launches of ANOTHER group (the queue's group covers all envs; the
-  // per-tick groups a quarter each): the burst starts with the order they give, not with the one this group left behind
-  // (measured: 20 per-tick launches after a queue window of 200 ticks, 15.7 -> 16.1 M env-steps/s)
-  if (G.nout == 0) {
-    memcpy(e->h_large_stage + (size_t)G.cur * N + G.lo, e->h_large.data() + G.lo, (size_t)G.n);
-    int kmax = 0;
-    for (int i = G.lo; i < G.lo + G.n; i++) {
-      const int* li = e->h_info_last + 4 * (size_t)i;
-      if (li[0] >= 0 && (li[1] >> 16) > kmax) kmax = li[1] >> 16;
-    }
-    if (kmax > 0) sort_longest_first(G, e->h_info_last, kmax, G.h_order + (size_t)G.cur * N);
-  }
-  a.N = G.n; a.env_order = G.d_order + (size_t)G.cur * N + G.lo; a.seq_stride = e->N;
-  rc = profile_events(e, &G.p0, &G.p1);
-  if (rc) return rc;
-  HIPCHK(hipStreamWaitEvent(G.st, e->ev_main, 0));
-  if (G.p0) HIPCHK(hipEventRecord(G.p0, G.st));
-  guard_args(e, a);
-  a.pending = e->d_pending;
-  const int slot = (G.head + G.nout) % mre_env::RING;
-  a.large = e->d_large_stage + (size_t)G.cur * N;
-  a.launch_info = e->d_launch_info + (size_t)slot * 4 * N;
-  StepArgs ac = a;
-  ac.want_large = 0;
-  bool run_large = false;
-  const uint8_t* const fl = e->h_large_stage + (size_t)G.cur * N;   // (the very flags the kernels will read)
-  if (queue) {
-    // Queue launch: compact waves on G.st, the large kernel's waves next to them on G.st2 (capacity fallback inside the
-    // launch: mre_kernels.hip, queue_pop).  Ready lists, per-env accumulators and the count of finished envs start at
-    // zero (one block from the allocation's start, a multiple of 16 bytes); the envs flagged large are bucket 0 of the
-    // large shard.
-    const int nt = a.nsteps / a.control_steps, S = e->queue_shards, cap = (G.n + S - 1) / S;
-    const int SL = e->queue_lshards, capl = (G.n + SL - 1) / SL;
-    constexpr int QS = QUEUE_SHARDS_MAX + QUEUE_LSHARDS_MAX;
-    const size_t ctl = 2 * (size_t)QS * QUEUE_TICKS_MAX + 16;
-    const size_t stride = (size_t)S * cap + (size_t)SL * capl;
-    const size_t words = ctl + 4 * N + (size_t)nt * stride;
-    ac.sv_qpos = nullptr;   // (nothing is re-run: no rows to put back)
-    ac.q_head = e->q_ws; ac.q_tail = ac.q_head + QS * QUEUE_TICKS_MAX;
-    ac.q_done = ac.q_tail + QS * QUEUE_TICKS_MAX; ac.q_started = ac.q_done + 1; ac.q_acc = ac.q_done + 16;
-    ac.q_buf = ac.q_acc + 4 * N; ac.q_err = e->h_q_err; ac.q_nticks = nt; ac.q_shards = S; ac.q_cap = cap; ac.q_stride = (int)stride;
-    ac.q_lshards = SL; ac.q_capl = capl;
-    ac.q_gen = e->q_gen; ac.q_gen_expect = (int)(e->n_queue_launches + 1);
-    // the envs flagged large, per large shard (env e: shard e % SL, in env order): counts in hl[0 .. SL), lists from hl[16]
-    int* const hl = e->h_qlist + (size_t)(e->n_queue_launches % (mre_env::RING + 1)) * (N + 32);
-    int nl = 0;
-    for (int j = 0; j < SL; j++) hl[j] = 0;
-    memset(hl + 16, 0, (size_t)SL * capl * 4);
-    for (int i = G.lo; i < G.lo + G.n; i++)
-      if (fl[i]) { const int j = i % SL; hl[16 + (size_t)j * capl + hl[j]++] = i + 1; nl++; }   // (the queue's group is all envs: lo = 0)
-    run_large = true;
-    // 1. the large kernel's waiting launch, first: see step_body (q_gen)
-    StepArgs al = ac;
-    al.want_large = 1; al.q_wait = 1;
-    // A wave per env that is large already and some for those that come over -- up to the share of the compute units'
-    // LDS that the large envs' share of the work asks for: with x large and y compact waves per unit (26.5 x + 20.4 y =
-    // 160 KB) both kinds finish together when (work of the large envs) / x = (work of the compact envs) / y.  A fixed cap
-    // of two per unit was right for the benchmark (a dozen large envs) and starved the whole-episode run at tuned gains,
-    // where 44 % of 8192 envs grasp at once: 25.8 -> 14.7 M env-steps/s inside step().  Never so many that a unit has no
-    // room for compact waves (x < 6 by construction): large waves wait for the compact ones to finish.
-    int lw = nl + (e->queue_last_handovers > e->queue_spare_large ? e->queue_last_handovers : e->queue_spare_large);
-    {
-      // (the two kinds' work from the envs' own latest durations where there are any: the large envs are the
-      //  contact-rich ones, their ticks cost 1.3 .. 2.5 compact ticks depending on the phase)
-      double wl = 0, wc = 0;
-      for (int i = G.lo; i < G.lo + G.n; i++) {
-        const int* li = e->h_info_last + 4 * (size_t)i;
-        const double d = li[0] >= 0 ? (double)(li[1] >> 16) : 0.0;
-        if (fl[i]) wl += d; else wc += d;
-      }
-      const double ncomp = (double)(G.n - nl);
-      const double r = (wl > 0 && wc > 0) ? wl / wc : (ncomp > 0 ? 1.3 * (double)nl / ncomp : 1e9);
-      const double x = r * 160.0 / (26.5 * r + 20.4);   // large waves per compute unit at balance
-      int bal = (int)(x * (double)(e->queue_large_waves_max / 2));   // (queue_large_waves_max = 2 per unit)
-      if (bal < e->queue_large_waves_max / 4) bal = e->queue_large_waves_max / 4;
-      if (lw > bal) lw = bal;
-    }
-    if (lw < 1) lw = 1;
-    // (test knob MRE_QUEUE_TEST_SERIAL=1: on the compact kernel's own stream, i.e. strictly before it -- what a profiler
-    //  that serialises dispatches makes of the two streams; the launch then leaves after its bounded wait and the one
-    //  behind the compact kernel does the large kernel's whole share)
-    hipStream_t const st_large = e->queue_test_serial ? G.st : G.st2;
-    if (e->solver == MRE_SOLVER_NEWTON) mre_launch_step_queue_large_newton(&al, lw, st_large);
-    else mre_launch_step_queue_large(&al, lw, st_large);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(G.ev_join, st_large));
-    // 2. the lists, then the launch's number
-    HIPCHK(hipMemsetAsync(e->q_ws, 0, ((words * 4 + 15) / 16) * 16, G.st));
-    if (nl > 0) {
-      HIPCHK(hipMemcpyAsync(ac.q_buf + (size_t)S * cap, hl + 16, (size_t)SL * capl * 4, hipMemcpyHostToDevice, G.st));
-      // (bucket 0's tail word of every large shard: one word per row of QUEUE_TICKS_MAX)
-      HIPCHK(hipMemcpy2DAsync(ac.q_tail + S * QUEUE_TICKS_MAX, (size_t)QUEUE_TICKS_MAX * 4, hl, 4, 4, (size_t)SL, hipMemcpyHostToDevice, G.st));
-    }
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)e->q_gen, ac.q_gen_expect, 1, G.st));
-    // 3. the compact kernel
-    const int nwaves = G.n < e->queue_waves ? G.n : e->queue_waves;
-    if (e->solver == MRE_SOLVER_NEWTON) mre_launch_step_queue_newton(&ac, nwaves, G.st);
-    else mre_launch_step_queue(&ac, nwaves, G.st);
-    HIPCHK(hipGetLastError());
-    // Behind the compact kernel, the large kernel once more, not waiting: nothing to do when the two ran side by side
-    // (a few microseconds), the rest of the job when they did not -- results never depend on how the GPU overlaps them.
-    // (as many waves as the GPU holds of the large kernel: when a scripted phase closes hundreds of grasps inside one
-    //  launch, the hand-overs outnumber the waiting launch's spare waves and pile up behind them -- here, with the compact
-    //  kernel gone, they all run at once)
-    al.q_wait = 0;
-    const int sweep = G.n < 3 * e->queue_large_waves_max ? G.n : 3 * e->queue_large_waves_max;
-    if (e->solver == MRE_SOLVER_NEWTON) mre_launch_step_queue_large_newton(&al, sweep, G.st);
-    else mre_launch_step_queue_large(&al, sweep, G.st);
-    e->n_queue_launches++;
-  } else {
-    for (int i = G.lo; i < G.lo + G.n && !run_large; i++) run_large = fl[i] != 0;
-    if (run_large) {
-      HIPCHK(hipEventRecord(G.ev_fork, G.st));
-      HIPCHK(hipStreamWaitEvent(G.st2, G.ev_fork, 0));
-      StepArgs al = a;
-      al.want_large = 1;
-      launch_large(e, al, G.st2);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(G.ev_join, G.st2));
-    }
-    launch_compact(e, ac, G.st, false);
-  }
-  HIPCHK(hipGetLastError());
-  if (run_large) HIPCHK(hipStreamWaitEvent(G.st, G.ev_join, 0));
-  if (G.p1) HIPCHK(hipEventRecord(G.p1, G.st));
-  // (the kernels stored their 16 B of launch info per env into mapped host memory: the event is all that follows)
-  HIPCHK(hipEventRecord(G.out[slot].ev_info, G.st));
-  G.out[slot].args = a;
-  G.out[slot].stage = G.cur;
-  G.nout++;
-  return MRE_OK;
-}
-
-static int launch_step(mre_env* e, const StepArgs& a, bool settle = false, bool pipeline_ok = true, bool allow_queue = false) {
-  if (e->broken) return drain(e);   // (reports the failure)
-  HIPCHK(hipSetDevice(e->device));  // the HIP current device is per thread; callers may have moved it
-  {
-    const bool guarded_ = e->fallback && a.nsteps > 0 && (a.flags & F_NO_CONSTRAINTS) == 0;
-    if (++e->calls_since_drain >= 2) e->sync_streak = 0;
-    const bool pipelined = pipeline_ok && e->sync_streak < 2 && e->groups.size() > 1 && guarded_ && !settle && a.env_mask == nullptr && !e->use_order &&
-                           a.trace == nullptr && a.contacts == nullptr && a.settle_steps == nullptr && a.geoms == nullptr &&
-                           (a.flags & (F_DETECT | F_SETTLE_EXIT | F_OSC_EVAL)) == 0;
-    // a rollout of several ticks over more envs than the GPU holds waves: one queue launch of all envs (mre_env::qgroup)
-    const bool queue = allow_queue && e->queue_ok && pipeline_ok && guarded_ && !e->compact_only && !e->large_only && !settle && (a.mode == CTRL_SEQ || a.mode == CTRL_OSC) && a.env_mask == nullptr && !e->use_order &&
-                       a.contacts == nullptr && a.settle_steps == nullptr && a.geoms == nullptr &&
-                       (a.flags & (F_DETECT | F_SETTLE_EXIT | F_OSC_EVAL)) == 0 && a.control_steps > 0 &&
-                       a.nsteps % a.control_steps == 0 && a.nsteps >= 2 * a.control_steps &&
-                       a.nsteps <= QUEUE_TICKS_MAX * a.control_steps && e->queue_waves > 0 && e->N > e->queue_waves;
-    if (queue) {
-      for (auto& G : e->groups) { int rc = drain_group(e, G); if (rc) return rc; }
-      HIPCHK(hipEventRecord(e->ev_main, e->stream));
-      int rc = launch_group(e, e->qgroup, a, true);
-      // (a caller with a trace buffer reads it when the call returns: stepping calls with a trace have always completed first)
-      if (!rc && a.trace != nullptr) rc = drain_group(e, e->qgroup);
-      return rc;
-    }
-    { int rc = drain_group(e, e->qgroup); if (rc) return rc; }
-    if (pipelined) {
-      struct Timer { mre_env* e; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-                     ~Timer() { e->dbg_call_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); e->dbg_calls++; } } timer_{e};
-      HIPCHK(hipEventRecord(e->ev_main, e->stream));
-      // serve the groups in the order their previous launches complete
-      const size_t ng = e->groups.size();
-      bool done[8] = {false, false, false, false, false, false, false, false};
-      for (size_t left = ng; left > 0;) {
-        size_t pick = ng;
-        for (size_t g = 0; g < ng && pick == ng; g++)
-          if (!done[g] && (e->groups[g].nout <= (a.nsteps <= 50 ? e->ring - 1 : 0) ||   // (launch_group's `keep`: nothing to wait for)
-                           hipEventQuery(e->groups[g].out[e->groups[g].head].ev_info) == hipSuccess)) pick = g;
-        (void)hipGetLastError();   // (hipErrorNotReady of a query is not an error)
-        if (pick == ng) {          // none ready: wait for the first outstanding one
-          for (size_t g = 0; g < ng && pick == ng; g++) if (!done[g]) pick = g;
-        }
-        int rc = launch_group(e, e->groups[pick], a);
-        if (rc) return rc;
-        done[pick] = true; left--;
-      }
-      return MRE_OK;
-    }
-    DRAIN_PENDING(e);
-  }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (e->profiling) {
-    if (e->events_used == e->events.size()) {
-      hipEvent_t x, y;
-      HIPCHK(hipEventCreate(&x)); HIPCHK(hipEventCreate(&y));
-      e->events.emplace_back(x, y);
-    }
-    e0 = e->events[e->events_used].first; e1 = e->events[e->events_used].second;
-    e->events_used++;
-    HIPCHK(hipEventRecord(e0, e->stream));
-  }
-  const bool guarded = e->fallback && a.nsteps > 0 && (a.flags & F_NO_CONSTRAINTS) == 0;
-  if (!guarded) {
-    launch_compact(e, a, e->stream, settle);
-    HIPCHK(hipGetLastError());
-  } else {
-    const size_t N = (size_t)e->N;
-    if (e->d_large_stale) {   // promotions / demotions decided by the pipelined path since the last synchronous launch
-      HIPCHK(hipMemcpyAsync(e->d_large, e->h_large.data(), N, hipMemcpyHostToDevice, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-      e->d_large_stale = false;
-    }
-    StepArgs ac = a;
-    guard_args(e, ac);
-    ac.want_large = 0;
-    // (recounted from the flags every launch: an env flagged large is masked out of the compact
-    // kernel, so the large kernel MUST run whenever a flag is set)
-    e->n_large = 0;
-    for (size_t i = 0; i < N; i++) e->n_large += e->h_large[i];
-    const bool run_large = e->n_large > 0;
-    if (run_large) {
-      HIPCHK(hipEventRecord(e->ev_fork, e->stream));
-      HIPCHK(hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
-      StepArgs al = ac;
-      al.want_large = 1;
-      launch_large(e, al, e->stream2);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(e->ev_join, e->stream2));
-    }
-    launch_compact(e, ac, e->stream, settle);
-    HIPCHK(hipGetLastError());
-    if (run_large) HIPCHK(hipStreamWaitEvent(e->stream, e->ev_join, 0));
-    HIPCHK(hipStreamSynchronize(e->stream));   // (launch info: stored to mapped host memory by the kernels)
-    memcpy(e->h_info_last, e->h_launch_info, N * 16);
-    int nrerun = 0;
-    bool changed = false;
-    for (size_t i = 0; i < N; i++) {
-      const int* li = e->h_launch_info + 4 * i;
-      e->h_rerun[i] = 0;
-      if (li[0] < 0) continue;
-      const int hw_ncon = li[1] & 0xFFFF, hw_nefc = li[2], hw_nrrow = li[3] & 0xFFFF, hw_npp = li[3] >> 16;
-      if (!e->h_large[i]) {
-        if (li[0] > 0) {  // overflowed the compact kernel: re-run this launch on the large one
-          e->h_rerun[i] = 1; e->h_large[i] = 1; nrerun++; changed = true; e->n_large++; e->n_promotions++;
-        } else if (!e->compact_only && near_compact_caps(e, hw_ncon, hw_nefc, hw_nrrow, hw_npp)) {
-          // within 1/8 of a compact capacity: move over BEFORE it overflows -- a promotion at a launch
-          // boundary costs nothing, an overflow costs a re-run of the whole launch (a scripted phase
-          // is one launch of 2000 steps)
-          e->h_large[i] = 1; changed = true; e->n_large++; e->n_promotions++;
-        }
-      } else if (!e->large_only && li[0] == 0 && 8 * hw_ncon <= 5 * NCON_MAX && 8 * hw_nefc <= 5 * NEFC_MAX &&
-                 8 * hw_nrrow <= 5 * compact_nrrow_max(e) && 8 * hw_npp <= 5 * NPP_MAX) {
-        e->h_large[i] = 0; changed = true; e->n_large--; e->n_demotions++;  // back below 5/8: demote
-      }
-    }
-    // Dispatch order for the next launch: a launch ends with its slowest wavefront, and the hardware hands
-    // workgroups to free slots in index order, so the envs that took longest in this launch (the kernel
-    // reports each env's own duration, s_memtime ticks >> 10) go first in the next one -- longest
-    // processing time first.  Counting sort over 256 duration buckets, stable; results do not depend on it.
-    if (!e->use_order) {
-      int kmax = 0;
-      for (size_t i = 0; i < N; i++)
-        if (e->h_launch_info[4 * i] >= 0) { const int k = e->h_launch_info[4 * i + 1] >> 16; if (k > kmax) kmax = k; }
-      if (kmax > 0) {
-        int count[258] = {0};
-        auto bucket = [&](size_t i) {
-          const int k = e->h_launch_info[4 * i] < 0 ? 0 : (e->h_launch_info[4 * i + 1] >> 16);
-          return (int)((long long)k * 255 / kmax);
-        };
-        for (size_t i = 0; i < N; i++) count[255 - bucket(i) + 1]++;
-        for (int k = 1; k <= 256; k++) count[k] += count[k - 1];
-        for (size_t i = 0; i < N; i++) e->h_auto_order[count[255 - bucket(i)]++] = (int)i;
-        // (the pinned staging buffer is rewritten only after the next launch's read-back sync)
-        HIPCHK(hipMemcpyAsync(e->auto_order, e->h_auto_order, N * 4, hipMemcpyHostToDevice, e->stream));
-        e->have_auto_order = true;
-      } else {
-        e->have_auto_order = false;
-      }
-    }
-    if (nrerun > 0) {
-      HIPCHK(hipMemcpyAsync(e->mask_r, e->h_rerun.data(), N, hipMemcpyHostToDevice, e->stream));
-      mre_launch_restore_rows(e->mask_r, 0, e->N, e->qpos, e->sv_qpos, e->qvel, e->sv_qvel, e->qacc_ws, e->sv_qacc_ws,
-                              e->qfine, e->sv_qfine, e->ctrl, e->sv_ctrl, e->nstep, e->sv_nstep, e->status,
-                              e->sv_status, e->converged, e->sv_converged, nullptr, e->stream);
-      StepArgs ar = a;
-      ar.env_mask = e->mask_r; ar.launch_info = nullptr;
-      launch_large(e, ar, e->stream);
-      HIPCHK(hipGetLastError());
-      e->n_reruns += nrerun;
-    }
-    if (changed) {
-      // the staged copy must outlive the async upload: h_large is only touched after a stream sync
-      HIPCHK(hipMemcpyAsync(e->d_large, e->h_large.data(), N, hipMemcpyHostToDevice, e->stream));
-      HIPCHK(hipStreamSynchronize(e->stream));
-    }
-  }
-  if (e1) HIPCHK(hipEventRecord(e1, e->stream));
-  return MRE_OK;
 }
 
 // ------------------------------------------------------------------- lifecycle
@@ -816,91 +70,7 @@ static int create_buffers(mre_env* e, int num_envs, int device_id) {
   HIPCHK(hipMemsetAsync(e->d_pending, 0, N, e->stream));
   HIPCHK(hipMemsetAsync(e->d_large, 0, N, e->stream));
   e->h_large.assign(N, 0); e->h_rerun.assign(N, 0);
-  {
-    // env groups of the pipelined stepping path (MRE_GROUPS = 1: every call completes before it returns)
-    int ng = 4, min_envs = 512;   // (measured on the bench: 2, 3 and 4 groups are within 1 % for Newton, 4 best for PGS)
-    if (const char* g = getenv("MRE_GROUPS")) ng = atoi(g);
-    if (const char* g = getenv("MRE_GROUP_MIN")) min_envs = atoi(g);   // test knob: smallest group worth a launch of its own
-    if (ng < 1) ng = 1;
-    if (ng > 8) ng = 8;
-    if (const char* r = getenv("MRE_RING")) { e->ring = atoi(r); if (e->ring < 2) e->ring = 2; if (e->ring > mre_env::RING) e->ring = mre_env::RING; }
-    while (ng > 1 && num_envs < min_envs * ng) ng--;
-    HIPCHK(hipHostMalloc((void**)&e->h_grp_order, mre_env::NSTAGE * N * 4, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(hipHostGetDevicePointer((void**)&e->d_grp_order, e->h_grp_order, 0));
-    for (int k = 0; k < mre_env::NSTAGE; k++)
-      for (int i = 0; i < num_envs; i++) e->h_grp_order[(size_t)k * N + i] = i;
-    HIPCHK(hipEventCreateWithFlags(&e->ev_main, hipEventDisableTiming));
-    e->groups.resize(ng);
-    {
-      // the queue's group: all envs, default stream priority
-      auto& Q = e->qgroup;
-      Q.lo = 0; Q.n = num_envs;
-      HIPCHK(hipHostMalloc((void**)&e->h_qgrp_order, mre_env::NSTAGE * N * 4, hipHostMallocMapped | hipHostMallocCoherent));
-      Q.h_order = e->h_qgrp_order;
-      HIPCHK(hipHostGetDevicePointer((void**)&Q.d_order, Q.h_order, 0));
-      for (int k = 0; k < mre_env::NSTAGE; k++)
-        for (int i = 0; i < num_envs; i++) Q.h_order[(size_t)k * N + i] = i;
-      {
-        // the large kernel's waves on a stream of HIGHER priority: its own hardware queue (streams of one priority share a
-        // few), and its few workgroups are placed before the compact kernel's 2048 fill the compute units' LDS
-        int least = 0, greatest = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCHK(hipStreamCreateWithPriority(&Q.st, hipStreamNonBlocking, least));
-        HIPCHK(hipStreamCreateWithPriority(&Q.st2, hipStreamNonBlocking, greatest));
-      }
-      HIPCHK(hipEventCreateWithFlags(&Q.ev_fork, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&Q.ev_join, hipEventDisableTiming));
-      for (auto& o : Q.out) HIPCHK(hipEventCreateWithFlags(&o.ev_info, hipEventDisableTiming));
-      if (const char* q = getenv("MRE_QUEUE")) e->queue_ok = atoi(q) != 0;
-      if (const char* q = getenv("MRE_QUEUE_TICKS")) { const int v = atoi(q); if (v >= 2 && v <= QUEUE_TICKS_MAX) e->queue_ticks = v; }
-      if (e->queue_run_ticks > e->queue_ticks) e->queue_run_ticks = e->queue_ticks;
-      hipDeviceProp_t prop;
-      HIPCHK(hipGetDeviceProperties(&prop, e->device));
-      {
-        const int a_ = mre_queue_waves_per_cu(), b_ = mre_queue_waves_per_cu_newton();
-        e->queue_waves = prop.multiProcessorCount * (a_ < b_ ? a_ : b_);
-      }
-      if (const char* q = getenv("MRE_QUEUE_WAVES")) { const int v = atoi(q); if (v > 0) e->queue_waves = v; }   // test knob
-      if (const char* q = getenv("MRE_QUEUE_SHARDS")) { const int v = atoi(q); if (v >= 1 && v <= QUEUE_SHARDS_MAX) e->queue_shards = v; }
-      if (const char* q = getenv("MRE_QUEUE_MIN_TICKS")) { const int v = atoi(q); if (v >= 2) e->queue_min_ticks = v; }
-      if (const char* q = getenv("MRE_QUEUE_TAIL_MIN")) { const float v = (float)atof(q); if (v > 0.f) e->queue_tail_min = v; }
-      if (const char* q = getenv("MRE_QUEUE_TEST_SERIAL")) e->queue_test_serial = atoi(q) != 0;
-      if (const char* q = getenv("MRE_QUEUE_SPARE_LARGE")) { const int v = atoi(q); if (v >= 0) e->queue_spare_large = v; }
-      e->queue_large_waves_max = 2 * prop.multiProcessorCount;
-      if (const char* q = getenv("MRE_QUEUE_LSHARDS")) { const int v = atoi(q); if (v >= 1 && v <= QUEUE_LSHARDS_MAX) e->queue_lshards = v; }
-      HIPCHK(hipMalloc(&e->q_ws, ((2 * (size_t)(QUEUE_SHARDS_MAX + QUEUE_LSHARDS_MAX) * QUEUE_TICKS_MAX + 16 + 4 * N +
-                                   (size_t)QUEUE_TICKS_MAX * (2 * N + QUEUE_SHARDS_MAX + QUEUE_LSHARDS_MAX)) * 4 + 15) / 16 * 16));
-      HIPCHK(hipMalloc(&e->q_gen, 64));
-      HIPCHK(hipMemsetAsync(e->q_gen, 0, 64, e->stream));
-      HIPCHK(hipHostMalloc((void**)&e->h_qlist, (size_t)(mre_env::RING + 1) * (N + 32) * 4, hipHostMallocDefault));
-      HIPCHK(hipHostMalloc((void**)&e->h_q_err, 64, hipHostMallocMapped | hipHostMallocCoherent));
-      *e->h_q_err = 0;
-    }
-    for (int g = 0; g < ng; g++) {
-      auto& G = e->groups[g];
-      G.h_order = e->h_grp_order; G.d_order = e->d_grp_order;
-      G.lo = (int)((long long)num_envs * g / ng);
-      G.n = (int)((long long)num_envs * (g + 1) / ng) - G.lo;
-      // descending stream priorities stagger the groups: the first group's workgroups are dispatched first and the
-      // later groups fill the slots its slow envs leave idle (MRE_GROUP_PRIORITY=0: equal priorities)
-      int pr = 0;
-      {
-        int least = 0, greatest = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        const char* gp = getenv("MRE_GROUP_PRIORITY");
-        if (!(gp && atoi(gp) == 0)) { pr = greatest + g; if (pr > least) pr = least; }
-        // tuning knob: one digit per group, 0 = highest priority level
-        if (const char* map = getenv("MRE_GROUP_PRIO_MAP")) {
-          if ((int)strlen(map) > g && map[g] >= '0' && map[g] <= '9') { pr = greatest + (map[g] - '0'); if (pr > least) pr = least; }
-        }
-      }
-      HIPCHK(hipStreamCreateWithPriority(&G.st, hipStreamNonBlocking, pr));
-      HIPCHK(hipStreamCreateWithPriority(&G.st2, hipStreamNonBlocking, pr));
-      HIPCHK(hipEventCreateWithFlags(&G.ev_fork, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&G.ev_join, hipEventDisableTiming));
-      for (auto& o : G.out) HIPCHK(hipEventCreateWithFlags(&o.ev_info, hipEventDisableTiming));
-    }
-  }
+  { int rc = sched_create(e); if (rc) return rc; }
   if (const char* fb = getenv("MRE_NO_FALLBACK")) e->fallback = atoi(fb) == 0;  // profiling knob only
   if (const char* fl = getenv("MRE_FORCE_LARGE")) {  // profiling knob only: start every env on the large kernel
     if (atoi(fl) != 0) {
@@ -964,22 +134,7 @@ extern "C" int mre_destroy(mre_env* e) {
   if (getenv("MRE_DEBUG_TIMING") && e->dbg_calls > 0)
     fprintf(stderr, "mre: %ld pipelined calls, %.1f us per call in the library, of which %.1f us waiting for launch info\n",
             e->dbg_calls, 1e6 * e->dbg_call_s / e->dbg_calls, 1e6 * e->dbg_wait_s / e->dbg_calls);
-  auto free_group = [](mre_env::Group& G) {
-    if (G.st) { (void)hipStreamSynchronize(G.st); (void)hipStreamDestroy(G.st); }
-    if (G.st2) { (void)hipStreamSynchronize(G.st2); (void)hipStreamDestroy(G.st2); }
-    if (G.ev_fork) (void)hipEventDestroy(G.ev_fork);
-    if (G.ev_join) (void)hipEventDestroy(G.ev_join);
-    for (auto& O : G.out) if (O.ev_info) (void)hipEventDestroy(O.ev_info);
-  };
-  for (auto& G : e->groups) free_group(G);
-  free_group(e->qgroup);
-  if (e->q_ws) (void)hipFree(e->q_ws);
-  if (e->q_gen) (void)hipFree(e->q_gen);
-  if (e->h_q_err) (void)hipHostFree(e->h_q_err);
-  if (e->h_qlist) (void)hipHostFree(e->h_qlist);
-  if (e->h_qgrp_order) (void)hipHostFree(e->h_qgrp_order);
-  if (e->ev_main) (void)hipEventDestroy(e->ev_main);
-  if (e->h_grp_order) (void)hipHostFree(e->h_grp_order);
+  sched_destroy(e);
   for (float* p : e->seq_copy) if (p) (void)hipFree(p);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   if (e->stream2) (void)hipStreamSynchronize(e->stream2);
@@ -1117,18 +272,11 @@ extern "C" int mre_render(mre_env* e, const float* cam_pos, const float* cam_mat
   StepArgs a;
   fill_args(e, a);
   a.nsteps = 0; a.trace = nullptr; a.env_order = nullptr; a.env_mask = dmask; a.geoms = e->geoms;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (e->profiling) {  // same event bracket as launch_step: tools/bench_render.py times the camera with it
-    if (e->events_used == e->events.size()) {
-      hipEvent_t x, y;
-      HIPCHK(hipEventCreate(&x)); HIPCHK(hipEventCreate(&y));
-      e->events.emplace_back(x, y);
-    }
-    e0 = e->events[e->events_used].first; e1 = e->events[e->events_used].second;
-    e->events_used++;
-    HIPCHK(hipEventRecord(e0, e->stream));
-  }
-  launch_compact(e, a, e->stream);
+  hipEvent_t e0, e1;   // same event bracket as launch_step: tools/bench_render.py times the camera with it
+  rc = profile_events(e, &e0, &e1);
+  if (rc) return rc;
+  if (e0) HIPCHK(hipEventRecord(e0, e->stream));
+  step_kernels(e->solver).step(&a, e->stream);
   HIPCHK(hipGetLastError());
   RenderArgs r;
   memset(&r, 0, sizeof(r));
@@ -1175,7 +323,7 @@ extern "C" int mre_render(mre_env* e, const float* cam_pos, const float* cam_mat
       if (dmask) {
         StepArgs a0 = a;
         a0.env_mask = nullptr;
-        launch_compact(e, a0, e->stream);
+        step_kernels(e->solver).step(&a0, e->stream);
         HIPCHK(hipGetLastError());
       }
       RenderArgs b = r;
@@ -1493,11 +641,7 @@ extern "C" int mre_get_state(mre_env* e, float* qpos, float* qvel) {
 // the handle's stream -- the local block of the end-of-rollout all_gather (bench.py, distributed.py)
 extern "C" int mre_pack_final_state(mre_env* e, float* out) {
   if (!e || !out) return fail(MRE_ERR_ARG, "null");
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, out) != hipSuccess || at.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return fail(MRE_ERR_ARG, "mre_pack_final_state: out must be a device pointer");
-  }
+  if (!is_device_ptr(out)) return fail(MRE_ERR_ARG, "mre_pack_final_state: out must be a device pointer");
   DRAIN(e);
   HIPCHK(hipSetDevice(e->device));
   mre_launch_pack_final(e->N, e->qpos, e->qvel, e->status, out, e->stream);
@@ -1551,16 +695,12 @@ extern "C" int mre_step(mre_env* e, int nsubsteps, unsigned flags) {
 extern "C" int mre_rollout_ticks(mre_env* e, const float* ctrl_seq, int nticks, int control_steps, unsigned flags,
                                  int ticks_per_launch) {
   if (!e || !ctrl_seq || nticks < 0 || control_steps < 1) return fail(MRE_ERR_ARG, "mre_rollout: bad argument");
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, ctrl_seq) != hipSuccess || at.type != hipMemoryTypeDevice) {
-    (void)hipGetLastError();
-    return fail(MRE_ERR_ARG, "mre_rollout: ctrl_seq must be a device pointer");
-  }
+  if (!is_device_ptr(ctrl_seq)) return fail(MRE_ERR_ARG, "mre_rollout: ctrl_seq must be a device pointer");
   int per = (ticks_per_launch <= 0 || ticks_per_launch > nticks) ? nticks : ticks_per_launch;
   bool allow_queue = ticks_per_launch >= 2;   // the caller's cut into launches of several ticks: queue launches where they apply
   // the library's choice (ticks_per_launch <= 0) for a batch that does not fit the GPU's wave slots: queue launches
-  if (ticks_per_launch <= 0 && e->queue_ok && e->queue_waves > 0 && e->N > e->queue_waves && nticks >= 2) {
-    if (nticks >= e->queue_min_ticks || (nticks >= 8 && !(e->tick_tail_valid && e->tick_tail < e->queue_tail_min))) {
+  if (ticks_per_launch <= 0 && policy::queue_fits(e->queue_ok, e->queue_waves, e->N) && nticks >= 2) {
+    if (policy::window_wants_queue(nticks, e->queue_min_ticks, e->tick_tail_valid, e->tick_tail, e->queue_tail_min)) {
       // (equal parts, none of a single tick: a launch of one tick is not a queue launch)
       const int nl = (nticks + e->queue_ticks - 1) / e->queue_ticks;
       per = (nticks + nl - 1) / nl;   // (a last part of a single tick is an ordinary launch)
@@ -1607,11 +747,7 @@ extern "C" int mre_set_trace(mre_env* e, float* out, int nenv, int max_steps) {
   if (!e) return fail(MRE_ERR_ARG, "null handle");
   DRAIN(e);
   if (out) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, out) != hipSuccess || at.type != hipMemoryTypeDevice) {
-      (void)hipGetLastError();
-      return fail(MRE_ERR_ARG, "mre_set_trace: trace buffer must be a device pointer");
-    }
+    if (!is_device_ptr(out)) return fail(MRE_ERR_ARG, "mre_set_trace: trace buffer must be a device pointer");
     if (nenv <= 0 || nenv > e->N || max_steps <= 0) return fail(MRE_ERR_ARG, "mre_set_trace: bad sizes");
   }
   e->trace = out; e->trace_nenv = out ? nenv : 0; e->trace_max = out ? max_steps : 0; e->trace_pos = 0;
@@ -1672,7 +808,7 @@ extern "C" int mre_get_sites(mre_env* e, float* tcp_pos, float* eef_pose, float*
   StepArgs a;
   fill_args(e, a);
   a.nsteps = 0; a.trace = nullptr;
-  launch_compact(e, a, e->stream);
+  step_kernels(e->solver).step(&a, e->stream);
   HIPCHK(hipGetLastError());
   const size_t N = (size_t)e->N;
   std::vector<float> hs(N * 16), hq;
@@ -1756,8 +892,8 @@ extern "C" int mre_run_controller(mre_env* e, int nticks, int control_steps, uin
     chunk = 50;
     // a batch that exceeds the GPU's wave slots: queue launches (mre_env::qgroup) -- an overflow is handled inside the
     // launch, so the launches are as long as the queue's
-    queue = e->queue_ok && !e->compact_only && e->queue_waves > 0 && e->N > e->queue_waves && !e->use_order &&
-            (nticks >= e->queue_min_ticks || (nticks >= 8 && !(e->tick_tail_valid && e->tick_tail < e->queue_tail_min)));
+    queue = policy::queue_fits(e->queue_ok, e->queue_waves, e->N) && !e->compact_only && !e->use_order &&
+            policy::window_wants_queue(nticks, e->queue_min_ticks, e->tick_tail_valid, e->tick_tail, e->queue_tail_min);
     if (queue) chunk = e->queue_run_ticks;
     if (const char* c = getenv("MRE_RUN_CHUNK")) { const int v = atoi(c); chunk = v > 0 ? v : nticks; }  // tuning knob
   }
@@ -1794,7 +930,7 @@ extern "C" int mre_osc_compute(mre_env* e, float* tau, float* grip) {
   fill_args(e, a);
   a.nsteps = 0; a.control_steps = 1; a.mode = CTRL_OSC; a.flags = F_OSC_EVAL; a.trace = nullptr;
   HIPCHK(hipSetDevice(e->device));
-  launch_compact(e, a, e->stream);
+  step_kernels(e->solver).step(&a, e->stream);
   HIPCHK(hipGetLastError());
   const size_t N = (size_t)e->N;
   std::vector<float> h(N * NU);
@@ -1840,7 +976,7 @@ static int detect_contacts(mre_env* e, const uint8_t* dmask, bool full = false, 
   a.nsteps = 0; a.flags = F_DETECT | (active_only ? F_DETECT_ACTIVE : 0u); a.trace = nullptr; a.env_mask = dmask;
   a.contacts = e->contacts; a.contacts_full = full ? e->contacts_full : nullptr;
   a.sites = nullptr; a.geoms = nullptr;
-  launch_compact(e, a, e->stream);
+  step_kernels(e->solver).step(&a, e->stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
 }

@@ -18,8 +18,10 @@ _HEADERS = ["mre_dev.h", "mre_math.h", "mre_collide.h", "mre_solver.h", "mre_new
 # Built and watched by needs_build(), but NOT hashed by source_hash(): the record kernels (varint packing, CRC-32C of
 # episode shards) launch nothing that bench.py times, and the hash names the step / camera sources that the committed
 # counter passes (profiles/*pmc_summary*.json) were taken on -- adding a unit beside them must not orphan those.
-# The model builder is host code like mre_api.cpp: it decides what is uploaded, not what a launch executes.
-_UNHASHED_SOURCES = ["mre_records.hip", "mre_records.h", "mre_model.cpp", "mre_model.h"]
+# The model builder and the launch scheduler are host code like mre_api.cpp: they decide what is uploaded and how
+# launches are issued, not what a launch executes.
+_UNHASHED_SOURCES = ["mre_records.hip", "mre_records.h", "mre_model.cpp", "mre_model.h", "mre_sched.cpp", "mre_env.h",
+                     "mre_policy.h", "mre_launch.h"]
 _LIB: Optional[C.CDLL] = None
 
 MRE_NQ, MRE_NV, MRE_NU, MRE_NQ_PAD, MRE_NV_PAD, MRE_MAX_PROPS = 43, 39, 8, 44, 40, 4
@@ -94,7 +96,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
              ("kernels_newton", "mre_kernels.hip", ["-DMRE_NEWTON"]),
              ("kernels_large_newton", "mre_kernels.hip", ["-DMRE_LARGE_CAPS", "-DMRE_NEWTON"]),
              ("render", "mre_render.hip", []), ("records", "mre_records.hip", []), ("api", "mre_api.cpp", []),
-             ("model", "mre_model.cpp", [])]
+             ("sched", "mre_sched.cpp", []), ("model", "mre_model.cpp", [])]
     procs = [(name, subprocess.Popen(base + flags + ["-c", os.path.join(_CSRC, src), "-o",
                                                      os.path.join(bdir, name + ".o")]))
              for name, src, flags in units]

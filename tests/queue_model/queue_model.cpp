@@ -1,5 +1,5 @@
 // CPU model of the queue launches' scheduling protocol (csrc/mre_kernels.hip: queue_pop_shard / queue_pop / queue_push,
-// step_body<QUEUE>; csrc/mre_api.cpp: launch_group_enqueue) -- test infrastructure, not the product.
+// step_body<QUEUE>; csrc/mre_sched.cpp: launch_group_enqueue) -- test infrastructure, not the product.
 //
 // Threads stand for waves: `waves` compact ones in `shards` shards, `lw` large ones that wait (the launch enqueued first),
 // and after all compact threads have left, `lw` large ones that do not wait (the launch behind the compact kernel).  The

@@ -13,7 +13,7 @@ base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-f
         "-fno-hip-fp32-correctly-rounded-divide-sqrt"] + extra
 units = [("k", "mre_kernels.hip", []), ("kl", "mre_kernels.hip", ["-DMRE_LARGE_CAPS"]), ("kn", "mre_kernels.hip", ["-DMRE_NEWTON"]),
          ("kln", "mre_kernels.hip", ["-DMRE_LARGE_CAPS", "-DMRE_NEWTON"]), ("r", "mre_render.hip", []), ("rec", "mre_records.hip", []), ("api", "mre_api.cpp", []),
-         ("model", "mre_model.cpp", [])]
+         ("sched", "mre_sched.cpp", []), ("model", "mre_model.cpp", [])]
 units = [u for u in units if os.path.exists(os.path.join(CSRC, u[1]))]   # (an earlier checkout has fewer units)
 procs = []
 for u, src, flags in units:

@@ -28,7 +28,7 @@ if sys.argv[1] == "build":
                                  ("kln", "mre_kernels.hip", ["-DMRE_LARGE_CAPS", "-DMRE_NEWTON", f"-DMRE_PHASE_STAMPS={k}"]),
                                  ("r", "mre_render.hip", []),
                                  ("rec", "mre_records.hip", []),
-                                 ("api", "mre_api.cpp", []),
+                                 ("api", "mre_api.cpp", []), ("sched", "mre_sched.cpp", []),
                                  ("model", "mre_model.cpp", [])):
             objs.append(os.path.join(DIAG, f"{name}{k}.o"))
             subprocess.check_call(base + flags + ["-c", os.path.join(CSRC, src), "-o", objs[-1]])

@@ -22,13 +22,13 @@ from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # bench.py's default cut (round 5): QUEUE launches -- the warm-up window is one launch of the queue kernel, the timed
-# window ceil(K / 200) launches of all 4096 envs (csrc/mre_api.cpp: mre_env::queue_ticks).  PER_TICK=1: the launches of
+# window ceil(K / 200) launches of all 4096 envs (csrc/mre_env.h: mre_env::queue_ticks).  PER_TICK=1: the launches of
 # rounds 1-5 (bench.py --fused 1: one launch per tick and env group).
 PER_TICK = os.environ.get("PER_TICK", "0") == "1"
 KERNELS = ({"PGS": "mre::k_step(", "Newton": "mre::k_step_newton("} if PER_TICK else
            {"PGS": "mre::k_step_queue(", "Newton": "mre::k_step_queue_newton("})
 KERNEL = KERNELS["PGS"]
-GROUPS = int(os.environ.get("MRE_GROUPS", "4"))   # env groups per tick (csrc/mre_api.cpp: one launch per group)
+GROUPS = int(os.environ.get("MRE_GROUPS", "4"))   # env groups per tick (csrc/mre_sched.cpp: one launch per group)
 STEPS = int(os.environ.get("BENCH_STEPS", "200"))
 WARMUP_TICKS = int(os.environ.get("BENCH_WARMUP", "20"))
 QUEUE_TICKS = int(os.environ.get("MRE_QUEUE_TICKS", "200"))
@@ -38,7 +38,7 @@ if PER_TICK:
     ENVS_PER_LAUNCH, TICKS_PER_LAUNCH = 4096 // GROUPS, 1.0
 else:
     # bench.py's warm-up window on a fresh handle: a queue launch from 8 ticks on (nothing measured yet says the regime is
-    # light: csrc/mre_api.cpp, tick_tail), per-tick launches below
+    # light: csrc/mre_policy.h, window_wants_queue), per-tick launches below
     WARMUP = (WARMUP_TICKS + QUEUE_TICKS - 1) // QUEUE_TICKS if WARMUP_TICKS >= 8 else 0
     TIMED = (STEPS + QUEUE_TICKS - 1) // QUEUE_TICKS
     ENVS_PER_LAUNCH, TICKS_PER_LAUNCH = 4096, STEPS / float(TIMED)

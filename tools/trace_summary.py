@@ -7,7 +7,7 @@ launches, and how many of the groups' launches are in flight at a time -- from a
 
 A launch "starts" when its first workgroup gets a slot: with every slot of the GPU taken, the gap between two launches
 of one group is the wait for a slot, not host latency (the host enqueues a group's next launch before the running one
-has ended: csrc/mre_api.cpp, launch_group)."""
+has ended: csrc/mre_sched.cpp, launch_group)."""
 import collections
 import csv
 import glob
