@@ -218,6 +218,20 @@ int mre_osc_compute(mre_env*, float* tau, float* grip);
 
 /* physics.data.site_xpos[pinch] (models/robot_arm.py:55-58), controller site pose,
  * prop poses (props_info, tasks/rearrangement.py:245-246): rows [N][3], [N][7], [N][4][7] */
+#define MRE_DYN_W 128
+/* mj_jacSite / mj_fullM / qfrc_bias of the arm on the CURRENT state, no stepping: out = device pointer
+ * [N][MRE_DYN_W]; site 0 = controller (attachment) site, 1 = pinch site.  Enqueued on the handle's stream
+ * after outstanding launches are drained; no host synchronisation.  Row of one env, float32 -- the very
+ * numbers the in-kernel law (csrc/mre_osc.h) works with:
+ *   [0:42)    jac[6][7] of the site over the 7 arm dofs, rows 0-2 jacp, rows 3-5 jacr
+ *   [42:91)   mass[7][7], the arm block of the full mass matrix (reflected gripper inertia included), dense
+ *   [91:98)   qfrc_bias of the arm dofs
+ *   [98:101)  site_xpos            [101:105) site quaternion, wxyz
+ *   [105:112) arm qpos             [112:119) arm qvel            [119:128) zero
+ * Nothing but out is written: state, warm start, ctrl, status and time are as before the call, and the rows
+ * are the same whichever solver the handle runs.  MRE_ERR_ARG: null handle, null / host / misaligned (8 bytes)
+ * out, another site value. */
+int mre_get_arm_dynamics(mre_env*, int site, float* out);
 int mre_get_sites(mre_env*, float* tcp_pos, float* eef_pose, float* prop_pose);
 int mre_get_status(mre_env*, uint32_t* status);
 /* telemetry: per-env [active contacts, constraint rows, solver iterations (PGS sweeps / Newton

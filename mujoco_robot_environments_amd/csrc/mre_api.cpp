@@ -648,6 +648,23 @@ extern "C" int mre_pack_final_state(mre_env* e, float* out) {
   HIPCHK(hipGetLastError());
   return MRE_OK;
 }
+// mj_jacSite / mj_fullM / qfrc_bias of the arm on the current state, packed per env by k_arm_dynamics: out[N][MRE_DYN_W]
+// (device pointer), enqueued on the handle's stream.  One kernel for every handle: the rows do not depend on the solver.
+extern "C" int mre_get_arm_dynamics(mre_env* e, int site, float* out) {
+  if (!e || !out) return fail(MRE_ERR_ARG, "mre_get_arm_dynamics: null");
+  if (site != 0 && site != 1) return fail(MRE_ERR_ARG, "mre_get_arm_dynamics: site must be 0 (controller site) or 1 (pinch site)");
+  if (!is_device_ptr(out) || ((uintptr_t)out & 7))
+    return fail(MRE_ERR_ARG, "mre_get_arm_dynamics: out must be a device pointer, 8-byte aligned");
+  DRAIN(e);
+  HIPCHK(hipSetDevice(e->device));
+  DynArgs a;
+  memset(&a, 0, sizeof(a));
+  a.M = e->dM; a.N = e->N; a.qpos = e->qpos; a.qvel = e->qvel; a.qfine = e->qfine; a.nprops = e->nprops;
+  a.prop_size = e->prop_size; a.site = site; a.out = out;
+  mre_launch_arm_dynamics(&a, e->stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
 extern "C" int mre_set_warmstart(mre_env* e, const float* w) {
   if (!e || !w) return fail(MRE_ERR_ARG, "null");
   DRAIN(e);

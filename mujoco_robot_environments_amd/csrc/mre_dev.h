@@ -349,6 +349,25 @@ struct SearchArgs {
   int* attempts;             // [N]: attempts used (>= 1); -max_attempts: none accepted; 0: env skipped
 };
 
+// Export of the arm's dynamics terms on the current state (k_arm_dynamics; mre_get_arm_dynamics): what a torque law
+// reads -- mj_jacSite, mj_fullM, qfrc_bias -- as the float32 values the in-kernel law (mre_osc.h) consumes.  One wave per
+// env; nothing but `out` is written.  Row layout (DYN_W floats): jac[6][7] (jacp; jacr) | mass[7][7] | qfrc_bias[7] |
+// site_xpos[3] | site quaternion wxyz | arm qpos[7] | arm qvel[7] | zeros.
+constexpr int DYN_W = 128;   // MRE_DYN_W
+constexpr int DYN_JAC = 0, DYN_MASS = 42, DYN_BIAS = 91, DYN_POS = 98, DYN_QUAT = 101, DYN_QPOS = 105, DYN_QVEL = 112,
+              DYN_PAD = 119;
+struct DynArgs {
+  const DevModel* M;
+  int N;
+  const float* qpos;         // [N][NQP]
+  const float* qvel;         // [N][NVP]
+  const float* qfine;        // [N][QFINE_ROW] or null
+  const int* nprops;         // [N]
+  const float* prop_size;    // [N][NPROP][3]
+  int site;                  // 0: the controller (attachment) site, 1: the pinch site
+  float* out;                // [N][DYN_W]
+};
+
 // sort_colours' selection + prop_pick (k_sort_select; tasks/rearrangement.py:700-751, :579-595), one thread per env
 struct SortArgs {
   const DevModel* M;

@@ -2187,6 +2187,79 @@ __global__ __launch_bounds__(64) void k_pose_search(SearchArgs a) {
   }
 }
 
+// mj_jacSite / mj_fullM / qfrc_bias of the arm on the current state (DynArgs, mre_dev.h): the position and velocity
+// stages exactly as the controller evaluation of a zero-step launch runs them (step_body: F_OSC_EVAL), then the terms
+// formed as osc_compute forms o.J and o.M (lane = matrix entry) -- the float32 numbers the in-kernel law consumes.
+// The row is staged in LDS and leaves in one 512-byte store per wave; the state rows are read, never written.
+__global__ __launch_bounds__(64) void k_arm_dynamics(DynArgs a) {
+  __shared__ Sm s;
+  __shared__ alignas(8) float row[DYN_W];
+  const int env = blockIdx.x, l = threadIdx.x;
+  if (env >= a.N) return;
+  ModelP M = (ModelP)a.M;
+  // ---- load state as a step launch does (step_body); the warm start and ctrl are no input of these stages
+  if (l < NQP) s.qpos[l] = a.qpos[(size_t)env * NQP + l];
+  if (l < NVP) { s.qvel[l] = a.qvel[(size_t)env * NVP + l]; s.qacc[l] = 0.f; s.qfrc_con[l] = 0.f; }
+  if (l < QFINE) s.qlo[l] = a.qfine != nullptr ? a.qfine[(size_t)env * QFINE_ROW + l] : 0.f;
+  if (l < NU) s.ctrl[l] = 0.f;
+  if (l == 0) { s.nprops = a.nprops[env]; s.overflow = 0; s.ncon = 0; s.nefc = 0; s.solver_iters = 0; }
+  if (l < NPROP * 3) s.prop_size[l / 3][l % 3] = a.prop_size[(size_t)env * NPROP * 3 + l];
+  MRE_SYNC();
+  if (l < NPROP) {
+    const float m = M->body_mass[NRB + l];
+    const float* z = s.prop_size[l];
+    s.prop_mass[l] = m;
+    s.prop_inertia[l][0] = m / 3.f * (z[1] * z[1] + z[2] * z[2]);
+    s.prop_inertia[l][1] = m / 3.f * (z[0] * z[0] + z[2] * z[2]);
+    s.prop_inertia[l][2] = m / 3.f * (z[0] * z[0] + z[1] * z[1]);
+  }
+  MRE_SYNC();
+  position_stage(M, s, l);
+  gripper_local(M, s, l);
+  crb_mass_matrix(M, s, l);
+  MRE_SYNC();
+  velocity_stage(M, s, l);
+  MRE_SYNC();
+  const int st = a.site != 0 ? M->opt_rec.tcp_site : M->opt_rec.eef_site;
+  if (l < 42) {
+    const int r = l / 7, c = l % 7;
+    const float* cd = s.cdof[c];
+    float off[3], t[3];
+    v3sub(off, s.site_xpos[st], s.com_robot);
+    v3cross(t, cd, off);
+    row[DYN_JAC + l] = (r < 3) ? (cd[3 + r] + t[r]) : cd[r - 3];
+  }
+  if (l < 49) {
+    const int i = l / 7, j = l % 7;
+    const int hi = i > j ? i : j, lo = i > j ? j : i;
+    row[DYN_MASS + l] = s.qM[M->dof_Madr[hi] + (hi - lo)];
+  }
+  if (l >= 49 && l < 56) {
+    const int d = l - 49;
+    row[DYN_BIAS + d] = s.qfrc_bias[d];
+    row[DYN_QPOS + d] = s.qpos[d];
+    row[DYN_QVEL + d] = s.qvel[d];
+  }
+  if (l >= 56 && l < 59) row[DYN_POS + (l - 56)] = s.site_xpos[st][l - 56];
+  if (l == 59) {
+    // the controller site's orientation is kept as a matrix (osc_errors reads it); the pinch site's is composed here
+    float q[4], m[9];
+    if (a.site != 0) {
+      const auto* SR = &M->site_rec[st];
+      const float sq[4] = {SR->quat[0], SR->quat[1], SR->quat[2], SR->quat[3]};
+      qmul(q, s.xquat[SR->body], sq);
+      q2mat(m, q);
+    } else {
+      for (int k = 0; k < 9; k++) m[k] = s.site_xmat[0][k];
+    }
+    mat2q(q, m);
+    for (int k = 0; k < 4; k++) row[DYN_QUAT + k] = q[k];
+  }
+  if (l < DYN_W - DYN_PAD) row[DYN_PAD + l] = 0.f;
+  MRE_SYNC();
+  reinterpret_cast<float2*>(a.out + (size_t)env * DYN_W)[l] = make_float2(row[2 * l], row[2 * l + 1]);
+}
+
 // mju_mat2Quat on a row-major matrix, fp64, normalised (model/compile.py: m2q)
 MRE_DEV void mat2quat_d(const double* m, double* q) {
   const double t = m[0] + m[4] + m[8];
@@ -2295,6 +2368,10 @@ extern "C" void mre_launch_restore_rows(const uint8_t* sel, int env0, int N, flo
 
 extern "C" void mre_launch_pose_search(const mre::SearchArgs* args, hipStream_t stream) {
   hipLaunchKernelGGL(mre::k_pose_search, dim3(args->N), dim3(64), 0, stream, *args);
+}
+
+extern "C" void mre_launch_arm_dynamics(const mre::DynArgs* args, hipStream_t stream) {
+  hipLaunchKernelGGL(mre::k_arm_dynamics, dim3(args->N), dim3(64), 0, stream, *args);
 }
 
 extern "C" void mre_launch_sort_select(const mre::SortArgs* args, hipStream_t stream) {

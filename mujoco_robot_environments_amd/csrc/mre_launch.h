@@ -28,6 +28,7 @@ void mre_launch_restore_rows(const uint8_t* sel, int env0, int N, float* qpos, c
                              hipStream_t stream);
 void mre_launch_pose_search(const mre::SearchArgs* args, hipStream_t stream);
 void mre_launch_sort_select(const mre::SortArgs* args, hipStream_t stream);
+void mre_launch_arm_dynamics(const mre::DynArgs* args, hipStream_t stream);
 void mre_launch_reset(const mre::DevModel* M, int N, float* qpos, float* qvel, float* qacc_ws, float* qfine, float* ctrl,
                       uint32_t* status, int* nstep, const uint8_t* mask, hipStream_t stream);
 }

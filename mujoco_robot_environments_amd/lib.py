@@ -28,6 +28,7 @@ MRE_NQ, MRE_NV, MRE_NU, MRE_NQ_PAD, MRE_NV_PAD, MRE_MAX_PROPS = 43, 39, 8, 44, 4
 MRE_TRACE_W = 88   # row of the parity trace (mre_set_trace): qpos, census columns, then qvel from MRE_TRACE_QVEL on
 MRE_TRACE_QVEL = 48
 MRE_FINAL_W = 83    # row of mre_pack_final_state: qpos[43], qvel[39], status
+MRE_DYN_W = 128     # row of mre_get_arm_dynamics: jac[6][7], mass[7][7], bias[7], site pos[3] quat[4], qpos[7], qvel[7], pad
 
 EXPORTS = [
     "mre_create", "mre_destroy", "mre_last_error", "mre_num_envs", "mre_stream", "mre_sync",
@@ -39,7 +40,7 @@ EXPORTS = [
     "mre_set_fallback", "mre_get_fallback_stats", "mre_get_queue_info", "mre_set_solver", "mre_get_solver", "mre_wait_stream", "mre_osc_compute", "mre_get_contacts", "mre_get_contacts_full", "mre_get_settle_steps", "mre_get_launch_info", "mre_prop_place", "mre_sort_colours", "mre_crc32c", "mre_osc_configure_env", "mre_set_env_ids", "mre_set_render_colours", "mre_render",
     "mre_get_state_f64", "mre_set_state_f64", "mre_get_time", "mre_pack_final_state",
     "mre_records_workspace_bytes", "mre_varint_pack_rows", "mre_crc32c_rows", "mre_crc32c_combine",
-    "mre_varint_unpack_workspace_bytes", "mre_varint_unpack_rows",
+    "mre_varint_unpack_workspace_bytes", "mre_varint_unpack_rows", "mre_get_arm_dynamics",
 ]
 # status bits of mre_varint_unpack_rows (include/mre.h)
 MRE_UNPACK_LONG, MRE_UNPACK_OVERFLOW, MRE_UNPACK_TRUNCATED, MRE_UNPACK_COUNT, MRE_UNPACK_DESC = 1, 2, 4, 8, 16
@@ -164,6 +165,7 @@ def lib() -> C.CDLL:
     L.mre_get_solver.argtypes = [vp]
     L.mre_wait_stream.argtypes = [vp, vp]
     L.mre_osc_compute.argtypes = [vp, fp, fp]
+    L.mre_get_arm_dynamics.argtypes = [vp, ci, fp]
     L.mre_get_contacts.argtypes = [vp, fp, fp]
     L.mre_get_contacts_full.argtypes = [vp, ci, fp, fp]
     L.mre_get_settle_steps.argtypes = [vp, fp]

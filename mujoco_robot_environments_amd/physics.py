@@ -315,6 +315,24 @@ class BatchedPhysics:
         check(_lib.lib().mre_osc_compute(self._h, _ptr(tau), _ptr(grip)), "mre_osc_compute")
         return tau, grip
 
+    SITES = {"eef": 0, "pinch": 1}   # controller (attachment) site, gripper pinch site (include/mre.h)
+
+    def arm_dynamics(self, site="eef"):
+        """mj_jacSite / mj_fullM / qfrc_bias of the arm on the current state, no stepping (mre_get_arm_dynamics): an
+        ``ArmTerms`` (controllers/torch_osc.py) of CUDA float32 views into one [N, 128] tensor -- jac [N, 6, 7] of
+        ``site`` ("eef": the controller site, "pinch"; or 0 / 1), mass [N, 7, 7], bias [N, 7], site_pos [N, 3],
+        site_quat [N, 4], qpos [N, 7], qvel [N, 7].  The kernel runs on the handle's stream and torch's current stream is
+        ordered after it on the device: nothing waits on the host, and nothing of the handle's state is written."""
+        from .controllers.torch_osc import ArmTerms
+        out = torch.empty((self.num_envs, _lib.MRE_DYN_W), dtype=torch.float32, device=self.device)
+        self._after_torch()   # the block may have been another tensor's on torch's stream a moment ago
+        check(_lib.lib().mre_get_arm_dynamics(self._h, int(self.SITES.get(site, site)), out.data_ptr()),
+              "mre_get_arm_dynamics")
+        if getattr(self, "_ext_stream", None) is None:
+            self._ext_stream = torch.cuda.ExternalStream(self.stream_ptr, device=self.device)
+        torch.cuda.current_stream(self.device).wait_stream(self._ext_stream)
+        return ArmTerms.from_packed(out)
+
     def gripper_set(self, closed) -> None:
         c = np.ascontiguousarray(np.broadcast_to(np.asarray(closed, np.uint8), (self.num_envs,)))
         check(_lib.lib().mre_gripper_set(self._h, _ptr(c)), "mre_gripper_set")

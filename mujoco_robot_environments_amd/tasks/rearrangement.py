@@ -84,8 +84,9 @@ class BatchedRearrangementEnv:
 
     def __init__(self, cfg: Optional[Cfg] = None, num_envs: int = 1, viewer=None, device: int = 0,
                  seed: Optional[int] = None, env_id_offset: int = 0, env_ids=None, render: bool = False,
-                 solver: str = "Newton"):
+                 solver: str = "Newton", torque_law=None):
         self._cfg = cfg if cfg is not None else DEFAULT_CONFIG
+        self.torque_law = torque_law   # law(terms, target) -> tau run in place of the in-kernel OSC (models/robot_arm.py)
         cfg = self._cfg
         self.num_envs = int(num_envs)
         self.has_viewer = False  # no viewer on a headless GPU batch (tasks/rearrangement.py:64-70)
@@ -251,7 +252,7 @@ class BatchedRearrangementEnv:
         steps = int(np.abs(self._physics.settle_steps()).max())
         cp = self._cfg.robots.arm.controller_config.controller_params
         mm = self._cfg.robots.end_effector.controller_config.controller
-        self._robot = RobotArm(self._physics, controller_params=cp, gripper_cfg=mm)
+        self._robot = RobotArm(self._physics, controller_params=cp, gripper_cfg=mm, torque_law=self.torque_law)
         self._robot.time = steps * self._physics.timestep
         pose0 = np.atleast_2d(self._robot.eef_pose).copy()
         pose0[:, 0] -= 0.1  # reference shifts x although the comment says "up" (App. D.5)
