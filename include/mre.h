@@ -251,8 +251,10 @@ int mre_set_env_order(mre_env*, const int32_t* order);
  *   depth device f32 [N][H][W]    or NULL     (distance along the optical axis [m]; 100 = nothing hit)
  *   seg   device u8  [N][H][W]    or NULL     (geom index: 0 ground, 1 table, 2..11 robot hulls,
  *                                              12 + p cube p; 255 = nothing hit)
- * width must be a multiple of 4.  Enqueued on the handle's stream.  Colours: cube albedo per env
- * [N][4][3] u8 and static geom albedo [16][3] floats (NULL keeps the current / default grey). */
+ * width must be a multiple of 4 and at most 1280, height at least 1, 0 < fovy_deg < 180; depth must be 16-byte
+ * aligned, rgb and seg 4-byte aligned (MRE_ERR_ARG otherwise, nothing is written).  Enqueued on the handle's stream.
+ * Colours: cube albedo per env [N][4][3] u8 and the other geoms' albedo [20][3] floats, one row per geom (NULL keeps
+ * the current / default grey). */
 int mre_set_render_colours(mre_env*, const uint8_t* prop_rgb, const float* geom_rgb);
 int mre_render(mre_env*, const float* cam_pos, const float* cam_mat, float fovy_deg, int height, int width,
                uint8_t* rgb, float* depth, uint8_t* seg, const uint8_t* mask);

@@ -7,14 +7,14 @@
 // HBM-bound by construction: 8 B are written per pixel (f32 depth, 3 x u8 colour, u8 geom id) and
 // the only reads are 1 KB of geom poses per workgroup.  One thread owns 4 horizontally adjacent pixels
 // so that depth leaves as one 16-byte store per lane, colour as three dwords and ids as one dword; a
-// workgroup of 320 threads covers two image rows per iteration.  Per workgroup the 16 geoms are turned
+// workgroup of 320 threads covers two image rows per iteration.  Per workgroup the NG geoms are turned
 // into (camera origin, ray basis) in their own frames plus a screen-space bounding rectangle, so a
 // pixel group only intersects the geoms whose rectangle it touches.
 //
 // Ground plane and table are fixed to the world: their image is the same for every env and frame of a
 // camera.  mre_render (mre_api.cpp) renders it once (geoms [0, 2), N = 1) and keeps it; a frame then
 // starts every pixel from that background -- 2.4 MB shared by all workgroups, served from L2 /
-// Infinity Cache -- and casts only the moving geoms [2, 16), whose rectangles cover a few percent of
+// Infinity Cache -- and casts only the moving geoms [2, NG), whose rectangles cover a few percent of
 // the image, so most 4-pixel groups are a copy (1.97 ms per 4096-env frame = 0.64 of HBM peak,
 // against 3.7 ms when every pixel casts all geoms).
 //
@@ -104,6 +104,14 @@ __global__ __launch_bounds__(RENDER_THREADS) void k_render(RenderArgs a) {
   const size_t img = (size_t)env * a.height * a.width;
   for (int row0 = blockIdx.y * rows_per_iter; row0 < a.height; row0 += gridDim.y * rows_per_iter) {
     const int row = row0 + tr;
+    // geoms whose screen rectangle reaches this iteration's rows (wave-uniform bit mask: lane g of every wave
+    // evaluates the test of geom g, g < NG), then only those are visited.  The ballot counts active lanes only, so it
+    // is taken by all 64 lanes, BEFORE the lanes that have no row to draw leave: a wave whose rows end inside its
+    // first NG lanes (width 800: lanes 0..7 of wave 3) would otherwise never visit the geoms of the missing lanes.
+    const int wl = t & 63;
+    const int gq = wl < NG ? wl : 0;
+    const bool rows_hit = wl >= a.g0 && wl < a.g1 && gv[gq].type >= 0 && gv[gq].y0 <= row0 + rows_per_iter - 1 && gv[gq].y1 >= row0;
+    unsigned long long todo = __ballot(rows_hit);
     if (tr >= rows_per_iter || row >= a.height) continue;
     const int u0 = tg << 2;
     const float y = -(row - cy) * inv_f;
@@ -125,12 +133,6 @@ __global__ __launch_bounds__(RENDER_THREADS) void k_render(RenderArgs a) {
 #pragma unroll
       for (int p = 0; p < 4; p++) best_g[p] = 254;
     }
-    // geoms whose screen rectangle reaches this iteration's rows (wave-uniform bit mask: every
-    // wave evaluates the 16 tests in its first 16 lanes), then only those are visited
-    const int wl = t & 63;
-    const int gq = wl < NG ? wl : 0;
-    const bool rows_hit = wl >= a.g0 && wl < a.g1 && gv[gq].type >= 0 && gv[gq].y0 <= row0 + rows_per_iter - 1 && gv[gq].y1 >= row0;
-    unsigned long long todo = __ballot(rows_hit);
     while (todo != 0ull) {
       const int g = __builtin_ctzll(todo);
       todo &= todo - 1ull;

@@ -35,14 +35,18 @@ def geom_poses(A, qpos, nprops, half_sizes):
     return pos, mat, size, typ
 
 
-def render(A, qpos, nprops, half_sizes, prop_rgb, geom_rgb, cam_pos, cam_mat, fovy, height, width):
-    """-> rgb uint8 [H,W,3], depth float64 [H,W], seg int [H,W] (255 background)."""
+def render(A, qpos, nprops, half_sizes, prop_rgb, geom_rgb, cam_pos, cam_mat, fovy, height, width,
+           pixel_offset=(0.0, 0.0)):
+    """-> rgb uint8 [H,W,3], depth float64 [H,W], seg int [H,W] (255 background).
+    pixel_offset (du, dv): the ray of pixel (u, v) goes through (u + du, v + dv) -- the tests render a case a
+    fraction of a pixel off to find the pixels whose answer hangs on a silhouette or a checker edge."""
+    du, dv = float(pixel_offset[0]), float(pixel_offset[1])
     pos, mat, size, typ = geom_poses(A, qpos, nprops, half_sizes)
     cam_pos = np.asarray(cam_pos, np.float64); Rc = np.asarray(cam_mat, np.float64).reshape(3, 3)
     f = 0.5 * height / np.tan(np.deg2rad(fovy) / 2)
     cx, cy = 0.5 * (width - 1), 0.5 * (height - 1)
     u, v = np.meshgrid(np.arange(width), np.arange(height))
-    dc = np.stack([(u - cx) / f, -(v - cy) / f, -np.ones_like(u, float)], axis=-1)   # camera frame
+    dc = np.stack([(u + du - cx) / f, -(v + dv - cy) / f, -np.ones_like(u, float)], axis=-1)   # camera frame
     dw = dc @ Rc.T                                                                    # world frame
     best = np.full((height, width), ZFAR); seg = np.full((height, width), 255, int)
     normal = np.zeros((height, width, 3))
