@@ -78,6 +78,10 @@ def main():
         if not active.any():
             print("Task demonstration is complete")
             break
+        if args.render:   # the state the pair's first observation shows: which cubes does the camera not see at all?
+            in_use = np.arange(4)[None, :] < env.nprops[:, None]
+            hidden = int(((env.prop_labels()["visible_pixels"] == 0) & in_use).sum())
+            print(f"pair {step}: {hidden} of {int(in_use.sum())} in-use cubes have no visible pixel in the observation")
         pick_action = {"pose": pick_pose, "pixel_coords": env.world_2_pixel(cam, pick_pose[:, :3]), "gripper_rot": 0.0}
         place_action = {"pose": place_pose, "pixel_coords": env.world_2_pixel(cam, place_pose[:, :3]), "gripper_rot": 0.0}
         env.last_converged[:] = True

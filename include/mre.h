@@ -345,6 +345,24 @@ int mre_varint_unpack_rows(void* stream, const uint8_t* src, size_t src_bytes, c
  * crc_a * x^(8 len_b) mod P xor crc_b over the reflected Castagnoli polynomial. */
 uint32_t mre_crc32c_combine(uint32_t crc_a, uint32_t crc_b, size_t len_b);
 
+/* Frame labels on the device (csrc/mre_labels.hip): what props_info takes from a segmentation image
+ * (get_bbox, tasks/rearrangement.py:254-268), for every env and every label id0 .. id0 + nid - 1 in one pass.
+ *   seg    device u8  [n][height][width], contiguous, at any byte alignment (what mre_render writes, or a view of it)
+ *   depth  device f32 [n][height][width] or NULL, 4-byte aligned; finite and non-negative, which is what mre_render
+ *          writes -- negative, infinite or NaN depths are not supported (zmin is then unspecified)
+ *   stats  device int64 [n][nid][7]: {xmin, ymin, xmax, ymax, count, sum_x, sum_y} over the pixels of env e whose seg byte
+ *          is id0 + k (x = column, y = row): the PASCAL-VOC box, the visible pixel count, and the centroid's numerators
+ *   zmin   device f32 [n][nid]: the smallest depth among those pixels; NULL if and only if depth is NULL
+ * A label with no pixel gives {-1, -1, -1, -1, 0, 0, 0} and zmin = +inf.  Every output element is written by the call;
+ * the caller initialises nothing.  All arithmetic is integer (zmin: a minimum), so the outputs are the same bits on
+ * every run.  Enqueued on `stream` (hipStream_t, NULL = the legacy default stream) of the current device; nothing
+ * synchronises; no byte outside seg[0 .. n * height * width) and depth[0 .. n * height * width) is read.
+ * MRE_ERR_ARG, with nothing launched, unless n >= 0 (0: MRE_OK, nothing launched), height and width >= 1,
+ * height * width < 2^31, 1 <= nid <= 8, id0 >= 0, id0 + nid <= 256, seg and stats non-NULL device pointers (stats 8-byte
+ * aligned), depth and zmin both NULL or both 4-byte aligned device pointers. */
+int mre_seg_labels(void* stream, const uint8_t* seg, const float* depth, int n, int height, int width, int id0, int nid,
+                   int64_t* stats, float* zmin);
+
 #define MRE_SOLVER_PGS 0
 #define MRE_SOLVER_NEWTON 2
 int mre_set_solver(mre_env*, int solver);

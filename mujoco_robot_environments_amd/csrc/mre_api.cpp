@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "mre_env.h"
+#include "mre_labels.h"
 #include "mre_launch.h"
 #include "mre_model.h"
 #include "mre_records.h"
@@ -500,6 +501,31 @@ extern "C" int mre_varint_unpack_rows(void* stream, const uint8_t* src, size_t s
   a.max_src_len = max_src_len; a.rows = (uint32_t)rows; a.nseg = (uint32_t)nseg;
   a.out = out; a.out_capacity = out_capacity; a.status = status; a.segoff = (uint32_t*)workspace;
   mre_launch_varint_unpack(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+// ---- frame labels on the device (csrc/mre_labels.hip): boxes, counts, coordinate sums and nearest depth per label
+extern "C" int mre_seg_labels(void* stream, const uint8_t* seg, const float* depth, int n, int height, int width,
+                              int id0, int nid, int64_t* stats, float* zmin) {
+  const std::string w("mre_seg_labels");
+  if (n < 0 || height < 1 || width < 1 || (long long)height * width >= (1ll << 31))
+    return fail(MRE_ERR_ARG, w + ": n >= 0, height and width >= 1, height * width < 2^31");
+  if (nid < 1 || nid > (int)LAB_MAX_IDS || id0 < 0 || id0 + nid > 256)
+    return fail(MRE_ERR_ARG, w + ": 1 <= nid <= 8 labels inside 0 .. 255");
+  if (!seg || !stats) return fail(MRE_ERR_ARG, w + ": null seg or stats");
+  if ((depth == nullptr) != (zmin == nullptr)) return fail(MRE_ERR_ARG, w + ": depth and zmin go together");
+  if (((uintptr_t)depth & 3) || ((uintptr_t)zmin & 3) || ((uintptr_t)stats & 7))
+    return fail(MRE_ERR_ARG, w + ": depth and zmin must be 4-byte aligned, stats 8-byte aligned");
+  if (n == 0) return MRE_OK;
+  if (!is_device_ptr(seg) || !is_device_ptr(stats) || (depth && (!is_device_ptr(depth) || !is_device_ptr(zmin))))
+    return fail(MRE_ERR_ARG, w + ": seg, depth, stats and zmin must be device pointers");
+  LabelArgs a;
+  memset(&a, 0, sizeof(a));
+  a.seg = seg; a.depth = depth; a.n = (uint32_t)n; a.hw = (uint32_t)(height * width); a.w = (uint32_t)width;
+  a.id0 = (uint32_t)id0; a.nid = (uint32_t)nid; a.chunks = label_chunks(a.n, a.hw);
+  a.stats = (unsigned long long*)stats; a.zmin = (uint32_t*)zmin;
+  mre_launch_seg_labels(&a, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
 }

@@ -19,8 +19,9 @@ _HEADERS = ["mre_dev.h", "mre_math.h", "mre_collide.h", "mre_solver.h", "mre_new
 # episode shards) launch nothing that bench.py times, and the hash names the step / camera sources that the committed
 # counter passes (profiles/*pmc_summary*.json) were taken on -- adding a unit beside them must not orphan those.
 # The model builder and the launch scheduler are host code like mre_api.cpp: they decide what is uploaded and how
-# launches are issued, not what a launch executes.
-_UNHASHED_SOURCES = ["mre_records.hip", "mre_records.h", "mre_model.cpp", "mre_model.h", "mre_sched.cpp", "mre_env.h",
+# launches are issued, not what a launch executes.  The frame-label kernel (mre_labels.hip) reads rendered images and is
+# launched by neither the step nor the camera.
+_UNHASHED_SOURCES = ["mre_records.hip", "mre_records.h", "mre_labels.hip", "mre_labels.h", "mre_model.cpp", "mre_model.h", "mre_sched.cpp", "mre_env.h",
                      "mre_policy.h", "mre_launch.h"]
 _LIB: Optional[C.CDLL] = None
 
@@ -40,7 +41,7 @@ EXPORTS = [
     "mre_set_fallback", "mre_get_fallback_stats", "mre_get_queue_info", "mre_set_solver", "mre_get_solver", "mre_wait_stream", "mre_osc_compute", "mre_get_contacts", "mre_get_contacts_full", "mre_get_settle_steps", "mre_get_launch_info", "mre_prop_place", "mre_sort_colours", "mre_crc32c", "mre_osc_configure_env", "mre_set_env_ids", "mre_set_render_colours", "mre_render",
     "mre_get_state_f64", "mre_set_state_f64", "mre_get_time", "mre_pack_final_state",
     "mre_records_workspace_bytes", "mre_varint_pack_rows", "mre_crc32c_rows", "mre_crc32c_combine",
-    "mre_varint_unpack_workspace_bytes", "mre_varint_unpack_rows", "mre_get_arm_dynamics",
+    "mre_varint_unpack_workspace_bytes", "mre_varint_unpack_rows", "mre_get_arm_dynamics", "mre_seg_labels",
 ]
 # status bits of mre_varint_unpack_rows (include/mre.h)
 MRE_UNPACK_LONG, MRE_UNPACK_OVERFLOW, MRE_UNPACK_TRUNCATED, MRE_UNPACK_COUNT, MRE_UNPACK_DESC = 1, 2, 4, 8, 16
@@ -96,7 +97,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     units = [("kernels", "mre_kernels.hip", []), ("kernels_large", "mre_kernels.hip", ["-DMRE_LARGE_CAPS"]),
              ("kernels_newton", "mre_kernels.hip", ["-DMRE_NEWTON"]),
              ("kernels_large_newton", "mre_kernels.hip", ["-DMRE_LARGE_CAPS", "-DMRE_NEWTON"]),
-             ("render", "mre_render.hip", []), ("records", "mre_records.hip", []), ("api", "mre_api.cpp", []),
+             ("render", "mre_render.hip", []), ("records", "mre_records.hip", []),
+             ("labels", "mre_labels.hip", []), ("api", "mre_api.cpp", []),
              ("sched", "mre_sched.cpp", []), ("model", "mre_model.cpp", [])]
     procs = [(name, subprocess.Popen(base + flags + ["-c", os.path.join(_CSRC, src), "-o",
                                                      os.path.join(bdir, name + ".o")]))
@@ -189,6 +191,7 @@ def lib() -> C.CDLL:
     L.mre_varint_unpack_workspace_bytes.restype = sz
     L.mre_varint_unpack_workspace_bytes.argtypes = [ci, sz]
     L.mre_varint_unpack_rows.argtypes = [vp, fp, sz, fp, fp, fp, fp, ci, sz, fp, sz, fp, fp, sz]
+    L.mre_seg_labels.argtypes = [vp, fp, fp, ci, ci, ci, ci, ci, fp, fp]
     for name in EXPORTS:
         if name not in ("mre_last_error", "mre_stream", "mre_crc32c", "mre_crc32c_combine",
                         "mre_records_workspace_bytes", "mre_varint_unpack_workspace_bytes"):

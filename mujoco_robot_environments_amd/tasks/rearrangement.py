@@ -28,7 +28,7 @@ from typing import Dict, Optional
 import numpy as np
 from scipy.spatial.transform import Rotation as R
 
-from .. import demo_logic, placement, rng
+from .. import demo_logic, perception, placement, rng
 from ..config import Cfg, colour_separator_task_config, default_config  # noqa: F401
 from ..model import compile as _compile
 from ..model import spec as _spec
@@ -193,20 +193,30 @@ class BatchedRearrangementEnv:
     def prop_bboxes(self, seg=None) -> np.ndarray:
         """PASCAL-VOC boxes [N, 4 cubes, (xmin, ymin, xmax, ymax)] of the VISIBLE pixels of every cube
         in the segmentation image (get_bbox, tasks/rearrangement.py:254-268); -1 where a cube is not
-        in view or not in use."""
+        in view or not in use.  One pass over the image on the device (perception.seg_labels) for a CUDA
+        ``seg`` or the env's own render; ``self`` is not touched when ``seg`` is given."""
         import torch
         if seg is None:
             seg = self.render(rgb=False, depth=False)[2]
-        n, h, w = seg.shape
-        out = torch.full((n, 4, 4), -1, dtype=torch.int64, device=seg.device)
-        for p in range(4):
-            m = seg == (PROP_GEOM_ID0 + p)
-            cols, rows = m.any(dim=1), m.any(dim=2)
-            vis = cols.any(dim=1)
-            box = torch.stack([cols.int().argmax(dim=1), rows.int().argmax(dim=1),
-                               w - 1 - cols.flip(1).int().argmax(dim=1), h - 1 - rows.flip(1).int().argmax(dim=1)], dim=1)
-            out[:, p] = torch.where(vis[:, None], box, out[:, p])
-        return out.cpu().numpy()
+        box = perception.seg_labels(torch.as_tensor(seg), None, PROP_GEOM_ID0, 4).box
+        return box.contiguous().cpu().numpy()
+
+    def prop_labels(self, seg=None, depth=None) -> dict:
+        """What a frame says about every cube slot, as numpy arrays: ``bbox`` int64 [N, 4, 4] (prop_bboxes),
+        ``visible_pixels`` int64 [N, 4] (0: the cube is hidden, out of view or not in use), ``centroid`` float64
+        [N, 4, (x, y)] of the visible pixels (NaN where there are none) and ``nearest_depth`` float32 [N, 4], the
+        smallest depth among them (+inf where there are none; None when ``seg`` is given without ``depth``).
+        The images are the caller's (CUDA or CPU tensors [N, H, W]) or one ``render(rgb=False)`` of the current state
+        when neither is given; ``self`` is not touched when ``seg`` is given."""
+        import torch
+        if seg is None:
+            _, d, seg = self.render(rgb=False, depth=depth is None)
+            depth = d if depth is None else depth
+        seg = torch.as_tensor(seg)
+        lab = perception.seg_labels(seg, None if depth is None else torch.as_tensor(depth).to(seg.device), PROP_GEOM_ID0, 4)
+        return {"bbox": lab.box.contiguous().cpu().numpy(), "visible_pixels": lab.count.contiguous().cpu().numpy(),
+                "centroid": perception.centroid(lab).cpu().numpy(),
+                "nearest_depth": None if lab.zmin is None else lab.zmin.cpu().numpy()}
 
     def _compute_observation(self):
         if not self.render_observations:
@@ -393,6 +403,41 @@ class BatchedRearrangementEnv:
         w = np.linalg.inv(E) @ camc
         return w[:3] / w[3]
 
+    def pixel_2_world_batch(self, camera_name, coords, depth=None) -> np.ndarray:
+        """pixel_2_world for one pixel per env: coords [N, 2] (x, y) -> world points [N, 3] float64, row i equal to
+        ``pixel_2_world(camera_name, coords[i], env=i)``.  With rendering on, the depths are one gather from ``depth``
+        [N, H, W] (the caller's, e.g. the observation's, or one render of the batch); without, the table-plane ray.
+        A pixel outside the image raises ValueError."""
+        h, w = self.overhead_camera_height, self.overhead_camera_width
+        K = self._get_camera_intrinsics(camera_name, h, w)
+        E = self._get_camera_extrinsics(camera_name)
+        coords = np.asarray(coords, np.float64)
+        if coords.shape != (self.num_envs, 2):
+            raise ValueError(f"coords must be [{self.num_envs}, 2]")
+        rc = np.round(coords).astype(np.int64)  # coords_rounded (:509)
+        if (rc < 0).any() or (rc[:, 0] >= w).any() or (rc[:, 1] >= h).any():
+            raise ValueError(f"pixel outside the {w} x {h} image")
+        ray_c = (np.linalg.inv(K) @ np.concatenate([coords, np.ones((self.num_envs, 1))], axis=1).T).T
+        cam = self._cameras[camera_name]
+        if self.render_observations:
+            if depth is None:
+                depth = self._physics.render(cam["pos"], cam["mat"], cam["fovy"], h, w, rgb=False, seg=False)[1]
+            if tuple(depth.shape) != (self.num_envs, h, w):
+                raise ValueError(f"depth must be [{self.num_envs}, {h}, {w}]")
+            if hasattr(depth, "cpu"):
+                import torch
+                env = torch.arange(self.num_envs, device=depth.device)
+                d = depth[env, torch.as_tensor(rc[:, 1], device=depth.device), torch.as_tensor(rc[:, 0], device=depth.device)]
+                d = d.cpu().numpy().astype(np.float64)
+            else:
+                d = np.asarray(depth)[np.arange(self.num_envs), rc[:, 1], rc[:, 0]].astype(np.float64)
+        else:
+            d_w = (cam["mat"] @ (-ray_c).T).T  # camera looks along -z
+            d = (TABLE_TOP_Z - cam["pos"][2]) / d_w[:, 2]
+        camc = np.concatenate([ray_c * (-d[:, None]), np.ones((self.num_envs, 1))], axis=1)
+        wp = (np.linalg.inv(E) @ camc.T).T
+        return wp[:, :3] / wp[:, 3:4]
+
     def get_camera_params(self, camera_name):
         return {"intrinsics": self._get_camera_intrinsics(camera_name, self.overhead_camera_height, self.overhead_camera_width),
                 "extrinsics": self._get_camera_extrinsics(camera_name)}
@@ -432,6 +477,38 @@ class BatchedRearrangementEnv:
                 "rgba": self.prop_rgba[i, p].copy(), "bbox": bbox,
                 "labels": PropsLabels("cube", self.prop_colours[i][p], "plain")}
         return info
+
+    def props_info(self) -> dict:
+        """props_info_env for the whole batch, as arrays over [N envs, 4 cube slots]: ``position`` [N, 4, 3],
+        ``orientation`` [N, 4, 4] (scipy order x, y, z, w), ``rgba`` [N, 4, 4], ``bbox`` int64 [N, 4, 4],
+        ``visible_pixels`` int64 [N, 4] and ``in_use`` bool [N, 4] (slot p < nprops).  Slot p of env i agrees with
+        ``props_info_env(i)[PROP_GEOM_ID0 + p]`` wherever in_use is set; the scalar call's empty bbox (cube not in view)
+        is -1 here, like every entry of a slot not in use (position and orientation: NaN).  With rendering on, boxes and
+        visible pixel counts come from ONE segmentation render of the batch; without, boxes are the projected cube
+        corners and visible_pixels is -1 (not known).  (RearrangementEnv, the batch of one, keeps the reference's
+        ``props_info`` property: the dict of props_info_env(0).)"""
+        n = self.num_envs
+        in_use = np.arange(4)[None, :] < np.asarray(self.nprops)[:, None]
+        pose = self._physics.sites()[2].astype(np.float64)
+        qw = np.where(in_use[..., None], pose[..., 3:7], np.array([1.0, 0.0, 0.0, 0.0]))
+        qw = qw / np.linalg.norm(qw, axis=2, keepdims=True)
+        mat = np.moveaxis(_compile.q2m(np.moveaxis(qw.reshape(n * 4, 4), 1, 0)), 2, 0)   # [N * 4, 3, 3]
+        position = np.where(in_use[..., None], pose[..., :3], np.nan)
+        orientation = np.where(in_use[..., None], R.from_matrix(mat).as_quat().reshape(n, 4, 4), np.nan)
+        if self.render_observations:
+            lab = self.prop_labels(self.render(rgb=False, depth=False)[2])
+            bbox = np.where(in_use[..., None], lab["bbox"], -1)
+            visible = np.where(in_use, lab["visible_pixels"], 0)
+        else:
+            bbox = np.full((n, 4, 4), -1, np.int64)
+            visible = np.full((n, 4), -1, np.int64)
+            unit = np.array([[sx, sy, sz] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)])
+            for i, p in zip(*np.nonzero(in_use)):
+                px = self.world_2_pixel("overhead_camera/overhead_camera",
+                                        position[i, p] + (unit * self.prop_half_size[i, p]) @ mat[4 * i + p].T)
+                bbox[i, p] = [px[:, 0].min(), px[:, 1].min(), px[:, 0].max(), px[:, 1].max()]
+        return {"position": position, "orientation": orientation, "rgba": self.prop_rgba.copy(), "bbox": bbox,
+                "visible_pixels": visible, "in_use": in_use}
 
     def prop_pick_env(self, i: int, prop_id: int, info: Optional[dict] = None) -> np.ndarray:
         """tasks/rearrangement.py:579-595."""
