@@ -73,6 +73,7 @@ static int create_buffers(mre_env* e, int num_envs, int device_id) {
   e->h_large.assign(N, 0); e->h_rerun.assign(N, 0);
   { int rc = sched_create(e); if (rc) return rc; }
   if (const char* fb = getenv("MRE_NO_FALLBACK")) e->fallback = atoi(fb) == 0;  // profiling knob only
+  if (const char* ng = getenv("MRE_NARROW_GENERIC")) e->base_flags = atoi(ng) != 0 ? F_CLIP_ALWAYS : 0u;  // comparison knob only
   if (const char* fl = getenv("MRE_FORCE_LARGE")) {  // profiling knob only: start every env on the large kernel
     if (atoi(fl) != 0) {
       e->h_large.assign(N, 1); e->n_large = num_envs;
@@ -712,7 +713,7 @@ static void fill_args(mre_env* e, StepArgs& a) {
   a.M = e->dM; a.N = e->N; a.seq_stride = e->N;
   a.qpos = e->qpos; a.qvel = e->qvel; a.qacc_ws = e->qacc_ws; a.ctrl = e->ctrl; a.qfine = e->qfine;
   a.nprops = e->nprops; a.prop_size = e->prop_size;
-  a.control_steps = 1; a.mode = CTRL_HELD;
+  a.control_steps = 1; a.mode = CTRL_HELD; a.flags = e->base_flags;
   a.osc = e->d_osc_env ? e->d_osc_env : e->d_osc; a.osc_stride = e->d_osc_env ? 1 : 0;
   a.osc_target = e->osc_target; a.grip_closed = e->grip_closed;
   a.sites = e->sites; a.status = e->status; a.stats = e->stats; a.nstep = e->nstep;
@@ -724,7 +725,7 @@ extern "C" int mre_step(mre_env* e, int nsubsteps, unsigned flags) {
   if (!e || nsubsteps < 0) return fail(MRE_ERR_ARG, "mre_step: bad argument");
   StepArgs a;
   fill_args(e, a);
-  a.nsteps = nsubsteps; a.flags = flags;
+  a.nsteps = nsubsteps; a.flags |= flags;
   if (nsubsteps > 0) a.sites = nullptr;  // (site poses are refreshed by mre_get_sites: no kinematics pass for them here)
   int rc = launch_step(e, a);
   if (rc) return rc;
@@ -772,7 +773,7 @@ extern "C" int mre_rollout_ticks(mre_env* e, const float* ctrl_seq, int nticks, 
     StepArgs a;
     fill_args(e, a);   // (trace_base follows trace_pos)
     a.nsteps = nt * control_steps; a.control_steps = control_steps; a.mode = CTRL_SEQ;
-    a.ctrl_seq = src + (size_t)t0 * (size_t)e->N * NU; a.flags = flags;
+    a.ctrl_seq = src + (size_t)t0 * (size_t)e->N * NU; a.flags |= flags;
     a.sites = nullptr;  // (as in mre_step)
     int rc = launch_step(e, a, false, true, allow_queue);
     if (rc) return rc;
@@ -971,7 +972,7 @@ extern "C" int mre_osc_compute(mre_env* e, float* tau, float* grip) {
   DRAIN(e);
   StepArgs a;
   fill_args(e, a);
-  a.nsteps = 0; a.control_steps = 1; a.mode = CTRL_OSC; a.flags = F_OSC_EVAL; a.trace = nullptr;
+  a.nsteps = 0; a.control_steps = 1; a.mode = CTRL_OSC; a.flags |= F_OSC_EVAL; a.trace = nullptr;
   HIPCHK(hipSetDevice(e->device));
   step_kernels(e->solver).step(&a, e->stream);
   HIPCHK(hipGetLastError());
@@ -1004,7 +1005,7 @@ static void fill_search(mre_env* e, SearchArgs& sa) {
   memset(&sa, 0, sizeof(sa));
   sa.M = e->dM; sa.N = e->N; sa.qpos = e->qpos; sa.qfine = e->qfine; sa.nprops = e->nprops; sa.prop_size = e->prop_size;
   sa.env_ids = e->d_env_ids; sa.env_id_offset = e->env_id_offset;
-  sa.attempts = e->ps_attempts; sa.fixed_prop = -1;
+  sa.attempts = e->ps_attempts; sa.fixed_prop = -1; sa.flags = e->base_flags;
 }
 
 // physics.forward() + physics.data.contact on the current poses: one zero-step launch that runs the
@@ -1016,7 +1017,7 @@ static int detect_contacts(mre_env* e, const uint8_t* dmask, bool full = false, 
   if (full && !e->contacts_full) HIPCHK(hipMalloc(&e->contacts_full, N * CONTACT_EXPORT * 12 * 4));
   StepArgs a;
   fill_args(e, a);
-  a.nsteps = 0; a.flags = F_DETECT | (active_only ? F_DETECT_ACTIVE : 0u); a.trace = nullptr; a.env_mask = dmask;
+  a.nsteps = 0; a.flags |= F_DETECT | (active_only ? F_DETECT_ACTIVE : 0u); a.trace = nullptr; a.env_mask = dmask;
   a.contacts = e->contacts; a.contacts_full = full ? e->contacts_full : nullptr;
   a.sites = nullptr; a.geoms = nullptr;
   step_kernels(e->solver).step(&a, e->stream);
@@ -1167,7 +1168,7 @@ extern "C" int mre_place_props(mre_env* e, const uint8_t* mask, uint64_t seed, c
     // _max_settle_physics_time = 2 s; min time = settle_steps * dt (0.3 s in the reference)
     a.nsteps = (int)std::lround(2.0 / e->hM.opt_rec.timestep);
     if (a.nsteps < settle_steps) a.nsteps = settle_steps;
-    a.flags = F_FREEZE_ROBOT | F_SETTLE_EXIT; a.env_mask = e->mask;
+    a.flags |= F_FREEZE_ROBOT | F_SETTLE_EXIT; a.env_mask = e->mask;
     a.settle_steps = e->settle_steps; a.min_settle_steps = settle_steps;
     const bool prof = e->profiling;
     e->profiling = false;  // setup, not a control tick

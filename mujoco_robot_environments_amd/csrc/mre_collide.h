@@ -9,6 +9,9 @@
 // supporting edges.  Contact position is midway between the surfaces, normal
 // points from geom1 to geom2, dist < 0 is penetration (MuJoCo conventions).
 // Output: candidate k < n = position cand_xyz(buf,k)[0..2] and distance cand_dist(buf,k).
+// A face contact whose incident face lies wholly inside the reference face (a cube resting on the table) has
+// nothing to clip: its candidates are the four incident vertices, and they stay in registers (FaceCand) -- the
+// lane does not touch its LDS buffer.  The candidates are bit for bit those of the clipped path, in its order.
 #pragma once
 #include "mre_math.h"
 
@@ -17,6 +20,13 @@ namespace mre {
 constexpr int COLL_BUF = 48;   // floats per lane: poly[8][3] | q[8][3]; candidates: xyz in q, dist in poly[.][2]
 MRE_DEV float* cand_xyz(float* buf, int k) { return buf + 24 + 3 * k; }
 MRE_DEV float& cand_dist(float* buf, int k) { return buf[3 * k + 2]; }
+
+// Candidates of an unclipped face contact: slot v belongs to incident vertex v (fixed slots, constant indices only:
+// the struct lives in registers).  Mask bits 0..3: slot v holds a candidate; FACE_IN_REGS: the lane's candidates are
+// here and not in its LDS buffer.
+struct FaceCand { float x[4], y[4], z[4], d[4]; };
+constexpr unsigned FACE_IN_REGS = 16u;
+constexpr unsigned FACE_BRANCH = 32u;   // (diagnostic builds: the lane took the face-contact branch)
 
 // runtime pick of one of three values by arithmetic masks (a select chain over a local
 // array is turned back into an indexed stack access by the compiler -> scratch memory)
@@ -65,10 +75,16 @@ MRE_DEV int clip_poly(float* p, float* q, int n, float sx, float sy) {
   return n;
 }
 
+// the test clip_poly makes of one coordinate against one edge of the reference face
+MRE_DEV bool clip_keeps(float sg, float coord, float lim) { return sg * coord - lim <= 0; }
+
 // R1/R2: 3x3 row-major geom frames (columns = box axes); buf: this lane's LDS buffer.
-// Returns the number of candidates written (cand_xyz / cand_dist).
+// Returns the number of candidates written: to cand_xyz / cand_dist, or -- rmask & FACE_IN_REGS -- to the slots of rc
+// that rmask names.  clip_always: every face contact goes through clip_poly and the LDS buffer.
 MRE_DEV int box_box(const float* p1, const float* R1, const float* s1, const float* p2,
-                    const float* R2, const float* s2, float margin, float* normal, float* buf) {
+                    const float* R2, const float* s2, float margin, float* normal, float* buf,
+                    bool clip_always, FaceCand& rc, unsigned& rmask) {
+  rmask = 0u;
   float* poly = buf;
   float* qbuf = buf + 24;
   float A[3][3], B[3][3], dv[3], Cm[3][3], aC[3][3];
@@ -192,6 +208,7 @@ MRE_DEV int box_box(const float* p1, const float* R1, const float* s1, const flo
   v3addscl(ci, Aik, isg * sik);
   v3copy(cr, pr);
   v3addscl(cr, nr, sra);
+  float vx[4], vy[4], vd[4];
 #pragma unroll
   for (int v = 0; v < 4; v++) {
     const float su = (v == 0 || v == 3) ? 1.0f : -1.0f;
@@ -201,10 +218,36 @@ MRE_DEV int box_box(const float* p1, const float* R1, const float* s1, const flo
     v3addscl(w, Aiu, su * siu);
     v3addscl(w, Aiv, sv * siv);
     v3sub(w, w, cr);
-    poly[3 * v] = v3dot(w, Aru);
-    poly[3 * v + 1] = v3dot(w, Arv);
-    poly[3 * v + 2] = v3dot(w, nr);
+    vx[v] = v3dot(w, Aru);
+    vy[v] = v3dot(w, Arv);
+    vd[v] = v3dot(w, nr);
   }
+#if defined(MRE_PHASE_STAMPS)
+  rmask = FACE_BRANCH;
+#endif
+  // every vertex on the inner side of all four edges (clip_poly's own comparisons: on the edge counts as inside, a
+  // NaN as outside): the clipped polygon is the incident face itself, in the same order
+  bool inside = !clip_always;
+#pragma unroll
+  for (int v = 0; v < 4; v++)
+    inside = inside && clip_keeps(1.0f, vx[v], sru) && clip_keeps(-1.0f, vx[v], sru) &&
+             clip_keeps(1.0f, vy[v], srv) && clip_keeps(-1.0f, vy[v], srv);
+  if (inside) {
+    rmask |= FACE_IN_REGS;
+    int nc = 0;
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+      const float x = vx[v], y = vy[v], dep = vd[v];
+      rc.x[v] = cr[0] + x * Aru[0] + y * Arv[0] + 0.5f * dep * nr[0];
+      rc.y[v] = cr[1] + x * Aru[1] + y * Arv[1] + 0.5f * dep * nr[1];
+      rc.z[v] = cr[2] + x * Aru[2] + y * Arv[2] + 0.5f * dep * nr[2];
+      rc.d[v] = dep;
+      if (!(dep > margin)) { rmask |= 1u << v; nc++; }
+    }
+    return nc;
+  }
+#pragma unroll
+  for (int v = 0; v < 4; v++) { poly[3 * v] = vx[v]; poly[3 * v + 1] = vy[v]; poly[3 * v + 2] = vd[v]; }
   const int n = clip_poly(poly, qbuf, 4, sru, srv);
   int nc = 0;
   for (int v = 0; v < n; v++) {

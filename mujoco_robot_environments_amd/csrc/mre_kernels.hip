@@ -1723,7 +1723,7 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
     const bool constrained = (a.flags & F_NO_CONSTRAINTS) == 0;
     if (constrained) {
 
-      collide(M, s, l, false);
+      collide(M, s, l, false, (a.flags & F_CLIP_ALWAYS) != 0);
       MRE_STAMP(2);
       assemble_constraints(M, s, l);
 #ifdef MRE_NEWTON
@@ -1858,7 +1858,7 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
   if (a.nsteps == 0 && (a.flags & F_DETECT) != 0 && a.contacts != nullptr) {
     // physics.forward() + physics.data.contact: kinematics, then every detected contact
     position_stage(M, s, l);
-    collide(M, s, l, (a.flags & F_DETECT_ACTIVE) == 0);
+    collide(M, s, l, (a.flags & F_DETECT_ACTIVE) == 0, (a.flags & F_CLIP_ALWAYS) != 0);
     float* o = a.contacts + (size_t)env * (1 + 3 * CONTACT_EXPORT);
     const int n = s.ncon < CONTACT_EXPORT ? s.ncon : CONTACT_EXPORT;
     if (l == 0) o[0] = s.overflow ? -(float)s.ncon : (float)s.ncon;   // negative: the list is cut
@@ -2153,17 +2153,25 @@ __global__ __launch_bounds__(64) void k_pose_search(SearchArgs a) {
       geom_pose(M, s, g2, p2, R2, s2, &rb2);
       const float inc = M->pair_margin[pr];
       int n = 0;
+      FaceCand rc;
+      unsigned rm = 0u;
       v3sub(df, p2, p1);
       if (M->geom_type[g1] == 0) {
         float nn[3] = {R1[2], R1[5], R1[8]};
         if (v3dot(df, nn) - rb2 <= inc) n = plane_box(p1, R1, p2, R2, s2, inc, normal, buf);
       } else {
         const float r = rb1 + rb2 + inc;
-        if (v3dot(df, df) <= r * r) n = box_box(p1, R1, s1, p2, R2, s2, inc, normal, buf);
+        if (v3dot(df, df) <= r * r) n = box_box(p1, R1, s1, p2, R2, s2, inc, normal, buf, (a.flags & F_CLIP_ALWAYS) != 0, rc, rm);
       }
-      for (int c = 0; c < n; c++) {
-        const float d = cand_dist(buf, c);
-        if (d < inc && d <= a.max_dist) hit = true;   // a detected contact (dist < margin) close enough to reject
+      if (rm & FACE_IN_REGS) {   // an unclipped face contact: its candidates are in registers (mre_collide.h)
+#pragma unroll
+        for (int v = 0; v < 4; v++)
+          if (((rm >> v) & 1u) != 0u && rc.d[v] < inc && rc.d[v] <= a.max_dist) hit = true;
+      } else {
+        for (int c = 0; c < n; c++) {
+          const float d = cand_dist(buf, c);
+          if (d < inc && d <= a.max_dist) hit = true;   // a detected contact (dist < margin) close enough to reject
+        }
       }
     }
     const bool any = __ballot(hit) != 0ull;

@@ -1,9 +1,14 @@
 // mre_math.h -- small fp32 vector / quaternion / spatial-algebra helpers for
 // the gfx950 kernels (per-lane scalar code; cross-lane work lives in the kernels).
 #pragma once
+// (a host harness defines MRE_DEV itself -- static inline -- and compiles the per-lane code for the CPU,
+//  tests/narrow_phase_host; the cross-lane helpers and the hardware estimates below are then left out)
+#ifndef MRE_DEV
 #include <hip/hip_runtime.h>
-
 #define MRE_DEV __device__ __forceinline__
+#else
+#define MRE_PER_LANE_ONLY
+#endif
 // whole phases are real functions: register allocation is scoped per phase instead of across
 // the fused step loop (the inlined kernel needed 332 registers -> 1 wave per SIMD)
 // Diagnostic builds (-DMRE_PHASE_STAMPS=4, 5, ...: tools/phase_stamps.py): time inside a phase function by part,
@@ -50,8 +55,10 @@ constexpr float kMinVal = 1e-15f;
 // A use of x that costs no instruction.  Placed where the branches of a phase meet, it keeps a load issued at the
 // phase's entry THERE: the optimiser otherwise sinks a load whose only user sits in one branch into that branch, where
 // it becomes a trip to memory of its own, waited for at once (model records, mre_dev.h).
+#ifndef MRE_PER_LANE_ONLY
 MRE_DEV void keep_live(float x) { asm volatile("" ::"v"(x)); }
 MRE_DEV void keep_live(int x) { asm volatile("" ::"v"(x)); }
+#endif
 
 MRE_DEV void v3copy(float* r, const float* a) { r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; }
 MRE_DEV void v3zero(float* r) { r[0] = r[1] = r[2] = 0.f; }
@@ -178,6 +185,7 @@ MRE_DEV void cross_force(float* r, const float* vel, const float* f) {
 MRE_DEV float dot6(const float* a, const float* b) {
   return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3] + a[4] * b[4] + a[5] * b[5];
 }
+#ifndef MRE_PER_LANE_ONLY
 // wave64 sum, result uniform in every lane: DPP row reduction (quad_perm, row_half_mirror,
 // row_mirror), row_bcast15 / row_bcast31 across the four 16-lane rows, readlane 63.
 template <int CTRL, int ROW_MASK>
@@ -239,8 +247,10 @@ MRE_DEV float wave_max(float v) {
   v = dpp_max<0x143, 0xC>(v);
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+#endif
 MRE_DEV float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
+#ifndef MRE_PER_LANE_ONLY
 // fp64 reciprocal and reciprocal square root (PGS: robot-contact block update; integrator: the cubes' quaternions): the hardware estimates (v_rcp_f64 /
 // v_rsq_f64, ~2^-26 relative) + two Newton steps = 1e-16, a third of the instructions of the IEEE division / sqrt
 // sequences with their scaling and fix-up steps (operands here are never denormal, zero or infinite: guarded by the callers)
@@ -254,6 +264,6 @@ MRE_DEV double rsq64(double x) {
   y = y * (1.5 - 0.5 * x * y * y);
   return y * (1.5 - 0.5 * x * y * y);
 }
-
+#endif
 
 }  // namespace mre

@@ -81,14 +81,20 @@ MRE_DEV void geom_center(ModelP M, const Sm& s, int g, float* p, float* rbound) 
 // Narrow phase: lane = survivor (one pass for up to 64 of them; a scene has a dozen), full geom frames,
 // box-box / plane-box, then the per-lane candidate counts are turned into output slots by a ballot prefix
 // sum, so contacts come out in pair order exactly as a pair-by-pair loop would list them.
-MRE_PHASE_FN void collide(ModelP M, Sm& s, int l, bool detect) {
+// A lane whose box_box returns its candidates in registers (FACE_IN_REGS, mre_collide.h: an unclipped face contact)
+// filters, reduces and stores them from there, in the order and with the expressions of the LDS loops;
+// clip_always (F_CLIP_ALWAYS, wave-uniform) sends every lane through the LDS path.
+// The two stages are phase functions of their own and the loop over the narrow passes (one, as a rule) is the
+// caller's: inside one function the compiler hoists every address and constant of the narrow phase out of that loop
+// and carries the register candidates round it -- 246 VGPRs in one function, 72 and 166 in two (profiles/NOTES.md, round 11).
+// Broad phase: returns the number of survivors listed in s.iscr.
+MRE_PHASE_FN int collide_broad(ModelP M, Sm& s, int l, bool detect) {
   // per-lane clip buffers alias the Jacobian pools (contiguous Jp|Jr|Br, unused until assembly)
   // [JpA .. sched] is one contiguous block of arrays that are only written after collision
   static_assert(offsetof(Sm, hdr) + sizeof(((Sm*)0)->hdr) - offsetof(Sm, JpA) >= sizeof(float) * 64 * COLL_BUF,
                 "clip buffers do not fit");
   static_assert(NPAIR <= 256 && sizeof(((Sm*)0)->iscr) >= NPAIR, "survivor list: one byte per pair");
   MRE_DBG_T0();
-  float* buf = &s.JpA[0][0] + l * COLL_BUF;
   uint8_t* list = reinterpret_cast<uint8_t*>(s.iscr);
   const unsigned long long lt = (1ull << l) - 1ull;   // lanes below this one
   int nsurv = 0;
@@ -126,11 +132,21 @@ MRE_PHASE_FN void collide(ModelP M, Sm& s, int l, bool detect) {
   if (l == 0) s.ncon = 0;
   MRE_SYNC();
   MRE_DBG_STAMP(6, 0);
-  int base = 0;  // contacts kept by the earlier passes
-  for (int c0 = 0; c0 < nsurv; c0 += 64) {
+  return nsurv;
+}
+// One narrow pass over the survivors c0 .. c0 + 63; base: contacts kept by the earlier passes.  Returns the contacts
+// found so far (more than NCON_MAX: overflow, nothing further is stored).
+MRE_PHASE_FN int collide_narrow(ModelP M, Sm& s, int l, bool detect, bool clip_always, int c0, int nsurv, int base) {
+  MRE_DBG_T0();
+  float* buf = &s.JpA[0][0] + l * COLL_BUF;
+  const uint8_t* list = reinterpret_cast<const uint8_t*>(s.iscr);
+  const unsigned long long lt = (1ull << l) - 1ull;   // lanes below this one
+  {
     const int pr = (c0 + l < nsurv) ? list[c0 + l] : -1;
     float normal[3] = {0.f, 0.f, 1.f};
     int n = 0;
+    FaceCand rc;         // read only under the mask bits of rm
+    unsigned rm = 0u;
     if (pr >= 0) {
       const auto* R = &M->pair_rec[pr];
       const int b1 = R->b1, b2 = R->b2, pid1 = R->pid1, pid2 = R->pid2, type1 = R->type1;
@@ -150,20 +166,38 @@ MRE_PHASE_FN void collide(ModelP M, Sm& s, int l, bool detect) {
       MRE_DBG_STAMP(6, 1);
       if ((R->single >> 8) == 2) n = cyl_box(p1, R1, s1, p2, R2, s2[0], s2[2], inc, normal, buf);   // geom 2 is a cylinder
       else if (type1 == 0) n = plane_box(p1, R1, p2, R2, s2, inc, normal, buf);
-      else n = box_box(p1, R1, s1, p2, R2, s2, inc, normal, buf);
+      else n = box_box(p1, R1, s1, p2, R2, s2, inc, normal, buf, clip_always, rc, rm);
       MRE_DBG_STAMP(6, 2);
       // instantiate only contacts with dist < includemargin
       int m = 0;
-      for (int c = 0; c < n; c++)
-        if (cand_dist(buf, c) < inc) {
-          if (m != c) {
-            for (int k = 0; k < 3; k++) cand_xyz(buf, m)[k] = cand_xyz(buf, c)[k];
-            cand_dist(buf, m) = cand_dist(buf, c);
-          }
-          m++;
+      if (rm & FACE_IN_REGS) {
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+          if (((rm >> v) & 1u) != 0u && rc.d[v] < inc) m++;
+          else rm &= ~(1u << v);
         }
+      } else {
+        for (int c = 0; c < n; c++)
+          if (cand_dist(buf, c) < inc) {
+            if (m != c) {
+              for (int k = 0; k < 3; k++) cand_xyz(buf, m)[k] = cand_xyz(buf, c)[k];
+              cand_dist(buf, m) = cand_dist(buf, c);
+            }
+            m++;
+          }
+      }
       n = m;
     }
+#if defined(MRE_PHASE_STAMPS) && MRE_PHASE_STAMPS == 8
+    {   // face contacts of the wave, those that stayed in registers, and the same two for pairs with the table (geom 1)
+      const bool tbl = pr >= 0 && (M->pair_rec[pr].g1 == 1);
+      const unsigned long long fb = __ballot((rm & FACE_BRANCH) != 0u), fr = __ballot((rm & FACE_IN_REGS) != 0u), tb = __ballot(tbl);
+      if (l == 0) {
+        dbg_acc[0] += (unsigned long long)__popcll(fb) << 4; dbg_acc[1] += (unsigned long long)__popcll(fr) << 4;
+        dbg_acc[2] += (unsigned long long)__popcll(fb & tb) << 4; dbg_acc[3] += (unsigned long long)__popcll(fr & tb) << 4;
+      }
+    }
+#endif
     // mesh stand-in pairs keep ONE contact, like MuJoCo's convex-mesh test (formed at the write-out below)
     const bool single = pr >= 0 && n > 1 && (M->pair_rec[pr].single & 0xFF) != 0;
     const int ncand = n;
@@ -184,37 +218,75 @@ MRE_PHASE_FN void collide(ModelP M, Sm& s, int l, bool detect) {
       // below the threshold (the deepest point alone jumps between the corners of the clip polygon when two faces are
       // nearly parallel; oracle: collision()).  Written into candidate slot 0, which the loop below stores.
       const float incw = M->pair_rec[pr].margin - M->pair_rec[pr].gap;
-      float wsum = 0.f, px = 0.f, py = 0.f, pz = 0.f, dmin = cand_dist(buf, 0);
-      int best = 0;
-      for (int c = 0; c < ncand; c++) {
-        const float dc = cand_dist(buf, c);
-        if (dc < dmin) { dmin = dc; best = c; }
-        const float w = incw - dc;
-        if (w > 0.f) { wsum += w; px += w * cand_xyz(buf, c)[0]; py += w * cand_xyz(buf, c)[1]; pz += w * cand_xyz(buf, c)[2]; }
+      if (rm & FACE_IN_REGS) {
+        float wsum = 0.f, px = 0.f, py = 0.f, pz = 0.f, dmin = 0.f, bx = 0.f, by = 0.f, bz = 0.f;
+        bool first = true;
+#pragma unroll
+        for (int v = 0; v < 4; v++)
+          if (((rm >> v) & 1u) != 0u) {
+            const float dc = rc.d[v];
+            if (first || dc < dmin) { dmin = dc; bx = rc.x[v]; by = rc.y[v]; bz = rc.z[v]; }
+            first = false;
+            const float w = incw - dc;
+            if (w > 0.f) { wsum += w; px += w * rc.x[v]; py += w * rc.y[v]; pz += w * rc.z[v]; }
+          }
+        if (wsum > 0.f) { const float iw = 1.0f / wsum; px *= iw; py *= iw; pz *= iw; }
+        else { px = bx; py = by; pz = bz; }
+        rc.x[0] = px; rc.y[0] = py; rc.z[0] = pz; rc.d[0] = dmin;
+        rm = FACE_IN_REGS | 1u;
+      } else {
+        float wsum = 0.f, px = 0.f, py = 0.f, pz = 0.f, dmin = cand_dist(buf, 0);
+        int best = 0;
+        for (int c = 0; c < ncand; c++) {
+          const float dc = cand_dist(buf, c);
+          if (dc < dmin) { dmin = dc; best = c; }
+          const float w = incw - dc;
+          if (w > 0.f) { wsum += w; px += w * cand_xyz(buf, c)[0]; py += w * cand_xyz(buf, c)[1]; pz += w * cand_xyz(buf, c)[2]; }
+        }
+        if (wsum > 0.f) { const float iw = 1.0f / wsum; px *= iw; py *= iw; pz *= iw; }
+        else { px = cand_xyz(buf, best)[0]; py = cand_xyz(buf, best)[1]; pz = cand_xyz(buf, best)[2]; }
+        cand_xyz(buf, 0)[0] = px; cand_xyz(buf, 0)[1] = py; cand_xyz(buf, 0)[2] = pz;
+        cand_dist(buf, 0) = dmin;
       }
-      if (wsum > 0.f) { const float iw = 1.0f / wsum; px *= iw; py *= iw; pz *= iw; }
-      else { px = cand_xyz(buf, best)[0]; py = cand_xyz(buf, best)[1]; pz = cand_xyz(buf, best)[2]; }
-      cand_xyz(buf, 0)[0] = px; cand_xyz(buf, 0)[1] = py; cand_xyz(buf, 0)[2] = pz;
-      cand_dist(buf, 0) = dmin;
     }
     if (n > 0) {
       float f[9];
       v3copy(f, normal);
       make_frame(f);
-      for (int c = 0; c < n; c++) {
-        const int id = off + c;
-        if (id >= NCON_MAX) break;
-        const float cx0 = cand_xyz(buf, c)[0], cx1 = cand_xyz(buf, c)[1], cx2 = cand_xyz(buf, c)[2];
-        s.con_pos[id][0] = cx0; s.con_pos[id][1] = cx1; s.con_pos[id][2] = cx2;
-        for (int k = 0; k < 9; k++) s.con_frame[id][k] = f[k];
-        s.con_dist[id] = cand_dist(buf, c);
-        s.con_pair[id] = (uint8_t)pr;
+      if (rm & FACE_IN_REGS) {
+        int id = off;   // slots in vertex order; past NCON_MAX nothing more is stored
+#pragma unroll
+        for (int v = 0; v < 4; v++)
+          if (((rm >> v) & 1u) != 0u && id < NCON_MAX) {
+            s.con_pos[id][0] = rc.x[v]; s.con_pos[id][1] = rc.y[v]; s.con_pos[id][2] = rc.z[v];
+            for (int k = 0; k < 9; k++) s.con_frame[id][k] = f[k];
+            s.con_dist[id] = rc.d[v];
+            s.con_pair[id] = (uint8_t)pr;
+            id++;
+          }
+      } else {
+        for (int c = 0; c < n; c++) {
+          const int id = off + c;
+          if (id >= NCON_MAX) break;
+          const float cx0 = cand_xyz(buf, c)[0], cx1 = cand_xyz(buf, c)[1], cx2 = cand_xyz(buf, c)[2];
+          s.con_pos[id][0] = cx0; s.con_pos[id][1] = cx1; s.con_pos[id][2] = cx2;
+          for (int k = 0; k < 9; k++) s.con_frame[id][k] = f[k];
+          s.con_dist[id] = cand_dist(buf, c);
+          s.con_pair[id] = (uint8_t)pr;
+        }
       }
     }
     MRE_SYNC();
     MRE_DBG_STAMP(6, 3);
-    if (tot > NCON_MAX) break;   // (overflow: the env is re-run on the large kernel, or reported)
-    base = tot;
+    return tot;
+  }
+}
+MRE_DEV void collide(ModelP M, Sm& s, int l, bool detect, bool clip_always) {
+  const int nsurv = collide_broad(M, s, l, detect);
+  int base = 0;
+  for (int c0 = 0; c0 < nsurv; c0 += 64) {
+    base = collide_narrow(M, s, l, detect, clip_always, c0, nsurv, base);
+    if (base > NCON_MAX) break;   // (overflow: the env is re-run on the large kernel, or reported)
   }
 }
 

@@ -14,11 +14,15 @@ NAMES = ["position+crb+factor", "velocity", "collide", "assemble", "control", "s
          "  direction: M rows", "  direction: J'DJ on the matrix cores", "  direction: tiles to rows", "  direction: elimination, both solves, decrement",
          "  position_stage: kinematics", "  position_stage: comPos", "  (unused)", "  (unused)",
          "  collide: broad phase", "  collide: geom frames", "  collide: box-box / plane-box", "  collide: filter, prefix, write-out",
-         "  search: M v, J v", "  search: line search", "  search: move, update, J'f, gradient", "  (unused)"]
+         "  search: M v, J v", "  search: line search", "  search: move, update, J'f, gradient", "  (unused)",
+         # set 8 counts, it does not time: lanes per env and tick (5 steps) that took box_box's face-contact branch, those
+         # whose candidates stayed in registers (mre_collide.h), and the same two over the pairs with the table
+         "  collide: face contacts", "  collide: face contacts kept in registers", "  collide: table face contacts",
+         "  collide: table face contacts kept in registers"]
 
 if sys.argv[1] == "build":
     os.makedirs(DIAG, exist_ok=True)
-    for k in ([int(x) for x in sys.argv[2:]] or (0, 1, 2, 3, 4, 5, 6, 7)):
+    for k in ([int(x) for x in sys.argv[2:]] or (0, 1, 2, 3, 4, 5, 6, 7, 8)):
         base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-ffp-contract=on",
                 "-fno-hip-fp32-correctly-rounded-divide-sqrt"]
         objs = []

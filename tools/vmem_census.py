@@ -20,7 +20,8 @@ UNITS = [("kernels (compact PGS)", []), ("kernels_large (large PGS)", ["-DMRE_LA
          ("kernels_newton (compact Newton)", ["-DMRE_NEWTON"]),
          ("kernels_large_newton (large Newton)", ["-DMRE_LARGE_CAPS", "-DMRE_NEWTON"])]
 # the phases one step of the flagship (Newton) workload runs outside the solver, in the order of the step
-STEP_PHASES = ["position_stage", "gripper_local", "connect_rows_local", "velocity_stage", "finger_bias", "collide",
+STEP_PHASES = ["position_stage", "gripper_local", "connect_rows_local", "velocity_stage", "finger_bias", "collide_broad",
+               "collide_narrow",
                "assemble_constraints", "arm_actuation", "smooth_forces_assemble", "integrate_setup", "integrate"]
 
 LOAD = re.compile(r"^\s+(global_load|flat_load)_")
