@@ -363,6 +363,34 @@ uint32_t mre_crc32c_combine(uint32_t crc_a, uint32_t crc_b, size_t len_b);
 int mre_seg_labels(void* stream, const uint8_t* seg, const float* depth, int n, int height, int width, int id0, int nid,
                    int64_t* stats, float* zmin);
 
+/* Orthographic heightmaps on the device (csrc/mre_heightmap.hip): the top-down height, colour and label
+ * maps a Transporter network is trained on, from the frames of mre_render (or any frames of that layout).
+ *   depth  device f32 [n][height][width], 4-byte aligned      rgb  device u8 [n][height][width][3] or NULL
+ *   seg    device u8  [n][height][width] or NULL
+ *   cam    HOST f32 [12]: A row-major, then the camera position pos; A = -R K^-1 (pixel_2_world,
+ *          tasks/rearrangement.py:505-531), formed in float64 and rounded once
+ *   bounds HOST f32 [6]: lo[3], hi[3] of the box the map covers; cells are 1 / inv_cell wide
+ * For env e and pixel (u, v) with depth d, in float32 with every operation rounded on its own (no fused multiply-add):
+ *   t0 = A[k][0]*u;  t1 = A[k][1]*v;  s = t0 + t1;  s = s + A[k][2];  m = d*s;  P[k] = pos[k] + m      (k = 0, 1, 2)
+ *   cx = floorf((P[0] - lo[0]) * inv_cell)      cy = floorf((P[1] - lo[1]) * inv_cell)      hz = P[2] - lo[2]
+ *   valid  <=>  d > 0  &&  d < max_depth  &&  0 <= cx < out_w  &&  0 <= cy < out_h  &&  lo[2] <= P[2] <= hi[2]
+ * (NaN and infinite depths are not valid).  Cell (row cy, column cx) takes the valid pixel with the largest hz, among
+ * equal hz the smallest index v * width + u:
+ *   hmap  device f32 [n][out_h][out_w]     hz                  0.0f where no pixel landed
+ *   cmap  device u8  [n][out_h][out_w][3]  the pixel's rgb     0, 0, 0        NULL if and only if rgb is NULL
+ *   smap  device u8  [n][out_h][out_w]     the pixel's seg     255            NULL if and only if seg is NULL
+ *   src   device i32 [n][out_h][out_w]     the pixel's index   -1             or NULL
+ * A filled cell may hold hz = 0.0: src tells filled from empty.  Every element of every non-NULL output is written by
+ * the call and nothing else is; no byte outside the n images is read; the outputs are the same bits on every run.
+ * Enqueued on `stream` (hipStream_t, NULL = the legacy default stream) of the current device; nothing synchronises.
+ * MRE_ERR_ARG, with nothing launched, unless n >= 0 (0: MRE_OK, nothing launched), height and width >= 1,
+ * height * width < 2^31, 1 <= out_h, out_w <= 4096, inv_cell > 0 and max_depth > 0 (finite), cam and bounds non-NULL,
+ * lo <= hi (finite), depth and hmap non-NULL 4-byte-aligned device pointers, cmap NULL exactly when rgb is, smap NULL
+ * exactly when seg is, src NULL or a 4-byte-aligned device pointer. */
+int mre_heightmap(void* stream, const float* depth, const uint8_t* rgb, const uint8_t* seg, int n, int height, int width,
+                  const float* cam, const float* bounds, float inv_cell, float max_depth, int out_h, int out_w,
+                  float* hmap, uint8_t* cmap, uint8_t* smap, int32_t* src);
+
 #define MRE_SOLVER_PGS 0
 #define MRE_SOLVER_NEWTON 2
 int mre_set_solver(mre_env*, int solver);

@@ -14,6 +14,7 @@
 
 #include "mre_env.h"
 #include "mre_labels.h"
+#include "mre_heightmap.h"
 #include "mre_launch.h"
 #include "mre_model.h"
 #include "mre_records.h"
@@ -527,6 +528,60 @@ extern "C" int mre_seg_labels(void* stream, const uint8_t* seg, const float* dep
   a.id0 = (uint32_t)id0; a.nid = (uint32_t)nid; a.chunks = label_chunks(a.n, a.hw);
   a.stats = (unsigned long long*)stats; a.zmin = (uint32_t*)zmin;
   mre_launch_seg_labels(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+// ---- orthographic heightmaps on the device (csrc/mre_heightmap.hip): height, colour, label and source pixel per cell
+extern "C" int mre_heightmap(void* stream, const float* depth, const uint8_t* rgb, const uint8_t* seg, int n, int height,
+                             int width, const float* cam, const float* bounds, float inv_cell, float max_depth, int out_h,
+                             int out_w, float* hmap, uint8_t* cmap, uint8_t* smap, int32_t* src) {
+  const std::string w("mre_heightmap");
+  if (n < 0 || height < 1 || width < 1 || (long long)height * width >= (1ll << 31))
+    return fail(MRE_ERR_ARG, w + ": n >= 0, height and width >= 1, height * width < 2^31");
+  if (out_h < 1 || out_w < 1 || out_h > (int)HM_MAX_OUT || out_w > (int)HM_MAX_OUT)
+    return fail(MRE_ERR_ARG, w + ": 1 <= out_h, out_w <= 4096");
+  if (!(inv_cell > 0.f) || !(max_depth > 0.f) || !std::isfinite(inv_cell) || !std::isfinite(max_depth))
+    return fail(MRE_ERR_ARG, w + ": inv_cell and max_depth must be positive and finite");
+  if (!cam || !bounds) return fail(MRE_ERR_ARG, w + ": null cam or bounds");
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(bounds[k]) || !std::isfinite(bounds[3 + k]) || !(bounds[k] <= bounds[3 + k]))
+      return fail(MRE_ERR_ARG, w + ": bounds must be finite with lo <= hi");
+  if (!depth || !hmap) return fail(MRE_ERR_ARG, w + ": null depth or hmap");
+  if ((rgb == nullptr) != (cmap == nullptr)) return fail(MRE_ERR_ARG, w + ": rgb and cmap go together");
+  if ((seg == nullptr) != (smap == nullptr)) return fail(MRE_ERR_ARG, w + ": seg and smap go together");
+  if (((uintptr_t)depth & 3) || ((uintptr_t)hmap & 3) || ((uintptr_t)src & 3))
+    return fail(MRE_ERR_ARG, w + ": depth, hmap and src must be 4-byte aligned");
+  if (n == 0) return MRE_OK;
+  if (!is_device_ptr(depth) || !is_device_ptr(hmap) || (rgb && (!is_device_ptr(rgb) || !is_device_ptr(cmap))) ||
+      (seg && (!is_device_ptr(seg) || !is_device_ptr(smap))) || (src && !is_device_ptr(src)))
+    return fail(MRE_ERR_ARG, w + ": depth, rgb, seg, hmap, cmap, smap and src must be device pointers");
+  HeightmapArgs a;
+  memset(&a, 0, sizeof(a));
+  a.depth = depth; a.rgb = rgb; a.seg = seg; a.n = (uint32_t)n; a.h = (uint32_t)height; a.w = (uint32_t)width;
+  memcpy(a.g.cam, cam, sizeof(a.g.cam));
+  for (int k = 0; k < 3; k++) { a.g.lo[k] = bounds[k]; a.g.hi[k] = bounds[3 + k]; }
+  a.g.inv_cell = inv_cell; a.g.max_depth = max_depth; a.g.out_w = (float)out_w; a.g.out_h = (float)out_h;
+  a.cell = (float)(1.0 / (double)inv_cell);
+  // the inverse of A bounds the pixels a tile can take (the source rectangle); without one every tile scans the image
+  const double m[9] = {cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7], cam[8]};
+  const double co[9] = {m[4] * m[8] - m[5] * m[7], m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
+                        m[5] * m[6] - m[3] * m[8], m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
+                        m[3] * m[7] - m[4] * m[6], m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]};
+  const double det = m[0] * co[0] + m[1] * co[3] + m[2] * co[6];
+  double big = 0.0;
+  for (int k = 0; k < 9; k++) big = std::max(big, std::fabs(m[k]));
+  bool usable = std::isfinite(det) && std::fabs(det) > 1e-12 * big * big * big && std::isfinite(cam[9]) &&
+                std::isfinite(cam[10]) && std::isfinite(cam[11]);
+  for (int k = 0; k < 9; k++) {
+    a.inv[k] = (float)(co[k] / det);
+    usable = usable && std::isfinite(a.inv[k]);
+  }
+  a.whole_image = usable ? 0u : 1u;
+  a.out_h = (uint32_t)out_h; a.out_w = (uint32_t)out_w;
+  a.tiles_x = (a.out_w + HM_TILE - 1) / HM_TILE; a.tiles_y = (a.out_h + HM_TILE - 1) / HM_TILE;
+  a.hmap = hmap; a.cmap = cmap; a.smap = smap; a.src = src;
+  mre_launch_heightmap(&a, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
 }

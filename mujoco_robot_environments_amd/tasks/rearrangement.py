@@ -67,6 +67,11 @@ COLOURS = {"red": (1.0, 0.0, 0.0), "green": (0.0, 1.0, 0.0), "blue": (0.0, 0.0, 
            "yellow": (1.0, 1.0, 0.0), "cyan": (0.0, 1.0, 1.0), "magenta": (1.0, 0.0, 1.0)}
 COLOUR_NOISE = 0.1      # environment/props.py:274,290
 OVERHEAD = "overhead_camera/overhead_camera"
+# The box BatchedRearrangementEnv.heightmap covers by default, (lo, hi) in world metres: the reach of the arm over the
+# table, from 1 cm BELOW the table top to 29 cm above it -- 320 rows (y) x 240 columns (x) at the default cell of 2.5 mm.
+# This project's choice (the reference has no heightmap).  lo_z must sit below the table: the table's pixels come back
+# from depth a float32 rounding above or below TABLE_TOP_Z, and a lo_z equal to it would cut the plane out of the map.
+HEIGHTMAP_BOUNDS = ((0.2, -0.4, TABLE_TOP_Z - 0.01), (0.8, 0.4, TABLE_TOP_Z + 0.29))
 
 
 def mat2quat(mat3x3) -> np.ndarray:
@@ -217,6 +222,24 @@ class BatchedRearrangementEnv:
         return {"bbox": lab.box.contiguous().cpu().numpy(), "visible_pixels": lab.count.contiguous().cpu().numpy(),
                 "centroid": perception.centroid(lab).cpu().numpy(),
                 "nearest_depth": None if lab.zmin is None else lab.zmin.cpu().numpy()}
+
+    def heightmap(self, depth=None, rgb=None, seg=None, camera: str = OVERHEAD, bounds=None, cell: float = 0.0025):
+        """Top-down orthographic maps of every env, the inputs of a Transporter network: a ``perception.HeightMap`` of
+        CUDA tensors -- height above ``bounds``' lo_z [N, rows, columns], colour [N, rows, columns, 3], seg
+        [N, rows, columns] and the source pixel of every cell -- over ``bounds`` (default HEIGHTMAP_BOUNDS) at ``cell``
+        metres per cell, row along world y and column along world x (``perception.world_2_cell`` maps a pick or place
+        position to its cell).  The frames are the caller's (``depth`` [N, H, W] with optional ``rgb`` / ``seg``, as
+        ``render`` returns them, seen from ``camera``) or one ``render`` of the current state when ``depth`` is not
+        given; ``self`` is not touched when it is."""
+        import torch
+        if depth is None:
+            rgb, depth, seg = self.render(camera=camera)
+        depth = torch.as_tensor(depth)
+        cam = self._cameras[camera]
+        cam12 = perception.heightmap_camera(cam["pos"], cam["mat"], cam["fovy"], int(depth.shape[1]), int(depth.shape[2]))
+        return perception.heightmap(depth, None if rgb is None else torch.as_tensor(rgb).to(depth.device),
+                                    None if seg is None else torch.as_tensor(seg).to(depth.device), cam=cam12,
+                                    bounds=HEIGHTMAP_BOUNDS if bounds is None else bounds, cell=cell)
 
     def _compute_observation(self):
         if not self.render_observations:
