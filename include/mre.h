@@ -391,6 +391,36 @@ int mre_heightmap(void* stream, const float* depth, const uint8_t* rgb, const ui
                   const float* cam, const float* bounds, float inv_cell, float max_depth, int out_h, int out_w,
                   float* hmap, uint8_t* cmap, uint8_t* smap, int32_t* src);
 
+/* Warped and cropped maps on the device (csrc/mre_warp.hip): a nearest-neighbour affine gather of the
+ * maps of mre_heightmap (or any maps of that layout) -- the SE(2) perturbation and the rotated pick crops of a Transporter
+ * training sample are both calls of it.
+ *   hmap   device f32 [n][in_h][in_w], 4-byte aligned          cmap  device u8 [n][in_h][in_w][3] or NULL
+ *   smap   device u8  [n][in_h][in_w] or NULL
+ *   index  device i32 [samples]: the source map of sample s; NULL = s itself (then samples <= n)
+ *   mats   device f32 [samples][6]: M row-major (2 x 3), OUTPUT cell (column, row, 1) -> SOURCE cell (column, row)
+ * For sample s, output row r and column c, in float32 with every operation rounded on its own (no fused multiply-add):
+ *   a = M[0]*c;  b = M[1]*r;  x = a + b;  x = x + M[2];  x = x + 0.5f;  fx = floorf(x)
+ *   a = M[3]*c;  b = M[4]*r;  y = a + b;  y = y + M[5];  y = y + 0.5f;  fy = floorf(y)
+ *   valid  <=>  0 <= e < n  &&  fx >= 0  &&  fx < in_w  &&  fy >= 0  &&  fy < in_h      (e = index[s], or s)
+ * (fx, fy compared as floats, before any conversion: NaN, infinite or huge matrix entries are not valid; an index
+ * outside [0, n) makes the whole sample invalid).  A valid cell copies source cell (row (int)fy, column (int)fx) of map e:
+ *   out_h_  device f32 [samples][out_h][out_w]     its height            0.0f where not valid
+ *   out_c   device u8  [samples][out_h][out_w][3]  its colour            0, 0, 0       NULL if and only if cmap is NULL
+ *   out_s   device u8  [samples][out_h][out_w]     its label             255           NULL if and only if smap is NULL
+ *   from    device i32 [samples][out_h][out_w]     (int)fy * in_w + (int)fx   -1       or NULL
+ * Every element of every non-NULL output is written exactly once by the call and nothing else is; no byte outside the n
+ * maps, index and mats is read; the outputs are the same bits on every run.  A row of 4 cells is stored at once when
+ * out_w is a multiple of 4, out_h_ and from are 16-byte aligned and out_c and out_s 4-byte aligned; any other width or
+ * byte offset is stored element by element, with the same result.  Enqueued on `stream` (hipStream_t, NULL = the legacy
+ * default stream) of the current device; nothing synchronises.
+ * MRE_ERR_ARG, with nothing launched, unless n >= 0 and samples >= 0 (either 0: MRE_OK, nothing launched),
+ * 1 <= in_h, in_w, out_h, out_w <= 4096, hmap, mats and out_h_ non-NULL 4-byte-aligned device pointers, out_c NULL exactly
+ * when cmap is, out_s NULL exactly when smap is, index and from NULL or 4-byte-aligned device pointers, samples <= n when
+ * index is NULL, and no output byte range overlaps an input byte range (the maps, index, mats). */
+int mre_warp_maps(void* stream, const float* hmap, const uint8_t* cmap, const uint8_t* smap, int n, int in_h, int in_w,
+                  const int32_t* index, const float* mats, int samples, int out_h, int out_w,
+                  float* out_h_, uint8_t* out_c, uint8_t* out_s, int32_t* from);
+
 #define MRE_SOLVER_PGS 0
 #define MRE_SOLVER_NEWTON 2
 int mre_set_solver(mre_env*, int solver);

@@ -15,6 +15,7 @@
 #include "mre_env.h"
 #include "mre_labels.h"
 #include "mre_heightmap.h"
+#include "mre_warp.h"
 #include "mre_launch.h"
 #include "mre_model.h"
 #include "mre_records.h"
@@ -582,6 +583,55 @@ extern "C" int mre_heightmap(void* stream, const float* depth, const uint8_t* rg
   a.tiles_x = (a.out_w + HM_TILE - 1) / HM_TILE; a.tiles_y = (a.out_h + HM_TILE - 1) / HM_TILE;
   a.hmap = hmap; a.cmap = cmap; a.smap = smap; a.src = src;
   mre_launch_heightmap(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+// ---- warped and cropped maps on the device (csrc/mre_warp.hip): a nearest-neighbour affine gather of the three maps
+extern "C" int mre_warp_maps(void* stream, const float* hmap, const uint8_t* cmap, const uint8_t* smap, int n, int in_h,
+                             int in_w, const int32_t* index, const float* mats, int samples, int out_h, int out_w,
+                             float* out_h_, uint8_t* out_c, uint8_t* out_s, int32_t* from) {
+  const std::string w("mre_warp_maps");
+  const int lim = (int)WP_MAX_DIM;
+  if (n < 0 || samples < 0) return fail(MRE_ERR_ARG, w + ": n >= 0 and samples >= 0");
+  if (in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || in_h > lim || in_w > lim || out_h > lim || out_w > lim)
+    return fail(MRE_ERR_ARG, w + ": 1 <= in_h, in_w, out_h, out_w <= 4096");
+  if (!hmap || !mats || !out_h_) return fail(MRE_ERR_ARG, w + ": null hmap, mats or height output");
+  if ((cmap == nullptr) != (out_c == nullptr)) return fail(MRE_ERR_ARG, w + ": cmap and its output go together");
+  if ((smap == nullptr) != (out_s == nullptr)) return fail(MRE_ERR_ARG, w + ": smap and its output go together");
+  if (((uintptr_t)hmap & 3) || ((uintptr_t)mats & 3) || ((uintptr_t)out_h_ & 3) || ((uintptr_t)from & 3) ||
+      ((uintptr_t)index & 3))
+    return fail(MRE_ERR_ARG, w + ": hmap, mats, index, the height output and from must be 4-byte aligned");
+  if (!index && samples > n) return fail(MRE_ERR_ARG, w + ": more samples than maps and no index");
+  // no output byte range may overlap an input byte range (n, samples <= 2^31 and maps <= 2^24 cells: no overflow)
+  const size_t in_cells = (size_t)n * in_h * in_w, out_cells = (size_t)samples * out_h * out_w;
+  const std::pair<const void*, size_t> ins[5] = {{hmap, 4 * in_cells}, {cmap, 3 * in_cells}, {smap, in_cells},
+                                                 {index, 4 * (size_t)samples}, {mats, 24 * (size_t)samples}};
+  const std::pair<const void*, size_t> outs[4] = {{out_h_, 4 * out_cells}, {out_c, 3 * out_cells}, {out_s, out_cells},
+                                                  {from, 4 * out_cells}};
+  for (const auto& o : outs)
+    for (const auto& i : ins) {
+      if (!o.first || !i.first || !o.second || !i.second) continue;
+      const uintptr_t o0 = (uintptr_t)o.first, i0 = (uintptr_t)i.first;
+      if (o0 < i0 + i.second && i0 < o0 + o.second)
+        return fail(MRE_ERR_ARG, w + ": an output overlaps an input");
+    }
+  if (n == 0 || samples == 0) return MRE_OK;
+  if (!is_device_ptr(hmap) || !is_device_ptr(mats) || !is_device_ptr(out_h_) || (index && !is_device_ptr(index)) ||
+      (cmap && (!is_device_ptr(cmap) || !is_device_ptr(out_c))) ||
+      (smap && (!is_device_ptr(smap) || !is_device_ptr(out_s))) || (from && !is_device_ptr(from)))
+    return fail(MRE_ERR_ARG, w + ": the maps, index, mats and the outputs must be device pointers");
+  WarpArgs a;
+  memset(&a, 0, sizeof(a));
+  a.hmap = hmap; a.cmap = cmap; a.smap = smap; a.index = index; a.mats = mats;
+  a.n = (uint32_t)n; a.in_h = (uint32_t)in_h; a.in_w = (uint32_t)in_w;
+  a.samples = (uint32_t)samples; a.out_h = (uint32_t)out_h; a.out_w = (uint32_t)out_w;
+  a.tiles_x = (a.out_w + WP_TILE_W - 1) / WP_TILE_W; a.tiles_y = (a.out_h + WP_TILE_H - 1) / WP_TILE_H;
+  // the wide stores: 4 cells of a row at once need the width a multiple of 4 and bases aligned to what a lane stores
+  a.vec = (out_w % 4 == 0 && !((uintptr_t)out_h_ & 15) && !((uintptr_t)from & 15) && !((uintptr_t)out_c & 3) &&
+           !((uintptr_t)out_s & 3)) ? 1u : 0u;
+  a.out_h_ = out_h_; a.out_c = out_c; a.out_s = out_s; a.from = from;
+  mre_launch_warp_maps(&a, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
 }

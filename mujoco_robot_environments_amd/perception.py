@@ -1,5 +1,6 @@
 """Frame labels and training inputs from the camera's images: the torch-facing wrappers of ``mre_seg_labels``
-(include/mre.h, csrc/mre_labels.hip) and ``mre_heightmap`` (csrc/mre_heightmap.hip).
+(include/mre.h, csrc/mre_labels.hip), ``mre_heightmap`` (csrc/mre_heightmap.hip) and ``mre_warp_maps``
+(csrc/mre_warp.hip).
 
 ``seg_labels``: for every env and every label of a small id range of a segmentation image it gives what the
 reference's ``props_info`` takes from one (``get_bbox``, tasks/rearrangement.py:254-268: the PASCAL-VOC box of the
@@ -10,6 +11,11 @@ of their coordinates (the centroid) and the smallest depth among them.  ``Batche
 ``heightmap``: the top-down orthographic height, colour and label maps a Transporter network is trained on, from the
 depth / rgb / seg frames of every env (``BatchedRearrangementEnv.heightmap``); ``world_2_cell`` puts pick and place
 points into the same map.
+
+``warp_maps``: a nearest-neighbour affine gather of those maps, and on it what a Transporter learner does to every
+sample: a random SE(2) perturbation of the map with its pick and place cells (``sample_perturbation``) and the rotated
+crops around the pick cell (``crop_matrices``), together ``transporter_sample``
+(``BatchedRearrangementEnv.transporter_sample``).
 
 The kernels are enqueued on torch's current stream; nothing here synchronises.
 """
@@ -23,6 +29,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from . import rng
 
 PROP_GEOM_ID0 = 12   # geom ids of prop_0..3 in the compiled scene (tasks/rearrangement.py)
 MAX_IDS = 8          # labels of one mre_seg_labels call
@@ -254,3 +261,270 @@ def world_2_cell(points, bounds, cell: float):
     cx, cy = _cells(p[..., 0], p[..., 1], lo, inv_cell)
     out = torch.stack([cx, cy], dim=-1).to(torch.int64)
     return out if is_tensor else out.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------- warped and cropped maps
+# height float32 [S, out_h, out_w] (0 where the source cell does not exist), colour uint8 [S, out_h, out_w, 3] (0) or None,
+# seg uint8 [S, out_h, out_w] (255) or None, source int32 [S, out_h, out_w]: row * in_w + column of the source cell inside
+# its map, -1 where it does not exist, or None
+WarpedMaps = collections.namedtuple("WarpedMaps", ["height", "colour", "seg", "source"])
+# F float64 [N, 2, 3] (source cell -> perturbed cell), M float32 [N, 6] (its inverse: the mats of warp_maps), cells int64
+# [N, K, 2] (the label cells moved by F), tries int64 [N] (the accepted attempt, from 1; -1: none, identity)
+Perturbation = collections.namedtuple("Perturbation", ["F", "M", "cells", "tries"])
+# maps: the perturbed WarpedMaps [N, rows, columns]; pick, place int64 [N, 2] (column, row) in them; crops: WarpedMaps of
+# leading shape [N, n_rotations]; tries as in Perturbation
+TransporterSample = collections.namedtuple("TransporterSample", ["maps", "pick", "place", "crops", "tries"])
+
+
+def _affine(a, b, tx, c, d, ty) -> np.ndarray:
+    """[[a, b, tx], [c, d, ty]] of broadcastable float64 arrays: [..., 2, 3]."""
+    a, b, tx, c, d, ty = np.broadcast_arrays(a, b, tx, c, d, ty)
+    return np.stack([np.stack([a, b, tx], axis=-1), np.stack([c, d, ty], axis=-1)], axis=-2)
+
+
+def se2_forward(theta, shift, pivot) -> np.ndarray:
+    """F = T(pivot + shift) R(theta) T(-pivot) in (column, row) cell coordinates, R = [[cos, -sin], [sin, cos]]: the
+    rigid motion that turns a map by ``theta`` about ``pivot`` [..., 2] and then moves it by ``shift`` [..., 2].
+    float64 [..., 2, 3]; element-wise arithmetic only, so a row does not depend on what else is in the batch."""
+    theta = np.asarray(theta, np.float64)
+    shift, pivot = np.asarray(shift, np.float64), np.asarray(pivot, np.float64)
+    cos, sin = np.cos(theta), np.sin(theta)
+    px, py = pivot[..., 0], pivot[..., 1]
+    tx = px + shift[..., 0] - (cos * px - sin * py)
+    ty = py + shift[..., 1] - (sin * px + cos * py)
+    return _affine(cos, -sin, tx, sin, cos, ty)
+
+
+def invert_affine(F) -> np.ndarray:
+    """The inverse of affine maps ``F`` [..., 2, 3], float64 [..., 2, 3]: for a forward motion F (source -> output) it
+    is the M of ``warp_maps`` (output -> source)."""
+    F = np.asarray(F, np.float64)
+    a, b, tx, c, d, ty = F[..., 0, 0], F[..., 0, 1], F[..., 0, 2], F[..., 1, 0], F[..., 1, 1], F[..., 1, 2]
+    det = a * d - b * c
+    ia, ib, ic, id_ = d / det, -b / det, -c / det, a / det
+    return _affine(ia, ib, -(ia * tx + ib * ty), ic, id_, -(ic * tx + id_ * ty))
+
+
+def affine_mats(M) -> np.ndarray:
+    """Affine maps [..., 2, 3] as the float32 [S, 6] rows ``warp_maps`` takes: rounded to float32 once."""
+    return np.ascontiguousarray(np.asarray(M, np.float64).reshape(-1, 6).astype(np.float32))
+
+
+def transform_cells(F, cells) -> np.ndarray:
+    """floor(F p + 0.5) for cells p = (column, row): int64.  ``F`` [..., 2, 3]; ``cells`` [..., 2], one cell per map, or
+    [..., K, 2], K cells per map."""
+    F, p = np.asarray(F, np.float64), np.asarray(cells, np.float64)
+    single = p.ndim == F.ndim - 1
+    if not single:
+        F = F[..., None, :, :]
+    x = F[..., 0, 0] * p[..., 0] + F[..., 0, 1] * p[..., 1] + F[..., 0, 2]
+    y = F[..., 1, 0] * p[..., 0] + F[..., 1, 1] * p[..., 1] + F[..., 1, 2]
+    return np.floor(np.stack([x, y], axis=-1) + 0.5).astype(np.int64)
+
+
+def _quarter_exact(k: int, n: int):
+    """cos and sin of 2 pi k / n, exactly 0 and +-1 at the quarter turns."""
+    if (4 * k) % n == 0:
+        q = (4 * k // n) % 4
+        return (1.0, 0.0, -1.0, 0.0)[q], (0.0, 1.0, 0.0, -1.0)[q]
+    a = 2.0 * np.pi * k / n
+    return float(np.cos(a)), float(np.sin(a))
+
+
+def crop_matrices(cells, n_rotations: int = 36, crop: int = 64):
+    """The ``mats`` float32 [N * n_rotations, 6] and ``index`` int32 [N * n_rotations] of the rotated crops around the
+    pivots ``cells`` [N, 2] (column, row): sample i * n_rotations + k is the crop x crop window centred on pivot i and
+    turned by 2 pi k / n_rotations, M = T(p) R(2 pi k / n_rotations) T(-crop / 2, -crop / 2), read from map i.  At k = 0
+    the entries are exactly 1, 0 and integers (crop even): the crop is the slice [p - crop / 2, p + crop / 2) of the
+    zero-padded map.  Formed in float64 and rounded to float32 once."""
+    p = np.asarray(cells, np.float64).reshape(-1, 2)
+    if n_rotations < 1 or crop < 1:
+        raise ValueError("n_rotations and crop must be at least 1")
+    M = np.empty((len(p), n_rotations, 2, 3), np.float64)
+    half = np.array([crop / 2.0, crop / 2.0])
+    for k in range(n_rotations):
+        cos, sin = _quarter_exact(k, n_rotations)
+        R = np.array([[cos, -sin], [sin, cos]])
+        M[:, k, :, :2] = R
+        M[:, k, :, 2] = p - R @ half
+    index = np.repeat(np.arange(len(p), dtype=np.int32), n_rotations)
+    return affine_mats(M), index
+
+
+def _warp_args(height, colour, seg, mats, index, out_shape):
+    """The checked arguments of warp_maps / warp_maps_reference: (n, in_h, in_w, samples, out_h, out_w)."""
+    if height.dim() != 3:
+        raise ValueError("height must be [N, H, W]")
+    if colour is not None and tuple(colour.shape) != tuple(height.shape) + (3,):
+        raise ValueError("colour must be [N, H, W, 3]")
+    if seg is not None and tuple(seg.shape) != tuple(height.shape):
+        raise ValueError("seg must have height's shape")
+    n, in_h, in_w = (int(x) for x in height.shape)
+    if mats.dim() != 2 or mats.shape[1] != 6:
+        raise ValueError("mats must be [S, 6] or [S, 2, 3]")
+    samples = int(mats.shape[0])
+    if index is None:
+        if samples > n:
+            raise ValueError("more samples than maps: give index, the source map of every sample")
+    elif index.dim() != 1 or int(index.shape[0]) != samples:
+        raise ValueError("index must be [S], one source map per row of mats")
+    out_h, out_w = (in_h, in_w) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
+    if not all(1 <= x <= MAX_MAP for x in (in_h, in_w, out_h, out_w)):
+        raise ValueError(f"maps have between 1 and {MAX_MAP} rows and columns")
+    return n, in_h, in_w, samples, out_h, out_w
+
+
+def _as_mats(mats, dev):
+    if isinstance(mats, torch.Tensor):
+        m = mats.to(device=dev, dtype=torch.float32)
+    else:
+        m = torch.from_numpy(np.ascontiguousarray(np.asarray(mats, np.float32))).to(dev)
+    return m.reshape(-1, 6).contiguous() if m.dim() == 3 and tuple(m.shape[1:]) == (2, 3) else m.contiguous()
+
+
+def _as_index(index, dev):
+    if index is None:
+        return None
+    if isinstance(index, torch.Tensor):
+        return index.to(device=dev, dtype=torch.int32).contiguous()
+    i = np.asarray(index)
+    if i.size and (i.min() < -2 ** 31 or i.max() > 2 ** 31 - 1):
+        raise ValueError("index must hold int32 values")
+    return torch.from_numpy(np.ascontiguousarray(i.astype(np.int32))).to(dev)
+
+
+def warp_maps_reference(height: torch.Tensor, colour: Optional[torch.Tensor] = None, seg: Optional[torch.Tensor] = None, *,
+                        mats, index=None, out_shape=None, with_source: bool = True) -> WarpedMaps:
+    """The statement of ``warp_maps`` (include/mre.h, mre_warp_maps) in plain torch, float32 operation by operation, on
+    whatever device ``height`` is on and for any strides: the fallback of ``warp_maps`` and, on the CPU, bit for bit
+    what the kernel computes.  It materialises int64 index images (in slices of about 2^24 cells); use it for small
+    batches and tests."""
+    dev = height.device
+    mats, index = _as_mats(mats, dev), _as_index(index, dev)
+    n, in_h, in_w, samples, out_h, out_w = _warp_args(height, colour, seg, mats, index, out_shape)
+    hw = in_h * in_w
+    c = torch.arange(out_w, dtype=torch.float32, device=dev).view(1, 1, out_w)
+    r = torch.arange(out_h, dtype=torch.float32, device=dev).view(1, out_h, 1)
+    e_all = torch.arange(samples, dtype=torch.int64, device=dev) if index is None else index.to(torch.int64)
+    out_hz = torch.empty((samples, out_h, out_w), dtype=torch.float32, device=dev)
+    out_c = None if colour is None else torch.empty((samples, out_h, out_w, 3), dtype=colour.dtype, device=dev)
+    out_s = None if seg is None else torch.empty((samples, out_h, out_w), dtype=seg.dtype, device=dev)
+    source = torch.empty((samples, out_h, out_w), dtype=torch.int32, device=dev) if with_source else None
+    if n == 0 or samples == 0:
+        return WarpedMaps(out_hz, out_c, out_s, source)
+    flat_h = height.to(torch.float32).reshape(-1)
+    flat_c = None if colour is None else colour.reshape(-1, 3)
+    flat_s = None if seg is None else seg.reshape(-1)
+    step = max(1, (1 << 24) // (out_h * out_w))
+    for s0 in range(0, samples, step):
+        m = mats[s0:s0 + step]
+        e = e_all[s0:s0 + step].view(-1, 1, 1)
+        k = [m[:, j].view(-1, 1, 1) for j in range(6)]
+        a = k[0] * c
+        b = k[1] * r
+        x = a + b
+        x = x + k[2]
+        x = x + 0.5
+        fx = torch.floor(x)
+        a = k[3] * c
+        b = k[4] * r
+        y = a + b
+        y = y + k[5]
+        y = y + 0.5
+        fy = torch.floor(y)
+        valid = (e >= 0) & (e < n) & (fx >= 0) & (fx < in_w) & (fy >= 0) & (fy < in_h)
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        src = torch.where(valid, fy, zero).to(torch.int64) * in_w + torch.where(valid, fx, zero).to(torch.int64)
+        where = torch.where(valid, e, 0) * hw + src
+        out_hz[s0:s0 + step] = torch.where(valid, flat_h[where], zero)
+        if out_c is not None:
+            out_c[s0:s0 + step] = torch.where(valid[..., None], flat_c[where], 0).to(colour.dtype)
+        if out_s is not None:
+            out_s[s0:s0 + step] = torch.where(valid, flat_s[where], 255).to(seg.dtype)
+        if source is not None:
+            source[s0:s0 + step] = torch.where(valid, src, -1).to(torch.int32)
+    return WarpedMaps(out_hz, out_c, out_s, source)
+
+
+def warp_maps(height: torch.Tensor, colour: Optional[torch.Tensor] = None, seg: Optional[torch.Tensor] = None, *,
+              mats, index=None, out_shape=None, with_source: bool = True) -> WarpedMaps:
+    """A nearest-neighbour affine gather of the maps ``height`` [N, H, W] (and ``colour`` [N, H, W, 3], ``seg``
+    [N, H, W]): output cell (row r, column c) of sample s takes the cell ``mats[s]`` (float32 [S, 6] or [S, 2, 3], OUTPUT
+    cell -> SOURCE cell, numpy or tensor) sends it to, rounded to the nearest, in map ``index[s]`` (int32 [S]; None: map
+    s, then S <= N) -- or 0 / (0, 0, 0) / 255 / source -1 where that cell or map does not exist.  See ``WarpedMaps`` and
+    include/mre.h for the exact statement; ``out_shape`` = (rows, columns) defaults to the input's.  ``se2_forward`` /
+    ``invert_affine`` / ``crop_matrices`` build the matrices.  Contiguous CUDA float32 height with uint8 colour / seg is
+    one launch of ``mre_warp_maps`` on torch's current stream, without a synchronise; anything else is computed by
+    ``warp_maps_reference`` with the same return values."""
+    dev = height.device
+    on_device = height.is_cuda and height.dtype == torch.float32 and height.is_contiguous() and all(
+        x is None or (x.device == dev and x.dtype == torch.uint8 and x.is_contiguous()) for x in (colour, seg))
+    if not on_device:
+        return warp_maps_reference(height, colour, seg, mats=mats, index=index, out_shape=out_shape,
+                                   with_source=with_source)
+    mats, index = _as_mats(mats, dev), _as_index(index, dev)
+    n, in_h, in_w, samples, out_h, out_w = _warp_args(height, colour, seg, mats, index, out_shape)
+    out_hz = torch.empty((samples, out_h, out_w), dtype=torch.float32, device=dev)
+    out_c = None if colour is None else torch.empty((samples, out_h, out_w, 3), dtype=torch.uint8, device=dev)
+    out_s = None if seg is None else torch.empty((samples, out_h, out_w), dtype=torch.uint8, device=dev)
+    source = torch.empty((samples, out_h, out_w), dtype=torch.int32, device=dev) if with_source else None
+    if n and samples:
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(_lib.lib().mre_warp_maps(stream, height.data_ptr(), ptr(colour), ptr(seg), n, in_h, in_w, ptr(index),
+                                                mats.data_ptr(), samples, out_h, out_w, out_hz.data_ptr(), ptr(out_c),
+                                                ptr(out_s), ptr(source)), "mre_warp_maps")
+    return WarpedMaps(out_hz, out_c, out_s, source)
+
+
+def sample_perturbation(seed: int, env_ids, draw: int, cells, shape, max_theta: float = np.pi, max_shift=None,
+                        max_tries: int = 16) -> Perturbation:
+    """A random rigid motion of the map of every env that keeps the env's label cells inside it: see ``Perturbation``.
+    ``cells`` int [N, K, 2] (column, row) are the label cells (pick, place), ``shape`` = (rows, columns) the map.  Attempt
+    a = 0 .. max_tries - 1 of an env draws u = rng.uniform(seed, env id, draw * max_tries + a, 3): theta =
+    (2 u0 - 1) max_theta about the map's centre ((columns - 1) / 2, (rows - 1) / 2), shift = (2 u1 - 1, 2 u2 - 1)
+    max_shift cells (default: a quarter of the smaller side); the first attempt whose moved cells are all inside the map
+    is taken.  A pure function of (seed, global env id, draw): the same whatever the order or the sharding of the envs.
+    An env without an accepted attempt gets the identity and tries = -1.  The distribution is this project's choice."""
+    ids = np.asarray(env_ids, np.int64).reshape(-1)
+    n = len(ids)
+    cells = np.asarray(cells, np.int64).reshape(n, -1, 2)
+    rows, cols = int(shape[0]), int(shape[1])
+    max_shift = min(rows, cols) / 4.0 if max_shift is None else float(max_shift)
+    pivot = np.array([(cols - 1) / 2.0, (rows - 1) / 2.0])
+    F = np.broadcast_to(np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), (n, 2, 3)).copy()
+    moved, tries = cells.copy(), np.full(n, -1, np.int64)
+    pending = np.arange(n)
+    for attempt in range(int(max_tries)):
+        if not len(pending):
+            break
+        u = rng.uniform(seed, ids[pending], [int(draw) * int(max_tries) + attempt], 3)[0]
+        Fa = se2_forward((2.0 * u[:, 0] - 1.0) * float(max_theta), (2.0 * u[:, 1:3] - 1.0) * max_shift, pivot)
+        q = transform_cells(Fa, cells[pending])
+        ok = ((q[..., 0] >= 0) & (q[..., 0] < cols) & (q[..., 1] >= 0) & (q[..., 1] < rows)).all(axis=1)
+        took = pending[ok]
+        F[took], moved[took], tries[took] = Fa[ok], q[ok], attempt + 1
+        pending = pending[~ok]
+    return Perturbation(F, affine_mats(invert_affine(F)), moved, tries)
+
+
+def transporter_sample(maps, pick_cells, place_cells, *, seed: int, env_ids, draw: int, n_rotations: int = 36,
+                       crop: int = 64) -> TransporterSample:
+    """One Transporter training sample per env from its ``maps`` (a ``HeightMap`` / ``WarpedMaps``, or (height, colour,
+    seg)): the maps under ``sample_perturbation(seed, env_ids, draw)`` of the pick and place cells ([N, 2] (column,
+    row)), both cells moved with them, and ``n_rotations`` crops of ``crop`` x ``crop`` cells of the perturbed maps around
+    the moved pick cell, crop k turned by 2 pi k / n_rotations (``crop_matrices``): see ``TransporterSample``.  Two
+    launches of ``mre_warp_maps`` for CUDA maps."""
+    height, colour, seg = maps[0], maps[1], maps[2]
+    to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    cells = np.stack([to_np(pick_cells), to_np(place_cells)], axis=1).astype(np.int64)
+    n = int(height.shape[0])
+    if cells.shape != (n, 2, 2):
+        raise ValueError("pick_cells and place_cells must be [N, 2]")
+    pert = sample_perturbation(seed, env_ids, draw, cells, tuple(height.shape[1:3]))
+    warped = warp_maps(height, colour, seg, mats=pert.M)
+    mats, index = crop_matrices(pert.cells[:, 0], n_rotations, crop)
+    flat = warp_maps(warped.height, warped.colour, warped.seg, mats=mats, index=index, out_shape=(crop, crop))
+    crops = WarpedMaps(*[None if x is None else x.view((n, n_rotations) + tuple(x.shape[1:])) for x in flat])
+    return TransporterSample(warped, pert.cells[:, 0], pert.cells[:, 1], crops, pert.tries)

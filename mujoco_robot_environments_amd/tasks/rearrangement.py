@@ -241,6 +241,21 @@ class BatchedRearrangementEnv:
                                     None if seg is None else torch.as_tensor(seg).to(depth.device), cam=cam12,
                                     bounds=HEIGHTMAP_BOUNDS if bounds is None else bounds, cell=cell)
 
+    def transporter_sample(self, seed: int, draw: int = 0, depth=None, rgb=None, seg=None, cell: float = 0.0025,
+                           n_rotations: int = 36, crop: int = 64, camera: str = OVERHEAD):
+        """One Transporter training sample per env on the device, a ``perception.TransporterSample``: the maps of
+        ``heightmap(depth, rgb, seg, cell=cell)`` under a random rigid motion keyed by (``seed``, global env id, ``draw``),
+        the pick and place cells of ``sort_colours(peek=True)`` moved with them, and ``n_rotations`` rotated crops of
+        ``crop`` x ``crop`` cells around the moved pick cell.  An env with nothing left to move has its home pose as
+        both cells; ``tries`` is -1 (and the maps unperturbed) where no motion kept both cells inside the map.  No state
+        of the env changes: no place draw is consumed."""
+        maps = self.heightmap(depth, rgb, seg, camera=camera, cell=cell)
+        _, pick, place = self.sort_colours(peek=True)
+        return perception.transporter_sample(
+            maps, perception.world_2_cell(pick[:, :3], HEIGHTMAP_BOUNDS, cell),
+            perception.world_2_cell(place[:, :3], HEIGHTMAP_BOUNDS, cell), seed=seed, env_ids=self.env_ids, draw=draw,
+            n_rotations=n_rotations, crop=crop)
+
     def _compute_observation(self):
         if not self.render_observations:
             return self._zeros_obs()
