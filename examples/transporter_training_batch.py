@@ -7,6 +7,11 @@ perturbed by a random rigid motion with their pick and place cells, and the rota
 Renders the envs after reset(), builds the maps and takes one sample per env.  Prints the shapes, the attempts the
 perturbation took, and for the first --show envs that have a cube to move: the pick cell before and after the motion with
 the label the maps hold there, and the memory of the batch.
+
+    python examples/transporter_training_batch.py --num-envs 64 --inputs
+also takes the same batch as the tensors a network consumes (BatchedRearrangementEnv.transporter_batch ->
+perception.warp_inputs -> csrc/mre_warp_inputs.hip): channels-first, normalised, bfloat16.  Prints their shapes, dtypes and
+the smallest and largest value of every channel, and feeds the scene through one torch.nn.Conv2d: nothing else is needed.
 """
 import argparse
 import os
@@ -30,6 +35,7 @@ def main():
     ap.add_argument("--rotations", type=int, default=36)
     ap.add_argument("--crop", type=int, default=64)
     ap.add_argument("--show", type=int, default=8, help="envs whose pick cells are printed")
+    ap.add_argument("--inputs", action="store_true", help="also take the batch as network-ready tensors and run a convolution on it")
     args = ap.parse_args()
     env = BatchedRearrangementEnv(cfg=colour_separator_task_config(), num_envs=args.num_envs, render=True)
     env.reset()
@@ -60,7 +66,27 @@ def main():
     tensors = [t for m in (s.maps, s.crops) for t in m if t is not None]
     print(f"one batch: {sum(t.numel() * t.element_size() for t in tensors) / 2 ** 20:.1f} MiB on {tensors[0].device} "
           f"({sum(t.numel() * t.element_size() for t in s.crops if t is not None) / 2 ** 20:.1f} MiB of it crops)")
+    if args.inputs:
+        show_inputs(env, args, depth, rgb, seg, s)
     env.close()
+
+
+def show_inputs(env, args, depth, rgb, seg, sample):
+    import torch
+    b = env.transporter_batch(args.seed, args.draw, depth, rgb, seg, cell=args.cell, n_rotations=args.rotations, crop=args.crop,
+                              channels=perception.CHANNELS_RGBHHH)
+    assert np.array_equal(b.pick, sample.pick) and np.array_equal(b.tries, sample.tries)   # the motion of the sample above
+    print(f"network inputs: scene {tuple(b.scene.shape)} {b.scene.dtype}, crops {tuple(b.crops.shape)} {b.crops.dtype} on "
+          f"{b.scene.device}; pick_index {b.pick_index.shape} {b.pick_index.dtype}, rotation_index all {int(b.rotation_index.max())}")
+    names = ["red", "green", "blue", "height"]
+    for k, src in enumerate(perception.CHANNELS_RGBHHH.sources):
+        sc, cr = b.scene[:, k].float(), b.crops[:, :, k].float()
+        print(f"  channel {k} ({names[src]:6s}): scene {float(sc.min()):.4f} .. {float(sc.max()):.4f}, "
+              f"crops {float(cr.min()):.4f} .. {float(cr.max()):.4f}")
+    conv = torch.nn.Conv2d(b.scene.shape[1], 8, 3).to(device=b.scene.device, dtype=b.scene.dtype)
+    with torch.no_grad():
+        y = conv(b.scene)
+    print(f"Conv2d({b.scene.shape[1]}, 8, 3)(scene) -> {tuple(y.shape)} {y.dtype}, finite: {bool(torch.isfinite(y).all())}")
 
 
 if __name__ == "__main__":

@@ -421,6 +421,44 @@ int mre_warp_maps(void* stream, const float* hmap, const uint8_t* cmap, const ui
                   const int32_t* index, const float* mats, int samples, int out_h, int out_w,
                   float* out_h_, uint8_t* out_c, uint8_t* out_s, int32_t* from);
 
+/* Network-ready inputs on the device (csrc/mre_warp_inputs.hip): the gather of mre_warp_maps written as
+ * the tensor a convolution consumes -- planar, normalised per channel, float32 or bfloat16 -- in one launch.
+ * hmap, cmap (may be NULL), n, in_h, in_w, index, mats, samples, out_h, out_w are those of mre_warp_maps: the same device
+ * pointers and alignment, the same source cell (fx, fy) and the same `valid`, NaN or huge matrix entries and an index
+ * outside [0, n) included.
+ *   channels    1 .. 8 channels of the output
+ *   chan_src    HOST i32 [channels]: what channel k holds, MRE_SRC_RED / _GREEN / _BLUE / _HEIGHT; sources may repeat and
+ *               come in any order (a colour source needs cmap)
+ *   chan_scale, chan_bias   HOST f32 [channels], finite
+ *   dtype       MRE_F32 or MRE_BF16
+ *   out         device [samples][channels][out_h][out_w] of that type, aligned to its element size
+ * The raw value v of a valid cell is the source cell's colour byte converted to float (exact) or its height; of any other
+ * cell 0.0f, in every channel -- the values mre_warp_maps writes.  Channel k of the cell is, in float32 with both
+ * operations rounded on their own (no fused multiply-add):
+ *   t = v * chan_scale[k];   t = t + chan_bias[k]
+ * MRE_F32 stores t.  MRE_BF16 stores t rounded to bfloat16, nearest and ties to even, on the bits: for a non-NaN t with
+ * bits b the upper half of  b + 0x7FFF + ((b >> 16) & 1)  (an overflow rounds to +-inf); a NaN t (from a NaN or infinite
+ * height only) stores some bfloat16 NaN.
+ * Every element of out is written exactly once by the call and nothing else is; no byte outside the n maps, index and mats
+ * is read; out is the same bits on every run.  A lane's 4 cells of a channel are stored at once (16 B, or 8 B of bfloat16)
+ * when out_w is a multiple of 4 and out is aligned to that; any other width or offset is stored element by element, with
+ * the same result.  Enqueued on `stream` of the current device; nothing synchronises.
+ * MRE_ERR_ARG, with nothing launched, unless the conditions of mre_warp_maps on the shared arguments hold (n == 0 or
+ * samples == 0: MRE_OK, nothing launched), 1 <= channels <= 8, the three channel arrays are non-NULL, every chan_src is one
+ * of the four codes, cmap is non-NULL when a colour source is named, every chan_scale and chan_bias is finite (0 * inf
+ * would make the sign and payload of a NaN part of the statement), dtype is one of the two codes, out is a non-NULL device
+ * pointer aligned to its element size and its byte range overlaps no input byte range (the maps, index, mats). */
+#define MRE_SRC_RED 0
+#define MRE_SRC_GREEN 1
+#define MRE_SRC_BLUE 2
+#define MRE_SRC_HEIGHT 3
+#define MRE_F32 0
+#define MRE_BF16 1
+int mre_warp_inputs(void* stream, const float* hmap, const uint8_t* cmap, int n, int in_h, int in_w,
+                    const int32_t* index, const float* mats, int samples, int out_h, int out_w,
+                    int channels, const int32_t* chan_src, const float* chan_scale, const float* chan_bias,
+                    int dtype, void* out);
+
 #define MRE_SOLVER_PGS 0
 #define MRE_SOLVER_NEWTON 2
 int mre_set_solver(mre_env*, int solver);

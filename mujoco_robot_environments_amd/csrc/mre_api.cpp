@@ -16,6 +16,7 @@
 #include "mre_labels.h"
 #include "mre_heightmap.h"
 #include "mre_warp.h"
+#include "mre_warp_inputs.h"
 #include "mre_launch.h"
 #include "mre_model.h"
 #include "mre_records.h"
@@ -632,6 +633,67 @@ extern "C" int mre_warp_maps(void* stream, const float* hmap, const uint8_t* cma
            !((uintptr_t)out_s & 3)) ? 1u : 0u;
   a.out_h_ = out_h_; a.out_c = out_c; a.out_s = out_s; a.from = from;
   mre_launch_warp_maps(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+// ---- network-ready inputs on the device (csrc/mre_warp_inputs.hip): the same gather, written planar and normalised
+extern "C" int mre_warp_inputs(void* stream, const float* hmap, const uint8_t* cmap, int n, int in_h, int in_w,
+                               const int32_t* index, const float* mats, int samples, int out_h, int out_w, int channels,
+                               const int32_t* chan_src, const float* chan_scale, const float* chan_bias, int dtype,
+                               void* out) {
+  const std::string w("mre_warp_inputs");
+  const int lim = (int)WP_MAX_DIM;
+  if (n < 0 || samples < 0) return fail(MRE_ERR_ARG, w + ": n >= 0 and samples >= 0");
+  if (in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || in_h > lim || in_w > lim || out_h > lim || out_w > lim)
+    return fail(MRE_ERR_ARG, w + ": 1 <= in_h, in_w, out_h, out_w <= 4096");
+  if (!hmap || !mats || !out) return fail(MRE_ERR_ARG, w + ": null hmap, mats or out");
+  if (((uintptr_t)hmap & 3) || ((uintptr_t)mats & 3) || ((uintptr_t)index & 3))
+    return fail(MRE_ERR_ARG, w + ": hmap, mats and index must be 4-byte aligned");
+  if (!index && samples > n) return fail(MRE_ERR_ARG, w + ": more samples than maps and no index");
+  if (channels < 1 || channels > WI_MAX_CHANNELS) return fail(MRE_ERR_ARG, w + ": 1 <= channels <= 8");
+  if (!chan_src || !chan_scale || !chan_bias) return fail(MRE_ERR_ARG, w + ": null chan_src, chan_scale or chan_bias");
+  bool colour = false;
+  for (int k = 0; k < channels; k++) {
+    if (chan_src[k] < MRE_SRC_RED || chan_src[k] > MRE_SRC_HEIGHT)
+      return fail(MRE_ERR_ARG, w + ": chan_src must be 0 (red), 1 (green), 2 (blue) or 3 (height)");
+    colour = colour || chan_src[k] != MRE_SRC_HEIGHT;
+    if (!std::isfinite(chan_scale[k]) || !std::isfinite(chan_bias[k]))
+      return fail(MRE_ERR_ARG, w + ": chan_scale and chan_bias must be finite");
+  }
+  if (colour && !cmap) return fail(MRE_ERR_ARG, w + ": a colour source needs cmap");
+  if (dtype != MRE_F32 && dtype != MRE_BF16) return fail(MRE_ERR_ARG, w + ": dtype must be MRE_F32 or MRE_BF16");
+  const size_t esize = dtype == MRE_BF16 ? 2 : 4;
+  if ((uintptr_t)out & (esize - 1)) return fail(MRE_ERR_ARG, w + ": out must be aligned to its element size");
+  // out may overlap no input byte range (samples <= 2^31, 8 channels, maps <= 2^24 cells, 4 B: below 2^60)
+  const size_t in_cells = (size_t)n * in_h * in_w;
+  const size_t out_bytes = (size_t)samples * channels * out_h * out_w * esize;
+  const std::pair<const void*, size_t> ins[4] = {{hmap, 4 * in_cells}, {cmap, 3 * in_cells},
+                                                 {index, 4 * (size_t)samples}, {mats, 24 * (size_t)samples}};
+  for (const auto& i : ins) {
+    if (!i.first || !i.second || !out_bytes) continue;
+    const uintptr_t o0 = (uintptr_t)out, i0 = (uintptr_t)i.first;
+    if (o0 < i0 + i.second && i0 < o0 + out_bytes) return fail(MRE_ERR_ARG, w + ": out overlaps an input");
+  }
+  if (n == 0 || samples == 0) return MRE_OK;
+  if (!is_device_ptr(hmap) || !is_device_ptr(mats) || !is_device_ptr(out) || (index && !is_device_ptr(index)) ||
+      (colour && !is_device_ptr(cmap)))
+    return fail(MRE_ERR_ARG, w + ": the maps, index, mats and out must be device pointers");
+  WarpInputArgs a;
+  memset(&a, 0, sizeof(a));
+  a.hmap = hmap; a.cmap = colour ? cmap : nullptr; a.index = index; a.mats = mats;
+  a.n = (uint32_t)n; a.in_h = (uint32_t)in_h; a.in_w = (uint32_t)in_w;
+  a.samples = (uint32_t)samples; a.out_h = (uint32_t)out_h; a.out_w = (uint32_t)out_w;
+  a.tiles_x = (a.out_w + WP_TILE_W - 1) / WP_TILE_W; a.tiles_y = (a.out_h + WP_TILE_H - 1) / WP_TILE_H;
+  // the wide stores: a lane's 4 cells of a channel at once need the width a multiple of 4 (every row and every channel
+  // plane then starts at a multiple of 4 elements) and out aligned to those 4 elements
+  a.vec = (out_w % 4 == 0 && ((size_t)out_h * out_w) % 4 == 0 && !((uintptr_t)out & (4 * esize - 1))) ? 1u : 0u;
+  a.colour = colour ? 1u : 0u; a.bf16 = dtype == MRE_BF16 ? 1u : 0u; a.channels = (uint32_t)channels;
+  for (int k = 0; k < channels; k++) {
+    a.src[k] = (uint32_t)chan_src[k]; a.scale[k] = chan_scale[k]; a.bias[k] = chan_bias[k];
+  }
+  a.out = out;
+  mre_launch_warp_inputs(&a, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
 }

@@ -17,6 +17,11 @@ sample: a random SE(2) perturbation of the map with its pick and place cells (``
 crops around the pick cell (``crop_matrices``), together ``transporter_sample``
 (``BatchedRearrangementEnv.transporter_sample``).
 
+``warp_inputs``: the same gather written as the tensor a network consumes -- channels-first, normalised per channel
+(``Channels``), float32 or bfloat16 -- by ``mre_warp_inputs`` (csrc/mre_warp_inputs.hip) in one launch, and on it
+``transporter_batch`` (``BatchedRearrangementEnv.transporter_batch``): the perturbed scene, the rotated pick crops and the
+label indices of a Transporter training batch, ready for a convolution.
+
 The kernels are enqueued on torch's current stream; nothing here synchronises.
 """
 from __future__ import annotations
@@ -528,3 +533,155 @@ def transporter_sample(maps, pick_cells, place_cells, *, seed: int, env_ids, dra
     flat = warp_maps(warped.height, warped.colour, warped.seg, mats=mats, index=index, out_shape=(crop, crop))
     crops = WarpedMaps(*[None if x is None else x.view((n, n_rotations) + tuple(x.shape[1:])) for x in flat])
     return TransporterSample(warped, pert.cells[:, 0], pert.cells[:, 1], crops, pert.tries)
+
+
+# ------------------------------------------------------------------------------------------------- network inputs
+SRC_RED, SRC_GREEN, SRC_BLUE, SRC_HEIGHT = 0, 1, 2, 3   # MRE_SRC_* of include/mre.h
+MAX_CHANNELS = 8
+_DTYPES = {torch.float32: 0, torch.bfloat16: 1}          # MRE_F32, MRE_BF16
+# hi_z - lo_z of tasks.rearrangement.HEIGHTMAP_BOUNDS in metres (tests/test_warp_inputs.py holds the two together): the
+# heights of the default maps lie in [0, HEIGHT_SPAN]
+HEIGHT_SPAN = 0.3
+
+
+class Channels(collections.namedtuple("Channels", ["sources", "scales", "biases"])):
+    """The channels of a network input: channel k holds source ``sources[k]`` (0 red, 1 green, 2 blue, 3 height; they may
+    repeat, in any order, 1 to 8 of them) of the gathered cell as a float32, times ``scales[k]``, plus ``biases[k]`` --
+    two float32 operations, each rounded.  A cell whose source cell does not exist is a raw 0, so it holds the bias.
+    Scales and biases are finite and are kept as the float32 values the kernel is given."""
+    __slots__ = ()
+
+    def __new__(cls, sources, scales=None, biases=None):
+        src = tuple(int(x) for x in sources)
+        one = lambda v, fill: np.broadcast_to(np.asarray(fill if v is None else v, np.float64), (len(src),))
+        with np.errstate(over="ignore"):   # a value beyond float32 becomes an inf, which is refused below
+            sc, bi = one(scales, 1.0).astype(np.float32), one(biases, 0.0).astype(np.float32)
+        if not 1 <= len(src) <= MAX_CHANNELS:
+            raise ValueError(f"between 1 and {MAX_CHANNELS} channels")
+        if any(x not in (SRC_RED, SRC_GREEN, SRC_BLUE, SRC_HEIGHT) for x in src):
+            raise ValueError("a channel's source is 0 (red), 1 (green), 2 (blue) or 3 (height)")
+        if not (np.isfinite(sc).all() and np.isfinite(bi).all()):
+            raise ValueError("scales and biases must be finite (as float32)")
+        return super().__new__(cls, src, tuple(float(x) for x in sc), tuple(float(x) for x in bi))
+
+    @classmethod
+    def from_mean_std(cls, sources, mean, std, colour_unit: float = 1.0 / 255.0) -> "Channels":
+        """Channels that hold (u - mean) / std, u the colour byte times ``colour_unit`` or the height: scale = unit / std
+        and bias = -mean / std, formed in float64 and rounded to float32 once.  ``mean`` and ``std``: one per channel, or
+        one for all."""
+        src = np.asarray([int(x) for x in sources], np.int64)
+        mean = np.broadcast_to(np.asarray(mean, np.float64), src.shape)
+        std = np.broadcast_to(np.asarray(std, np.float64), src.shape)
+        unit = np.where(src == SRC_HEIGHT, 1.0, float(colour_unit))
+        return cls(src, unit / std, -mean / std)
+
+    @property
+    def uses_colour(self) -> bool:
+        return any(x != SRC_HEIGHT for x in self.sources)
+
+
+# every channel in [0, 1] on the default maps: colour bytes by 1 / 255, heights by 1 / HEIGHT_SPAN; RGBHHH is the six-channel
+# input of Ravens' Transporter (the height three times)
+CHANNELS_RGBH = Channels((0, 1, 2, 3), (1 / 255.0,) * 3 + (1 / HEIGHT_SPAN,))
+CHANNELS_RGBHHH = Channels((0, 1, 2, 3, 3, 3), (1 / 255.0,) * 3 + (1 / HEIGHT_SPAN,) * 3)
+
+# scene [N, C, rows, columns] and crops [N, n_rotations, C, crop, crop]: the network inputs; pick, place int64 [N, 2]
+# (column, row) in the scene; pick_index, place_index int64 [N] = row * columns + column; rotation_index int64 [N];
+# tries as in Perturbation
+TransporterBatch = collections.namedtuple(
+    "TransporterBatch", ["scene", "crops", "pick", "place", "pick_index", "place_index", "rotation_index", "tries"])
+
+
+def _as_channels(channels) -> Channels:
+    return channels if isinstance(channels, Channels) else Channels(*channels)
+
+
+def _input_args(colour, channels, dtype) -> Channels:
+    channels = _as_channels(channels)
+    if dtype not in _DTYPES:
+        raise ValueError("dtype must be torch.float32 or torch.bfloat16")
+    if channels.uses_colour and colour is None:
+        raise ValueError("a colour channel needs the colour map")
+    return channels
+
+
+def warp_inputs_reference(height: torch.Tensor, colour: Optional[torch.Tensor] = None, *, mats, index=None,
+                          out_shape=None, channels=CHANNELS_RGBH, dtype=torch.float32) -> torch.Tensor:
+    """The statement of ``warp_inputs`` (include/mre.h, mre_warp_inputs) in plain torch, float32 operation by operation,
+    on whatever device ``height`` is on and for any strides: ``warp_maps_reference``, the colour bytes and the height as
+    float32 planes, ``x * scale`` and ``+ bias`` as two operations, ``.to(dtype)``.  The fallback of ``warp_inputs`` and, on
+    the CPU, bit for bit what the kernel computes."""
+    channels = _input_args(colour, channels, dtype)
+    w = warp_maps_reference(height, colour if channels.uses_colour else None, mats=mats, index=index, out_shape=out_shape,
+                            with_source=False)
+    dev = w.height.device
+    planes = [w.height if s == SRC_HEIGHT else w.colour[..., s].to(torch.float32) for s in channels.sources]
+    x = torch.stack(planes, dim=1)
+    x = x * torch.tensor(channels.scales, dtype=torch.float32, device=dev).view(1, -1, 1, 1)
+    x = x + torch.tensor(channels.biases, dtype=torch.float32, device=dev).view(1, -1, 1, 1)
+    return x.to(dtype)
+
+
+def warp_inputs(height: torch.Tensor, colour: Optional[torch.Tensor] = None, *, mats, index=None, out_shape=None,
+                channels=CHANNELS_RGBH, dtype=torch.float32) -> torch.Tensor:
+    """The gather of ``warp_maps`` -- the same ``mats``, ``index`` and ``out_shape``, the same source cell and the same
+    empty cells, bit for bit -- as a network input [S, C, rows, columns] of ``dtype`` (float32 or bfloat16, rounded to
+    nearest even): channel k is ``channels`` (a ``Channels``, or its three sequences) applied to the gathered colour byte or
+    height, and to 0 where the source cell does not exist.  Contiguous CUDA float32 height with uint8 colour is one launch
+    of ``mre_warp_inputs`` on torch's current stream, without a synchronise and with no intermediate; anything else is
+    computed by ``warp_inputs_reference`` with the same result."""
+    channels = _input_args(colour, channels, dtype)
+    dev = height.device
+    on_device = height.is_cuda and height.dtype == torch.float32 and height.is_contiguous() and (
+        colour is None or (colour.device == dev and colour.dtype == torch.uint8 and colour.is_contiguous()))
+    if not on_device:
+        return warp_inputs_reference(height, colour, mats=mats, index=index, out_shape=out_shape, channels=channels,
+                                     dtype=dtype)
+    mats, index = _as_mats(mats, dev), _as_index(index, dev)
+    n, in_h, in_w, samples, out_h, out_w = _warp_args(height, colour, None, mats, index, out_shape)
+    nc = len(channels.sources)
+    out = torch.empty((samples, nc, out_h, out_w), dtype=dtype, device=dev)
+    if n and samples:
+        src = (C.c_int32 * nc)(*channels.sources)
+        scale, bias = (C.c_float * nc)(*channels.scales), (C.c_float * nc)(*channels.biases)
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(_lib.lib().mre_warp_inputs(
+                stream, height.data_ptr(), colour.data_ptr() if channels.uses_colour else None, n, in_h, in_w,
+                None if index is None else index.data_ptr(), mats.data_ptr(), samples, out_h, out_w, nc,
+                C.addressof(src), C.addressof(scale), C.addressof(bias), _DTYPES[dtype], out.data_ptr()), "mre_warp_inputs")
+    return out
+
+
+def transporter_batch(maps, pick_cells, place_cells, *, seed: int, env_ids, draw: int, n_rotations: int = 36,
+                      crop: int = 64, channels=CHANNELS_RGBH, dtype=torch.float32) -> TransporterBatch:
+    """One Transporter training batch from the ``maps`` of the envs (a ``HeightMap`` / ``WarpedMaps``, or (height,
+    colour)), as the tensors a network takes: see ``TransporterBatch``.  The motion is ``transporter_sample``'s -- the same
+    ``sample_perturbation(seed, env_ids, draw)`` of the pick and place cells ([N, 2] (column, row)), so the same (seed, env
+    id, draw) gives the same motion.  ``scene`` is ``warp_inputs`` of the source maps under that motion; ``crops`` is
+    ``warp_inputs`` of the perturbed maps under ``crop_matrices`` around the moved pick cell.  The perturbed uint8 / float32
+    maps are still made once by ``warp_maps``, because the crops gather from them (nearest of nearest is not nearest of the
+    composition); the crops themselves are never written as bytes.  Three launches for CUDA maps.
+
+    ``pick_index`` / ``place_index`` are row * columns + column of the moved cells: the class a softmax over the flattened
+    scene is trained on (meaningful where the cell is inside the map, as it is where ``tries`` > 0).  ``rotation_index`` is
+    0 for every env: the scripted demonstrator's ``gripper_rot`` is 0 for the pick and for the place, so the relative
+    rotation bin a Transporter's place head is trained on is bin 0."""
+    height, colour = maps[0], maps[1]
+    channels = _input_args(colour, channels, dtype)
+    to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    cells = np.stack([to_np(pick_cells), to_np(place_cells)], axis=1).astype(np.int64)
+    n = int(height.shape[0])
+    if cells.shape != (n, 2, 2):
+        raise ValueError("pick_cells and place_cells must be [N, 2]")
+    cols = int(height.shape[2])
+    pert = sample_perturbation(seed, env_ids, draw, cells, tuple(height.shape[1:3]))
+    kw = dict(channels=channels, dtype=dtype)
+    scene = warp_inputs(height, colour, mats=pert.M, **kw)
+    warped = warp_maps(height, colour if channels.uses_colour else None, mats=pert.M, with_source=False)
+    mats, index = crop_matrices(pert.cells[:, 0], n_rotations, crop)
+    crops = warp_inputs(warped.height, warped.colour, mats=mats, index=index, out_shape=(crop, crop), **kw)
+    pick, place = pert.cells[:, 0], pert.cells[:, 1]
+    return TransporterBatch(scene, crops.view((n, n_rotations) + tuple(crops.shape[1:])), pick, place,
+                            pick[:, 1] * cols + pick[:, 0], place[:, 1] * cols + place[:, 0], np.zeros(n, np.int64),
+                            pert.tries)

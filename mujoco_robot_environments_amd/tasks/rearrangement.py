@@ -26,6 +26,7 @@ import enum
 from typing import Dict, Optional
 
 import numpy as np
+import torch
 from scipy.spatial.transform import Rotation as R
 
 from .. import demo_logic, perception, placement, rng
@@ -255,6 +256,22 @@ class BatchedRearrangementEnv:
             maps, perception.world_2_cell(pick[:, :3], HEIGHTMAP_BOUNDS, cell),
             perception.world_2_cell(place[:, :3], HEIGHTMAP_BOUNDS, cell), seed=seed, env_ids=self.env_ids, draw=draw,
             n_rotations=n_rotations, crop=crop)
+
+    def transporter_batch(self, seed: int, draw: int = 0, depth=None, rgb=None, seg=None, cell: float = 0.0025,
+                          n_rotations: int = 36, crop: int = 64, channels=perception.CHANNELS_RGBH,
+                          dtype=torch.bfloat16, camera: str = OVERHEAD):
+        """One Transporter training batch on the device as the tensors a network takes, a
+        ``perception.TransporterBatch``: ``scene`` [N, C, rows, columns] and ``crops`` [N, n_rotations, C, crop, crop],
+        channels-first, normalised by ``channels`` (a ``perception.Channels``) and in ``dtype``, with the
+        moved pick and place cells and their flat indices.  The steps of ``transporter_sample`` up to the cells -- the same
+        maps, the same motion for the same (``seed``, global env id, ``draw``) -- then ``perception.transporter_batch``.  No
+        state of the env changes."""
+        maps = self.heightmap(depth, rgb, seg, camera=camera, cell=cell)
+        _, pick, place = self.sort_colours(peek=True)
+        return perception.transporter_batch(
+            maps, perception.world_2_cell(pick[:, :3], HEIGHTMAP_BOUNDS, cell),
+            perception.world_2_cell(place[:, :3], HEIGHTMAP_BOUNDS, cell), seed=seed, env_ids=self.env_ids, draw=draw,
+            n_rotations=n_rotations, crop=crop, channels=channels, dtype=dtype)
 
     def _compute_observation(self):
         if not self.render_observations:
