@@ -77,6 +77,7 @@ static int create_buffers(mre_env* e, int num_envs, int device_id) {
   { int rc = sched_create(e); if (rc) return rc; }
   if (const char* fb = getenv("MRE_NO_FALLBACK")) e->fallback = atoi(fb) == 0;  // profiling knob only
   if (const char* ng = getenv("MRE_NARROW_GENERIC")) e->base_flags = atoi(ng) != 0 ? F_CLIP_ALWAYS : 0u;  // comparison knob only
+  if (const char* ng = getenv("MRE_NEWTON_GENERIC")) e->base_flags |= atoi(ng) != 0 ? F_NW_ALL_TILES : 0u;  // likewise: every Hessian tile
   if (const char* fl = getenv("MRE_FORCE_LARGE")) {  // profiling knob only: start every env on the large kernel
     if (atoi(fl) != 0) {
       e->h_large.assign(N, 1); e->n_large = num_envs;

@@ -226,12 +226,14 @@ struct OscConfig {
 // (OSC.compute_control_output + MinMax.compute_control_output) in ctrl without stepping
 enum StepFlags : unsigned { F_NO_CONSTRAINTS = 1u, F_FREEZE_ROBOT = 2u, F_CONV_CONTINUE = 4u, F_CONV_OPEN = 8u,
                             F_OSC_EVAL = 16u, F_DETECT = 32u, F_SETTLE_EXIT = 64u, F_DETECT_ACTIVE = 128u,
-                            F_CLIP_ALWAYS = 256u };
+                            F_CLIP_ALWAYS = 256u, F_NW_ALL_TILES = 512u };
 // F_DETECT (zero-step launch): narrow phase on the current poses, every detected contact (dist < margin)
 //   exported to `contacts` -- physics.forward() + physics.data.contact of the reference's PropPlacer
 // F_DETECT_ACTIVE (with F_DETECT): the list the next solve would get instead (dist < margin - gap: collide(.., detect = false))
 // F_CLIP_ALWAYS: the narrow phase clips every face contact through its LDS buffers, also where nothing is clipped
 //   (set for every launch of a handle created under MRE_NARROW_GENERIC=1: the two paths compared inside one process)
+// F_NW_ALL_TILES: nw_direction forms and moves all six Hessian tiles, also the cross tiles the step's contact set leaves
+//   zero (set for every launch of a handle created under MRE_NEWTON_GENERIC=1; mre_newton.h)
 // F_SETTLE_EXIT: an env leaves the step loop once its cubes have settled (max |qvel| < 1e-3, max |qacc| <
 //   1e-2, time > min_settle_steps * dt: environment/prop_initializer.py:240-258); steps taken -> settle_steps
 enum CtrlMode : int { CTRL_HELD = 0, CTRL_SEQ = 1, CTRL_OSC = 2 };

@@ -60,7 +60,7 @@ struct mre_env {
   size_t events_used = 0;
   // ---- capacity fallback (see launch_step): per-env kernel choice, pre-launch state copies
   bool fallback = true;
-  unsigned base_flags = 0;    // StepFlags of every launch (F_CLIP_ALWAYS under MRE_NARROW_GENERIC=1)
+  unsigned base_flags = 0;    // StepFlags of every launch (F_CLIP_ALWAYS under MRE_NARROW_GENERIC=1, F_NW_ALL_TILES under MRE_NEWTON_GENERIC=1)
   bool large_only = false;
   bool compact_only = false;  // mre_set_fallback(0)  // mre_set_fallback(2): every env on the large kernel (reference run for the fallback)
   hipStream_t stream2 = nullptr;

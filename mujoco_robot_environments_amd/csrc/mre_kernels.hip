@@ -1727,7 +1727,7 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
       MRE_STAMP(2);
       assemble_constraints(M, s, l);
 #ifdef MRE_NEWTON
-      nw_build_lists(s, l);
+      nw_build_lists(s, l, a.flags);
 #else
       solve_robot_rows(s, l);
       assemble_blocks(M, s, l);

@@ -23,6 +23,7 @@
 namespace mre {
 
 constexpr int NW_QUAD = 0, NW_SAT = 1, NW_CONE = 4;
+constexpr unsigned NW_CPL_ALL_TILES = 0x80u;  // Sm::cpl_robot, above the four cube bits: the launch carries F_NW_ALL_TILES
 constexpr int NW_LS_MAX = 20;       // line-search evaluations at most (opt.ls_iterations = 50 in fp64)
 constexpr float NW_LS_TOL = 0.01f;  // opt.ls_tolerance
 #ifndef NW_LS_REL_VALUE
@@ -273,7 +274,8 @@ struct NwPoint { float alpha, cost, d1, d2; };
 // Per-cube contact lists and the block coupling of the Hessian (lane 0, after the assembly has
 // fixed the kept contacts and their robot slots).  A phase of its own: the row assembly is at the
 // edge of its register budget.
-MRE_PHASE_FN void nw_build_lists(Sm& s, int l) {
+// flags: the launch's StepFlags; F_NW_ALL_TILES rides to nw_direction in a spare bit of the robot mask it reads anyway.
+MRE_PHASE_FN void nw_build_lists(Sm& s, int l, unsigned flags) {
   // lane = contact; a cube's list is the ascending run of the contacts that touch it (ballot prefix counts)
   const int kept = s.ncon;
   const bool on = l < kept;
@@ -296,6 +298,7 @@ MRE_PHASE_FN void nw_build_lists(Sm& s, int l) {
 #pragma unroll
   for (int b = 0; b < 6; b++)
     if (__ballot(pairbit == b) != 0ull) cc |= 1u << b;
+  if ((flags & F_NW_ALL_TILES) != 0u) cr |= NW_CPL_ALL_TILES;
   if (l == 0) { s.cpl_robot = (uint8_t)cr; s.cpl_cubes = (uint8_t)cc; }
   // lane = row: where the row's Jacobian words of every cube live (read by the matrix-core pass of nw_direction)
   const int nscalar = 7 + s.nl;
@@ -357,6 +360,7 @@ MRE_DEV float nw_update_gradient(Sm& s, int l, const NwLane& c, int nscalar, int
 // cost), first constraint update and gradient.  Returns the cost.
 template <bool PYR>
 MRE_DEV float nw_setup_impl(ModelP M, Sm& s, int l) {
+  MRE_DBG_T0();
   const NwLane c = nw_lane(M, s, l);
   const int nefc = s.nefc, ncon = s.ncon, nscalar = 7 + s.nl;
   // (the dense robot block cannot be written by crb_mass_matrix: the narrow phase's per-lane clip buffers run over
@@ -369,6 +373,7 @@ MRE_DEV float nw_setup_impl(ModelP M, Sm& s, int l) {
     s.Md[i][j] = v; s.Md[j][i] = v;
   }
   MRE_SYNC();
+  MRE_DBG_STAMP(10, 0);
   const bool on = l < NV && c.lact;
   const float fs = on ? s.qfrc_smooth[l] : 0.f, as = on ? s.qacc_smooth[l] : 0.f;
   float qa = on ? s.qacc[l] : 0.f;
@@ -381,27 +386,62 @@ MRE_DEV float nw_setup_impl(ModelP M, Sm& s, int l) {
     s.jv[i] = d2 - aref;
   }
   MRE_SYNC();
+  MRE_DBG_STAMP(10, 1);
   const float gauss = wave_sum(0.5f * (Ma - fs) * (qa - as));
   const float cost_ws = gauss + nw_update<false, PYR>(s, l, nscalar, ncon, c.mu_scale, s.jar);
   const float cost_sm = nw_update<false, PYR>(s, l, nscalar, ncon, c.mu_scale, s.jv);
-  if (cost_ws > cost_sm || !(cost_ws == cost_ws)) {
+  const bool smooth_wins = cost_ws > cost_sm || !(cost_ws == cost_ws);
+#if defined(MRE_PHASE_STAMPS) && MRE_PHASE_STAMPS == 11
+  // diagnostic build 11 counts: set-up calls of the launch and those in which qacc_smooth beat the warm start
+  if (threadIdx.x == 0) { dbg_acc[0] += 1ull << 4; dbg_acc[1] += (unsigned long long)smooth_wins << 4; }
+#endif
+  if (smooth_wins) {
     qa = as; Ma = fs;  // M qacc_smooth = qfrc_smooth
     for (int i = l; i < nefc; i += 64) s.jar[i] = s.jv[i];
   }
   if (l < NVP) { s.qacc[l] = qa; s.nw_Ma[l] = Ma; }
   MRE_SYNC();
-  return nw_update_gradient<PYR>(s, l, c, nscalar, ncon);
+  MRE_DBG_STAMP(10, 2);
+  const float cost = nw_update_gradient<PYR>(s, l, c, nscalar, ncon);
+  MRE_DBG_STAMP(10, 3);
+  return cost;
 }
 MRE_PHASE_FN float nw_setup(ModelP M, Sm& s, int l) { return nw_setup_impl<false>(M, s, l); }
 MRE_PHASE_FN float nw_setup_pyramidal(ModelP M, Sm& s, int l) { return nw_setup_impl<true>(M, s, l); }
 
 // Phase 2: search = -H^-1 grad.  H = M + J' D J (+ cone Hessians) with its rows in registers,
 // block-sparse factorisation H = W W', both triangular solves.
+// Bit NW_CPL_ALL_TILES of s.cpl_robot (F_NW_ALL_TILES): also form and move the cross tiles that the contact set leaves zero.
 MRE_PHASE_FN void nw_direction(ModelP M, Sm& s, int l) {
   MRE_DBG_T0();
   const NwLane c = nw_lane(M, s, l);
   const int nefc = s.nefc, nscalar = 7 + s.nl, nprops = s.nprops;
   const int lp = c.lp, lk = c.lk;
+  // Which cross tiles a row of this step can reach.  A row feeds a cross tile only if it has both parts: equality and
+  // limit rows are robot-only, cube-table contacts cube-only, so c10 / c20 (cubes 0-1 / 2-3 x robot) take a kept
+  // contact that joins the robot to a cube of the group (cpl_robot) and c21 one that joins a cube of {0, 1} to one of
+  // {2, 3} (cpl_cubes) -- the masks that already tell the elimination which blocks fill in.  A tile that is not
+  // formed leaves its part of hh as it was initialised: these are off-diagonal blocks, set from the literal 0.f below
+  // (Md enters the robot x robot block only, which c00 always serves), and a formed tile without such a row is +0.0 in
+  // every word that is read (accumulators start at +0.0 and only take products with a zero word of the row), so
+  // "+= +0.0" on +0.0 and no addition at all leave the same bits.
+  bool t10, t20, t21;
+  {
+    const unsigned cr = (unsigned)uni((int)s.cpl_robot), cq = (unsigned)uni((int)s.cpl_cubes);
+    constexpr unsigned across = (1u << cube_pair_bit(0, 2)) | (1u << cube_pair_bit(0, 3)) | (1u << cube_pair_bit(1, 2)) |
+                                (1u << cube_pair_bit(1, 3));
+    const bool all_tiles = (cr & NW_CPL_ALL_TILES) != 0u;
+    t10 = all_tiles || (cr & 0x3u) != 0u;
+    t20 = all_tiles || (cr & 0xCu) != 0u;
+    t21 = all_tiles || (cq & across) != 0u;
+  }
+#if defined(MRE_PHASE_STAMPS) && MRE_PHASE_STAMPS == 9
+  // diagnostic build 9 counts, it does not time: direction calls of the launch, and those that skipped c10 / c20 / c21
+  if (threadIdx.x == 0) {
+    dbg_acc[0] += 1ull << 4; dbg_acc[1] += (unsigned long long)!t10 << 4;
+    dbg_acc[2] += (unsigned long long)!t20 << 4; dbg_acc[3] += (unsigned long long)!t21 << 4;
+  }
+#endif
   float hh[NV];
 #pragma unroll
   for (int k = 0; k < NV; k++) {
@@ -459,7 +499,10 @@ MRE_PHASE_FN void nw_direction(ModelP M, Sm& s, int l) {
     // one chunk on the metadata `cur`; the metadata of the following chunk goes to `nxt`.  The loop calls it with
     // two sets in turn, so no registers are shuffled between chunks.
     struct Meta { int ii, st, h; float R; uint2 d; };
-    auto chunk = [&](const Meta& cur, Meta& nxt, int r0) {
+    // cross (compile time): the step has a cross tile.  The loop exists twice, so that the common step -- none --
+    // runs its three diagonal MFMAs with no test per chunk (tests inside the chunk cost more than the MFMAs they
+    // save: profiles/NOTES.md, round 5); with a cross tile the three flags pick per tile.
+    auto chunk = [&](auto cross, const Meta& cur, Meta& nxt, int r0) {
       const int ii = cur.ii, h = cur.h, st = cur.st;
       const uint2 d = cur.d;
       const bool quad = st == NW_QUAD, cone = st == NW_CONE;
@@ -492,20 +535,31 @@ MRE_PHASE_FN void nw_direction(ModelP M, Sm& s, int l) {
         a0 = v0 * D; a1 = v1 * D; a2 = v2 * D;
       }
       c00 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, v0, c00, 0, 0, 0);
-      c10 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, v0, c10, 0, 0, 0);
+      if constexpr (decltype(cross)::value) { if (t10) c10 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, v0, c10, 0, 0, 0); }
       c11 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, v1, c11, 0, 0, 0);
       if (nprops > 2) {   // (wave-uniform: cubes 2 and 3 exist)
-        c20 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, v0, c20, 0, 0, 0);
-        c21 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, v1, c21, 0, 0, 0);
+        if constexpr (decltype(cross)::value) {
+          if (t20) c20 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, v0, c20, 0, 0, 0);
+          if (t21) c21 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, v1, c21, 0, 0, 0);
+        }
         c22 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, v2, c22, 0, 0, 0);
       }
     };
     Meta mA, mB;
     meta(0, mA.ii, mA.st, mA.h, mA.R, mA.d);
     mB = mA;
-    for (int r0 = 0; r0 < nefc; r0 += 8) {
-      chunk(mA, mB, r0);
-      if (r0 + 4 < nefc) chunk(mB, mA, r0 + 4);
+    using NwYes = std::integral_constant<bool, true>;
+    using NwNo = std::integral_constant<bool, false>;
+    if (t10 || t20 || t21) {
+      for (int r0 = 0; r0 < nefc; r0 += 8) {
+        chunk(NwYes{}, mA, mB, r0);
+        if (r0 + 4 < nefc) chunk(NwYes{}, mB, mA, r0 + 4);
+      }
+    } else {
+      for (int r0 = 0; r0 < nefc; r0 += 8) {
+        chunk(NwNo{}, mA, mB, r0);
+        if (r0 + 4 < nefc) chunk(NwNo{}, mB, mA, r0 + 4);
+      }
     }
     MRE_DBG_STAMP(4, 1);
     // Tiles -> rows: lane j needs row j of H.  One tile at a time through LDS (the factor's home, unused until
@@ -532,24 +586,44 @@ MRE_PHASE_FN void nw_direction(ModelP M, Sm& s, int l) {
     }
     constexpr int T2 = 16 * TS;
     static_assert(2 * T2 <= NV * (NV + 1) / 2, "two tiles fit the factor's storage");
-    spill(c00, 0); spill(c10, T2);
-    MRE_SYNC();
-    NW_TILE(0, 0, 0, 0, NRV, 0, NRV)
-    if (nprops > 0) { NW_TILE(T2, 1, 0, NRV, 12, 0, NRV) }
-    MRE_SYNC();
-    if (nprops > 0) {
-      spill(c11, 0); spill(c20, T2);
+    // (every word of hh takes its sum from ONE tile, so which tiles share a trip changes no bit)
+    if (t10 || t20 || t21) {
+      spill(c00, 0);
+      if (t10) spill(c10, T2);
       MRE_SYNC();
-      NW_TILE(0, 1, 1, NRV, 12, NRV, 12)
-      if (nprops > 2) { NW_TILE(T2, 2, 0, NRV + 12, 12, 0, NRV) }
+      NW_TILE(0, 0, 0, 0, NRV, 0, NRV)
+      if (nprops > 0 && t10) { NW_TILE(T2, 1, 0, NRV, 12, 0, NRV) }
       MRE_SYNC();
-    }
-    if (nprops > 2) {
-      spill(c21, 0); spill(c22, T2);
+      if (nprops > 0) {
+        spill(c11, 0);
+        if (t20) spill(c20, T2);
+        MRE_SYNC();
+        NW_TILE(0, 1, 1, NRV, 12, NRV, 12)
+        if (nprops > 2 && t20) { NW_TILE(T2, 2, 0, NRV + 12, 12, 0, NRV) }
+        MRE_SYNC();
+      }
+      if (nprops > 2) {
+        if (t21) spill(c21, 0);
+        spill(c22, T2);
+        MRE_SYNC();
+        if (t21) { NW_TILE(0, 2, 1, NRV + 12, 12, NRV, 12) }
+        NW_TILE(T2, 2, 2, NRV + 12, 12, NRV + 12, 12)
+        MRE_SYNC();
+      }
+    } else {
+      // no cross tile: the three diagonal tiles take two trips (one for an env of at most two cubes) instead of three
+      spill(c00, 0);
+      if (nprops > 0) spill(c11, T2);
       MRE_SYNC();
-      NW_TILE(0, 2, 1, NRV + 12, 12, NRV, 12)
-      NW_TILE(T2, 2, 2, NRV + 12, 12, NRV + 12, 12)
+      NW_TILE(0, 0, 0, 0, NRV, 0, NRV)
+      if (nprops > 0) { NW_TILE(T2, 1, 1, NRV, 12, NRV, 12) }
       MRE_SYNC();
+      if (nprops > 2) {
+        spill(c22, 0);
+        MRE_SYNC();
+        NW_TILE(0, 2, 2, NRV + 12, 12, NRV + 12, 12)
+        MRE_SYNC();
+      }
     }
 #undef NW_TILE
   }

@@ -18,11 +18,20 @@ NAMES = ["position+crb+factor", "velocity", "collide", "assemble", "control", "s
          # set 8 counts, it does not time: lanes per env and tick (5 steps) that took box_box's face-contact branch, those
          # whose candidates stayed in registers (mre_collide.h), and the same two over the pairs with the table
          "  collide: face contacts", "  collide: face contacts kept in registers", "  collide: table face contacts",
-         "  collide: table face contacts kept in registers"]
+         "  collide: table face contacts kept in registers",
+         # set 9 counts too: nw_direction calls per env and tick, and those that formed no c10 / c20 / c21 tile (cubes 0-1 x
+         # robot, cubes 2-3 x robot, cubes 2-3 x cubes 0-1; an env of at most two cubes has no second group and always
+         # counts under the last two)
+         "  direction: calls", "  direction: calls without tile c10", "  direction: calls without tile c20",
+         "  direction: calls without tile c21",
+         "  setup: dense robot M", "  setup: M a, J a, J a_smooth", "  setup: constraint updates, choice of the start",
+         "  setup: J'f, gradient",
+         # set 11 counts: set-up calls per env and tick, and those in which qacc_smooth beat the warm start
+         "  setup: calls", "  setup: calls won by qacc_smooth", "  (unused)", "  (unused)"]
 
 if sys.argv[1] == "build":
     os.makedirs(DIAG, exist_ok=True)
-    for k in ([int(x) for x in sys.argv[2:]] or (0, 1, 2, 3, 4, 5, 6, 7, 8)):
+    for k in ([int(x) for x in sys.argv[2:]] or (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11)):
         base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-ffp-contract=on",
                 "-fno-hip-fp32-correctly-rounded-divide-sqrt"]
         objs = []
@@ -31,7 +40,9 @@ if sys.argv[1] == "build":
                                  ("kn", "mre_kernels.hip", ["-DMRE_NEWTON", f"-DMRE_PHASE_STAMPS={k}"]),
                                  ("kln", "mre_kernels.hip", ["-DMRE_LARGE_CAPS", "-DMRE_NEWTON", f"-DMRE_PHASE_STAMPS={k}"]),
                                  ("r", "mre_render.hip", []),
-                                 ("rec", "mre_records.hip", []),
+                                 ("rec", "mre_records.hip", []), ("lab", "mre_labels.hip", []),
+                                 ("hm", "mre_heightmap.hip", []), ("warp", "mre_warp.hip", []),
+                                 ("wi", "mre_warp_inputs.hip", []),
                                  ("api", "mre_api.cpp", []), ("sched", "mre_sched.cpp", []),
                                  ("model", "mre_model.cpp", [])):
             objs.append(os.path.join(DIAG, f"{name}{k}.o"))
