@@ -459,6 +459,40 @@ int mre_warp_inputs(void* stream, const float* hmap, const uint8_t* cmap, int n,
                     int channels, const int32_t* chan_src, const float* chan_scale, const float* chan_bias,
                     int dtype, void* out);
 
+/* The Transporter place head on the device (csrc/mre_correlate.hip): every env's scene feature map
+ * cross-correlated with that env's own rotated crop feature maps, and the best (rotation, row, column) per env.
+ *   scene   device bfloat16 [n][depth][h][w]
+ *   kern    device bfloat16 [n][rotations][depth][crop][crop], crop even
+ * For env e, rotation r, row y and column x:
+ *   logit[e][r][y][x] = sum_d sum_{i<crop} sum_{j<crop} scene[e][d][y + i - crop/2][x + j - crop/2] * kern[e][r][d][i][j]
+ * A scene cell outside [0, h) x [0, w) counts as 0.  Crop index crop/2 is the pivot -- where crop_matrices puts the pick
+ * cell at rotation 0 -- so a scene patch that equals the crop peaks at the cell where its pivot lies.
+ * Every product is exact in float32 because both factors are bfloat16.  The sum is accumulated in float32 on the matrix
+ * cores; its order is the kernel's own, fixed, and the same on every run; it is not part of the statement.
+ *   logits      NULL, or device [n][rotations][h][w] of `dtype`: the float32 sums (MRE_F32), or those sums rounded to
+ *               bfloat16 as mre_warp_inputs rounds (MRE_BF16)
+ *   best_index  device i64 [n], best_value device f32 [n] (NULL together): the largest float32 sum of env e, taken before
+ *               any bfloat16 rounding, and its flat index (r * h + y) * w + x.  The first cell is the initial candidate and
+ *               a later cell replaces it only when it is strictly greater: ties go to the lowest flat index, and a NaN
+ *               never wins.  The same bits whether or not logits is written.
+ *   workspace   device, 16-byte aligned, at least the bytes mre_correlate_workspace answers for (n, rotations, h, w);
+ *               its contents before and after the call mean nothing
+ * All inputs are assumed finite; non-finite inputs do not fault, and beyond that the results are unspecified.
+ * Every element of logits and best_* is written exactly once and nothing else but the workspace is; no atomics; the same
+ * bytes on every run.  Logits are stored 8 columns at a time where w is a multiple of 8 and logits is 16-byte aligned, else
+ * element by element at any element offset, with the same bits.  Enqueued on `stream` of the current device (two launches
+ * with best_*, one without); nothing synchronises.
+ * MRE_ERR_ARG, with nothing launched, unless n >= 0 (0: MRE_OK, nothing launched), 1 <= rotations <= 64,
+ * 1 <= depth <= 16, crop even and 2 <= crop <= 64, 1 <= h, w <= 4096, rotations * h * w < 2^31, scene and kern are non-NULL
+ * device pointers aligned to 2 bytes, dtype is MRE_F32 or MRE_BF16, logits is NULL or aligned to its element size,
+ * best_index and best_value are NULL together or aligned (8 and 4 bytes), logits and best_* are not all NULL, workspace
+ * is non-NULL, 16-byte aligned and large enough, and no output or workspace byte range overlaps an input.
+ * mre_correlate_workspace: MRE_ERR_ARG unless bytes is non-NULL and n, rotations, h, w are in those ranges; at least 16. */
+int mre_correlate_workspace(int n, int rotations, int h, int w, size_t* bytes);
+int mre_correlate(void* stream, const uint16_t* scene, const uint16_t* kern, int n, int rotations, int depth,
+                  int h, int w, int crop, int dtype, void* logits, int64_t* best_index, float* best_value,
+                  void* workspace, size_t workspace_bytes);
+
 #define MRE_SOLVER_PGS 0
 #define MRE_SOLVER_NEWTON 2
 int mre_set_solver(mre_env*, int solver);

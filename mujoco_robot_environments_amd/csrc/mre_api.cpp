@@ -17,6 +17,7 @@
 #include "mre_heightmap.h"
 #include "mre_warp.h"
 #include "mre_warp_inputs.h"
+#include "mre_correlate.h"
 #include "mre_launch.h"
 #include "mre_model.h"
 #include "mre_records.h"
@@ -695,6 +696,82 @@ extern "C" int mre_warp_inputs(void* stream, const float* hmap, const uint8_t* c
   }
   a.out = out;
   mre_launch_warp_inputs(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+// ---- the Transporter place head on the device (csrc/mre_correlate.hip): correlate the crops with the scene, best cell
+static bool correlate_shape_ok(int n, int rotations, int h, int w) {
+  return n >= 0 && rotations >= 1 && rotations <= CR_MAX_ROT && h >= 1 && w >= 1 && h <= CR_MAX_DIM && w <= CR_MAX_DIM &&
+         (long long)rotations * h * w < (1ll << 31);
+}
+
+static size_t correlate_workspace(int n, int h, int w) {
+  const size_t slots = (size_t)n * cr_tiles((uint32_t)h, CR_TILE_H) * cr_tiles((uint32_t)w, CR_TILE_W);
+  const size_t bytes = (slots * CR_SLOT_BYTES + 15) & ~(size_t)15;
+  return bytes ? bytes : 16;   // never 0: a workspace can always be allocated and passed
+}
+
+extern "C" int mre_correlate_workspace(int n, int rotations, int h, int w, size_t* bytes) {
+  const std::string wh("mre_correlate_workspace");
+  if (!bytes) return fail(MRE_ERR_ARG, wh + ": null bytes");
+  if (!correlate_shape_ok(n, rotations, h, w))
+    return fail(MRE_ERR_ARG, wh + ": n >= 0, 1 <= rotations <= 64, 1 <= h, w <= 4096, rotations * h * w < 2^31");
+  *bytes = correlate_workspace(n, h, w);
+  return MRE_OK;
+}
+
+extern "C" int mre_correlate(void* stream, const uint16_t* scene, const uint16_t* kern, int n, int rotations, int depth,
+                             int h, int w, int crop, int dtype, void* logits, int64_t* best_index, float* best_value,
+                             void* workspace, size_t workspace_bytes) {
+  const std::string wh("mre_correlate");
+  if (n < 0) return fail(MRE_ERR_ARG, wh + ": n >= 0");
+  if (rotations < 1 || rotations > CR_MAX_ROT) return fail(MRE_ERR_ARG, wh + ": 1 <= rotations <= 64");
+  if (depth < 1 || depth > CR_MAX_DEPTH) return fail(MRE_ERR_ARG, wh + ": 1 <= depth <= 16");
+  if (crop < 2 || crop > CR_MAX_CROP || (crop & 1)) return fail(MRE_ERR_ARG, wh + ": crop must be even, 2 <= crop <= 64");
+  if (h < 1 || w < 1 || h > CR_MAX_DIM || w > CR_MAX_DIM) return fail(MRE_ERR_ARG, wh + ": 1 <= h, w <= 4096");
+  if (!correlate_shape_ok(n, rotations, h, w)) return fail(MRE_ERR_ARG, wh + ": rotations * h * w must be below 2^31");
+  if (!scene || !kern) return fail(MRE_ERR_ARG, wh + ": null scene or kern");
+  if (((uintptr_t)scene & 1) || ((uintptr_t)kern & 1)) return fail(MRE_ERR_ARG, wh + ": scene and kern must be 2-byte aligned");
+  if (dtype != MRE_F32 && dtype != MRE_BF16) return fail(MRE_ERR_ARG, wh + ": dtype must be MRE_F32 or MRE_BF16");
+  const size_t esize = dtype == MRE_BF16 ? 2 : 4;
+  if ((uintptr_t)logits & (esize - 1)) return fail(MRE_ERR_ARG, wh + ": logits must be aligned to its element size");
+  if (!best_index != !best_value) return fail(MRE_ERR_ARG, wh + ": best_index and best_value are NULL together or not at all");
+  if (((uintptr_t)best_index & 7) || ((uintptr_t)best_value & 3))
+    return fail(MRE_ERR_ARG, wh + ": best_index must be 8-byte and best_value 4-byte aligned");
+  if (!logits && !best_index) return fail(MRE_ERR_ARG, wh + ": nothing to write: logits and best_* are all NULL");
+  const size_t need = correlate_workspace(n, h, w);
+  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need)
+    return fail(MRE_ERR_ARG, wh + ": workspace must be non-NULL, 16-byte aligned and as large as mre_correlate_workspace says");
+  // no output or workspace byte range may overlap an input (n < 2^31, 64 x 16 x 64 x 64 x 2 B per env: below 2^54)
+  const size_t cells = (size_t)h * w;
+  const std::pair<const void*, size_t> ins[2] = {{scene, 2 * (size_t)n * depth * cells},
+                                                 {kern, 2 * (size_t)n * rotations * depth * crop * crop}};
+  const std::pair<const void*, size_t> outs[4] = {{logits, esize * (size_t)n * rotations * cells}, {best_index, 8 * (size_t)n},
+                                                  {best_value, 4 * (size_t)n}, {workspace, need}};
+  for (const auto& o : outs)
+    for (const auto& i : ins) {
+      if (!o.first || !o.second || !i.second) continue;
+      const uintptr_t o0 = (uintptr_t)o.first, i0 = (uintptr_t)i.first;
+      if (o0 < i0 + i.second && i0 < o0 + o.second) return fail(MRE_ERR_ARG, wh + ": an output or the workspace overlaps an input");
+    }
+  if (n == 0) return MRE_OK;
+  if (!is_device_ptr(scene) || !is_device_ptr(kern) || !is_device_ptr(workspace) || (logits && !is_device_ptr(logits)) ||
+      (best_index && (!is_device_ptr(best_index) || !is_device_ptr(best_value))))
+    return fail(MRE_ERR_ARG, wh + ": scene, kern, the outputs and the workspace must be device pointers");
+  CorrelateArgs a;
+  memset(&a, 0, sizeof(a));
+  a.scene = scene; a.kern = kern; a.logits = logits; a.best_index = best_index; a.best_value = best_value;
+  a.workspace = workspace;
+  a.n = (uint32_t)n; a.rot = (uint32_t)rotations; a.depth = (uint32_t)depth; a.h = (uint32_t)h; a.w = (uint32_t)w;
+  a.crop = (uint32_t)crop;
+  a.tiles_x = cr_tiles(a.w, CR_TILE_W); a.tiles_y = cr_tiles(a.h, CR_TILE_H);
+  a.bf16 = dtype == MRE_BF16 ? 1u : 0u;
+  // the wide accesses: a lane's 8 taps of a kernel row (every row then starts at a multiple of 8 elements), and its 8
+  // logits of a pixel row
+  a.vec_kern = (crop % 8 == 0 && !((uintptr_t)kern & 15)) ? 1u : 0u;
+  a.vec_out = (logits && w % 8 == 0 && !((uintptr_t)logits & 15)) ? 1u : 0u;
+  mre_launch_correlate(&a, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
 }

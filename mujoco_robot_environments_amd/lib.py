@@ -21,10 +21,11 @@ _HEADERS = ["mre_dev.h", "mre_math.h", "mre_collide.h", "mre_solver.h", "mre_new
 # The model builder and the launch scheduler are host code like mre_api.cpp: they decide what is uploaded and how
 # launches are issued, not what a launch executes.  The frame-label kernel (mre_labels.hip) reads rendered images and is
 # launched by neither the step nor the camera, and so are the heightmap kernel (mre_heightmap.hip), the map warp
-# (mre_warp.hip) and the network inputs gathered like it (mre_warp_inputs.hip).
+# (mre_warp.hip), the network inputs gathered like it (mre_warp_inputs.hip) and the place head's correlation
+# (mre_correlate.hip).
 _UNHASHED_SOURCES = ["mre_records.hip", "mre_records.h", "mre_labels.hip", "mre_labels.h", "mre_heightmap.hip", "mre_heightmap.h",
                      "mre_heightmap_point.h", "mre_warp.hip", "mre_warp.h", "mre_warp_point.h", "mre_warp_inputs.hip", "mre_warp_inputs.h",
-                     "mre_warp_input_point.h", "mre_model.cpp", "mre_model.h", "mre_sched.cpp", "mre_env.h",
+                     "mre_warp_input_point.h", "mre_correlate.hip", "mre_correlate.h", "mre_model.cpp", "mre_model.h", "mre_sched.cpp", "mre_env.h",
                      "mre_policy.h", "mre_launch.h"]
 _LIB: Optional[C.CDLL] = None
 
@@ -45,7 +46,7 @@ EXPORTS = [
     "mre_get_state_f64", "mre_set_state_f64", "mre_get_time", "mre_pack_final_state",
     "mre_records_workspace_bytes", "mre_varint_pack_rows", "mre_crc32c_rows", "mre_crc32c_combine",
     "mre_varint_unpack_workspace_bytes", "mre_varint_unpack_rows", "mre_get_arm_dynamics", "mre_seg_labels",
-    "mre_heightmap", "mre_warp_maps", "mre_warp_inputs",
+    "mre_heightmap", "mre_warp_maps", "mre_warp_inputs", "mre_correlate_workspace", "mre_correlate",
 ]
 # status bits of mre_varint_unpack_rows (include/mre.h)
 MRE_UNPACK_LONG, MRE_UNPACK_OVERFLOW, MRE_UNPACK_TRUNCATED, MRE_UNPACK_COUNT, MRE_UNPACK_DESC = 1, 2, 4, 8, 16
@@ -103,7 +104,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
              ("kernels_large_newton", "mre_kernels.hip", ["-DMRE_LARGE_CAPS", "-DMRE_NEWTON"]),
              ("render", "mre_render.hip", []), ("records", "mre_records.hip", []),
              ("labels", "mre_labels.hip", []), ("heightmap", "mre_heightmap.hip", []),
-             ("warp", "mre_warp.hip", []), ("warp_inputs", "mre_warp_inputs.hip", []), ("api", "mre_api.cpp", []),
+             ("warp", "mre_warp.hip", []), ("warp_inputs", "mre_warp_inputs.hip", []),
+             ("correlate", "mre_correlate.hip", []), ("api", "mre_api.cpp", []),
              ("sched", "mre_sched.cpp", []), ("model", "mre_model.cpp", [])]
     procs = [(name, subprocess.Popen(base + flags + ["-c", os.path.join(_CSRC, src), "-o",
                                                      os.path.join(bdir, name + ".o")]))
@@ -200,6 +202,8 @@ def lib() -> C.CDLL:
     L.mre_heightmap.argtypes = [vp, fp, fp, fp, ci, ci, ci, fp, fp, C.c_float, C.c_float, ci, ci, fp, fp, fp, fp]
     L.mre_warp_maps.argtypes = [vp, fp, fp, fp, ci, ci, ci, fp, fp, ci, ci, ci, fp, fp, fp, fp]
     L.mre_warp_inputs.argtypes = [vp, fp, fp, ci, ci, ci, fp, fp, ci, ci, ci, ci, fp, fp, fp, ci, fp]
+    L.mre_correlate_workspace.argtypes = [ci, ci, ci, ci, C.POINTER(sz)]
+    L.mre_correlate.argtypes = [vp, fp, fp, ci, ci, ci, ci, ci, ci, ci, fp, fp, fp, fp, sz]
     for name in EXPORTS:
         if name not in ("mre_last_error", "mre_stream", "mre_crc32c", "mre_crc32c_combine",
                         "mre_records_workspace_bytes", "mre_varint_unpack_workspace_bytes"):

@@ -1,6 +1,6 @@
-"""Frame labels and training inputs from the camera's images: the torch-facing wrappers of ``mre_seg_labels``
-(include/mre.h, csrc/mre_labels.hip), ``mre_heightmap`` (csrc/mre_heightmap.hip) and ``mre_warp_maps``
-(csrc/mre_warp.hip).
+"""Frame labels, training inputs and the place decision from the camera's images: the torch-facing wrappers of
+``mre_seg_labels`` (include/mre.h, csrc/mre_labels.hip), ``mre_heightmap`` (csrc/mre_heightmap.hip), ``mre_warp_maps``
+(csrc/mre_warp.hip), ``mre_warp_inputs`` (csrc/mre_warp_inputs.hip) and ``mre_correlate`` (csrc/mre_correlate.hip).
 
 ``seg_labels``: for every env and every label of a small id range of a segmentation image it gives what the
 reference's ``props_info`` takes from one (``get_bbox``, tasks/rearrangement.py:254-268: the PASCAL-VOC box of the
@@ -21,6 +21,11 @@ crops around the pick cell (``crop_matrices``), together ``transporter_sample``
 (``Channels``), float32 or bfloat16 -- by ``mre_warp_inputs`` (csrc/mre_warp_inputs.hip) in one launch, and on it
 ``transporter_batch`` (``BatchedRearrangementEnv.transporter_batch``): the perturbed scene, the rotated pick crops and the
 label indices of a Transporter training batch, ready for a convolution.
+
+``correlate``: what consumes the network's output -- a Transporter's place head: every env's scene features
+cross-correlated with its own rotated crop features by ``mre_correlate`` (csrc/mre_correlate.hip, bf16 matrix cores), the
+best (rotation, row, column) per env without the logits ever being written; ``decode_place`` and ``cell_2_world`` turn it
+into cells, rotation bins and world positions (``BatchedRearrangementEnv.transporter_place``).
 
 The kernels are enqueued on torch's current stream; nothing here synchronises.
 """
@@ -685,3 +690,117 @@ def transporter_batch(maps, pick_cells, place_cells, *, seed: int, env_ids, draw
     return TransporterBatch(scene, crops.view((n, n_rotations) + tuple(crops.shape[1:])), pick, place,
                             pick[:, 1] * cols + pick[:, 0], place[:, 1] * cols + place[:, 0], np.zeros(n, np.int64),
                             pert.tries)
+
+
+# ------------------------------------------------------------------------------------------- the place head
+MAX_ROTATIONS, MAX_DEPTH, MAX_CROP = 64, 16, 64   # the limits of mre_correlate
+# logits float32 or bfloat16 [N, R, rows, columns] or None; index int64 [N], the flat (r * rows + y) * columns + x of the
+# largest float32 sum of every env (ties: the lowest), and value float32 [N], that sum; both None when not asked for
+Correlation = collections.namedtuple("Correlation", ["logits", "index", "value"])
+
+
+def _correlate_args(scene, kernels, logits, best):
+    if scene.dim() != 4 or kernels.dim() != 5:
+        raise ValueError("scene must be [N, D, rows, columns] and kernels [N, R, D, crop, crop]")
+    n, depth, h, w = (int(x) for x in scene.shape)
+    rot, crop = int(kernels.shape[1]), int(kernels.shape[3])
+    if tuple(kernels.shape) != (n, rot, depth, crop, crop):
+        raise ValueError("kernels must be [N, R, D, crop, crop] with the N and D of scene")
+    if not (1 <= rot <= MAX_ROTATIONS and 1 <= depth <= MAX_DEPTH and 2 <= crop <= MAX_CROP and crop % 2 == 0):
+        raise ValueError("1 <= R <= 64, 1 <= D <= 16 and an even crop of 2 .. 64")
+    if not (1 <= h <= MAX_MAP and 1 <= w <= MAX_MAP and rot * h * w < 2 ** 31):
+        raise ValueError("1 <= rows, columns <= 4096 and R * rows * columns < 2^31")
+    if logits not in (None, torch.float32, torch.bfloat16):
+        raise ValueError("logits must be None, torch.float32 or torch.bfloat16")
+    if logits is None and not best:
+        raise ValueError("nothing asked for: logits is None and best is False")
+    if kernels.device != scene.device:
+        raise ValueError("scene and kernels must be on one device")
+    return n, rot, depth, h, w, crop
+
+
+def correlate_reference(scene: torch.Tensor, kernels: torch.Tensor, *, logits=None, best: bool = True) -> Correlation:
+    """The statement of ``correlate`` (include/mre.h, mre_correlate) in plain torch, on whatever device and for any
+    strides and dtype: the grouped ``conv2d`` of the zero-padded scene with every env's own kernels in float32 from the
+    given values, cut to the scene's cells; the best cell is the first occurrence of the largest float32 sum (a NaN
+    counts as -inf).  The fallback of ``correlate``.  The order of its float32 additions is the library's, not the
+    kernel's: integer-valued inputs (every partial sum below 2^24) make both exact."""
+    n, rot, depth, h, w, crop = _correlate_args(scene, kernels, logits, best)
+    x = scene.to(torch.float32).reshape(1, n * depth, h, w)
+    k = kernels.to(torch.float32).reshape(n * rot, depth, crop, crop)
+    if n == 0:
+        out = torch.zeros((0, rot, h, w), dtype=torch.float32, device=scene.device)
+    else:
+        out = torch.nn.functional.conv2d(x, k, padding=crop // 2, groups=n)[..., :h, :w].reshape(n, rot, h, w)
+    index = value = None
+    if best:
+        flat = out.reshape(n, rot * h * w)
+        index = torch.where(torch.isnan(flat), torch.full_like(flat, float("-inf")), flat).argmax(dim=1)
+        value = flat.gather(1, index[:, None])[:, 0]
+    return Correlation(None if logits is None else out.to(logits).contiguous(), index, value)
+
+
+def correlate(scene: torch.Tensor, kernels: torch.Tensor, *, logits=None, best: bool = True) -> Correlation:
+    """A Transporter's place head: every env's ``scene`` features [N, D, rows, columns] cross-correlated with that env's
+    own ``kernels`` [N, R, D, crop, crop] (the features of its R rotated crops; crop even, its index crop / 2 the pivot),
+      logit[e, r, y, x] = sum over d, i, j of scene[e, d, y + i - crop/2, x + j - crop/2] * kernels[e, r, d, i, j]
+    with cells outside the scene counting as 0, and per env the largest sum with its flat index -- a ``Correlation``.
+    ``logits`` names the dtype the sums are written in (None: they are never written; 4096 envs x 36 x 320 x 240 of them
+    are 45 GB); ``best`` asks for ``index`` and ``value``, which are taken from the float32 sums and are the same bits
+    whether or not the logits are written.  ``decode_place`` turns ``index`` into cells and rotation bins.
+
+    Contiguous CUDA bfloat16 inputs are one call of ``mre_correlate`` (csrc/mre_correlate.hip, bf16 matrix cores, float32
+    accumulation) on torch's current stream with a ``torch.empty`` workspace, without a synchronise; anything else is
+    computed by ``correlate_reference``.  No autograd."""
+    n, rot, depth, h, w, crop = _correlate_args(scene, kernels, logits, best)
+    on_device = all(t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() for t in (scene, kernels))
+    if not on_device:
+        return correlate_reference(scene, kernels, logits=logits, best=best)
+    dev = scene.device
+    out = None if logits is None else torch.empty((n, rot, h, w), dtype=logits, device=dev)
+    index = torch.empty((n,), dtype=torch.int64, device=dev) if best else None
+    value = torch.empty((n,), dtype=torch.float32, device=dev) if best else None
+    if n:
+        L = _lib.lib()
+        nbytes = C.c_size_t(0)
+        _lib.check(L.mre_correlate_workspace(n, rot, h, w, C.byref(nbytes)), "mre_correlate_workspace")
+        work = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(L.mre_correlate(
+                stream, scene.detach().data_ptr(), kernels.detach().data_ptr(), n, rot, depth, h, w, crop,
+                _DTYPES[logits if logits is not None else torch.float32], None if out is None else out.data_ptr(),
+                index.data_ptr() if best else None, value.data_ptr() if best else None, work.data_ptr(), nbytes.value),
+                "mre_correlate")
+    return Correlation(out, index, value)
+
+
+def decode_place(index, shape, n_rotations: int):
+    """The flat indices of ``correlate`` [N] over ``shape`` = (rows, columns) as (cells int64 [N, 2] (column, row), rotation
+    bins int64 [N], angles float64 [N] = 2 pi bin / n_rotations, the turn of ``crop_matrices``' sample ``bin``).  Torch
+    tensors for a tensor, numpy arrays for anything else."""
+    rows, cols = int(shape[0]), int(shape[1])
+    is_tensor = isinstance(index, torch.Tensor)
+    idx = index.to(torch.int64) if is_tensor else torch.as_tensor(np.asarray(index, np.int64))
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_rotations * rows * cols):
+        raise ValueError("an index outside n_rotations * rows * columns")
+    bins = torch.div(idx, rows * cols, rounding_mode="floor")
+    rest = idx - bins * (rows * cols)
+    row = torch.div(rest, cols, rounding_mode="floor")
+    cells = torch.stack([rest - row * cols, row], dim=-1)
+    angles = bins.to(torch.float64) * (2.0 * np.pi / n_rotations)
+    if is_tensor:
+        return cells, bins, angles
+    return cells.numpy(), bins.numpy(), angles.numpy()
+
+
+def cell_2_world(cells, bounds, cell: float):
+    """World (x, y) of the centres of ``cells`` [..., 2] (column, row) of the map of ``bounds`` at ``cell``:
+    lo + (c + 0.5) * cell in float64 -- the inverse of ``world_2_cell`` up to the cell.  A torch tensor for a tensor, a
+    numpy array for anything else."""
+    lo, _, _ = _grid(bounds, cell)
+    is_tensor = isinstance(cells, torch.Tensor)
+    c = (cells if is_tensor else torch.as_tensor(np.asarray(cells))).to(torch.float64)
+    lo2 = torch.tensor([float(lo[0]), float(lo[1])], dtype=torch.float64, device=c.device)
+    out = lo2 + (c + 0.5) * float(cell)
+    return out if is_tensor else out.numpy()

@@ -73,6 +73,8 @@ OVERHEAD = "overhead_camera/overhead_camera"
 # This project's choice (the reference has no heightmap).  lo_z must sit below the table: the table's pixels come back
 # from depth a float32 rounding above or below TABLE_TOP_Z, and a lo_z equal to it would cut the plane out of the map.
 HEIGHTMAP_BOUNDS = ((0.2, -0.4, TABLE_TOP_Z - 0.01), (0.8, 0.4, TABLE_TOP_Z + 0.29))
+# what BatchedRearrangementEnv.transporter_place decides for every env
+PlaceDecision = collections.namedtuple("PlaceDecision", ["cells", "rotation", "angle", "xy", "value"])
 
 
 def mat2quat(mat3x3) -> np.ndarray:
@@ -272,6 +274,20 @@ class BatchedRearrangementEnv:
             maps, perception.world_2_cell(pick[:, :3], HEIGHTMAP_BOUNDS, cell),
             perception.world_2_cell(place[:, :3], HEIGHTMAP_BOUNDS, cell), seed=seed, env_ids=self.env_ids, draw=draw,
             n_rotations=n_rotations, crop=crop, channels=channels, dtype=dtype)
+
+    def transporter_place(self, scene_features, crop_features, cell: float = 0.0025):
+        """The place decision of a Transporter's place head for every env, on the device: ``scene_features`` [N, D, rows,
+        columns] (the network's output on ``transporter_batch``'s ``scene``) correlated with ``crop_features`` [N, R, D,
+        crop, crop] (its output on the rotated ``crops``) by ``perception.correlate``, the best cell and rotation bin of
+        every env by ``perception.decode_place``, and that cell's centre in the world by ``perception.cell_2_world`` on
+        ``HEIGHTMAP_BOUNDS`` at ``cell`` metres per cell.  A ``PlaceDecision``: cells int64 [N, 2] (column, row), rotation
+        bins int64 [N], angles float64 [N] (radians), xy float64 [N, 2] and the values float32 [N], on the features'
+        device.  No logits are written and no state of the env changes."""
+        rows, cols = int(scene_features.shape[2]), int(scene_features.shape[3])
+        n_rotations = int(crop_features.shape[1])
+        best = perception.correlate(scene_features, crop_features)
+        cells, bins, angles = perception.decode_place(best.index, (rows, cols), n_rotations)
+        return PlaceDecision(cells, bins, angles, perception.cell_2_world(cells, HEIGHTMAP_BOUNDS, cell), best.value)
 
     def _compute_observation(self):
         if not self.render_observations:
