@@ -590,50 +590,67 @@ extern "C" int mre_heightmap(void* stream, const float* depth, const uint8_t* rg
   return MRE_OK;
 }
 
+// A base (or null) and a length in bytes.  Whether a range of `outs` overlaps one of `ins`; a null or empty range
+// overlaps nothing.  The callers' lengths cannot overflow: they state why.
+typedef std::pair<const void*, size_t> ByteRange;
+template <size_t I, size_t O>
+static bool ranges_overlap(const ByteRange (&ins)[I], const ByteRange (&outs)[O]) {
+  for (const auto& o : outs)
+    for (const auto& i : ins) {
+      if (!o.first || !i.first || !o.second || !i.second) continue;
+      const uintptr_t o0 = (uintptr_t)o.first, i0 = (uintptr_t)i.first;
+      if (o0 < i0 + i.second && i0 < o0 + o.second) return true;
+    }
+  return false;
+}
+
+// ---- what mre_warp_maps and mre_warp_inputs gather from (csrc/mre_warp_gather.h): the checks on the arguments they
+// share, in the name `w` of the entry point, and those arguments as the kernels read them
+static int warp_source(const std::string& w, const float* hmap, const uint8_t* cmap, int n, int in_h, int in_w,
+                       const int32_t* index, const float* mats, int samples, int out_h, int out_w, WarpSource* s) {
+  const int lim = (int)WP_MAX_DIM;
+  if (n < 0 || samples < 0) return fail(MRE_ERR_ARG, w + ": n >= 0 and samples >= 0");
+  if (in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || in_h > lim || in_w > lim || out_h > lim || out_w > lim)
+    return fail(MRE_ERR_ARG, w + ": 1 <= in_h, in_w, out_h, out_w <= 4096");
+  if (!hmap || !mats) return fail(MRE_ERR_ARG, w + ": null hmap or mats");
+  if (((uintptr_t)hmap & 3) || ((uintptr_t)mats & 3) || ((uintptr_t)index & 3))
+    return fail(MRE_ERR_ARG, w + ": hmap, mats and index must be 4-byte aligned");
+  if (!index && samples > n) return fail(MRE_ERR_ARG, w + ": more samples than maps and no index");
+  s->hmap = hmap; s->cmap = cmap; s->index = index; s->mats = mats;
+  s->n = (uint32_t)n; s->in_h = (uint32_t)in_h; s->in_w = (uint32_t)in_w;
+  s->samples = (uint32_t)samples; s->out_h = (uint32_t)out_h; s->out_w = (uint32_t)out_w;
+  s->tiles_x = (s->out_w + WP_TILE_W - 1) / WP_TILE_W; s->tiles_y = (s->out_h + WP_TILE_H - 1) / WP_TILE_H;
+  return MRE_OK;
+}
+
 // ---- warped and cropped maps on the device (csrc/mre_warp.hip): a nearest-neighbour affine gather of the three maps
 extern "C" int mre_warp_maps(void* stream, const float* hmap, const uint8_t* cmap, const uint8_t* smap, int n, int in_h,
                              int in_w, const int32_t* index, const float* mats, int samples, int out_h, int out_w,
                              float* out_h_, uint8_t* out_c, uint8_t* out_s, int32_t* from) {
   const std::string w("mre_warp_maps");
-  const int lim = (int)WP_MAX_DIM;
-  if (n < 0 || samples < 0) return fail(MRE_ERR_ARG, w + ": n >= 0 and samples >= 0");
-  if (in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || in_h > lim || in_w > lim || out_h > lim || out_w > lim)
-    return fail(MRE_ERR_ARG, w + ": 1 <= in_h, in_w, out_h, out_w <= 4096");
-  if (!hmap || !mats || !out_h_) return fail(MRE_ERR_ARG, w + ": null hmap, mats or height output");
+  WarpArgs a;
+  memset(&a, 0, sizeof(a));
+  if (const int rc = warp_source(w, hmap, cmap, n, in_h, in_w, index, mats, samples, out_h, out_w, &a.source)) return rc;
+  if (!out_h_) return fail(MRE_ERR_ARG, w + ": null height output");
   if ((cmap == nullptr) != (out_c == nullptr)) return fail(MRE_ERR_ARG, w + ": cmap and its output go together");
   if ((smap == nullptr) != (out_s == nullptr)) return fail(MRE_ERR_ARG, w + ": smap and its output go together");
-  if (((uintptr_t)hmap & 3) || ((uintptr_t)mats & 3) || ((uintptr_t)out_h_ & 3) || ((uintptr_t)from & 3) ||
-      ((uintptr_t)index & 3))
-    return fail(MRE_ERR_ARG, w + ": hmap, mats, index, the height output and from must be 4-byte aligned");
-  if (!index && samples > n) return fail(MRE_ERR_ARG, w + ": more samples than maps and no index");
+  if (((uintptr_t)out_h_ & 3) || ((uintptr_t)from & 3))
+    return fail(MRE_ERR_ARG, w + ": the height output and from must be 4-byte aligned");
   // no output byte range may overlap an input byte range (n, samples <= 2^31 and maps <= 2^24 cells: no overflow)
   const size_t in_cells = (size_t)n * in_h * in_w, out_cells = (size_t)samples * out_h * out_w;
-  const std::pair<const void*, size_t> ins[5] = {{hmap, 4 * in_cells}, {cmap, 3 * in_cells}, {smap, in_cells},
-                                                 {index, 4 * (size_t)samples}, {mats, 24 * (size_t)samples}};
-  const std::pair<const void*, size_t> outs[4] = {{out_h_, 4 * out_cells}, {out_c, 3 * out_cells}, {out_s, out_cells},
-                                                  {from, 4 * out_cells}};
-  for (const auto& o : outs)
-    for (const auto& i : ins) {
-      if (!o.first || !i.first || !o.second || !i.second) continue;
-      const uintptr_t o0 = (uintptr_t)o.first, i0 = (uintptr_t)i.first;
-      if (o0 < i0 + i.second && i0 < o0 + o.second)
-        return fail(MRE_ERR_ARG, w + ": an output overlaps an input");
-    }
+  const ByteRange ins[5] = {{hmap, 4 * in_cells}, {cmap, 3 * in_cells}, {smap, in_cells},
+                            {index, 4 * (size_t)samples}, {mats, 24 * (size_t)samples}};
+  const ByteRange outs[4] = {{out_h_, 4 * out_cells}, {out_c, 3 * out_cells}, {out_s, out_cells}, {from, 4 * out_cells}};
+  if (ranges_overlap(ins, outs)) return fail(MRE_ERR_ARG, w + ": an output overlaps an input");
   if (n == 0 || samples == 0) return MRE_OK;
   if (!is_device_ptr(hmap) || !is_device_ptr(mats) || !is_device_ptr(out_h_) || (index && !is_device_ptr(index)) ||
       (cmap && (!is_device_ptr(cmap) || !is_device_ptr(out_c))) ||
       (smap && (!is_device_ptr(smap) || !is_device_ptr(out_s))) || (from && !is_device_ptr(from)))
     return fail(MRE_ERR_ARG, w + ": the maps, index, mats and the outputs must be device pointers");
-  WarpArgs a;
-  memset(&a, 0, sizeof(a));
-  a.hmap = hmap; a.cmap = cmap; a.smap = smap; a.index = index; a.mats = mats;
-  a.n = (uint32_t)n; a.in_h = (uint32_t)in_h; a.in_w = (uint32_t)in_w;
-  a.samples = (uint32_t)samples; a.out_h = (uint32_t)out_h; a.out_w = (uint32_t)out_w;
-  a.tiles_x = (a.out_w + WP_TILE_W - 1) / WP_TILE_W; a.tiles_y = (a.out_h + WP_TILE_H - 1) / WP_TILE_H;
   // the wide stores: 4 cells of a row at once need the width a multiple of 4 and bases aligned to what a lane stores
   a.vec = (out_w % 4 == 0 && !((uintptr_t)out_h_ & 15) && !((uintptr_t)from & 15) && !((uintptr_t)out_c & 3) &&
            !((uintptr_t)out_s & 3)) ? 1u : 0u;
-  a.out_h_ = out_h_; a.out_c = out_c; a.out_s = out_s; a.from = from;
+  a.smap = smap; a.out_h_ = out_h_; a.out_c = out_c; a.out_s = out_s; a.from = from;
   mre_launch_warp_maps(&a, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
@@ -645,14 +662,10 @@ extern "C" int mre_warp_inputs(void* stream, const float* hmap, const uint8_t* c
                                const int32_t* chan_src, const float* chan_scale, const float* chan_bias, int dtype,
                                void* out) {
   const std::string w("mre_warp_inputs");
-  const int lim = (int)WP_MAX_DIM;
-  if (n < 0 || samples < 0) return fail(MRE_ERR_ARG, w + ": n >= 0 and samples >= 0");
-  if (in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || in_h > lim || in_w > lim || out_h > lim || out_w > lim)
-    return fail(MRE_ERR_ARG, w + ": 1 <= in_h, in_w, out_h, out_w <= 4096");
-  if (!hmap || !mats || !out) return fail(MRE_ERR_ARG, w + ": null hmap, mats or out");
-  if (((uintptr_t)hmap & 3) || ((uintptr_t)mats & 3) || ((uintptr_t)index & 3))
-    return fail(MRE_ERR_ARG, w + ": hmap, mats and index must be 4-byte aligned");
-  if (!index && samples > n) return fail(MRE_ERR_ARG, w + ": more samples than maps and no index");
+  WarpInputArgs a;
+  memset(&a, 0, sizeof(a));
+  if (const int rc = warp_source(w, hmap, cmap, n, in_h, in_w, index, mats, samples, out_h, out_w, &a.source)) return rc;
+  if (!out) return fail(MRE_ERR_ARG, w + ": null out");
   if (channels < 1 || channels > WI_MAX_CHANNELS) return fail(MRE_ERR_ARG, w + ": 1 <= channels <= 8");
   if (!chan_src || !chan_scale || !chan_bias) return fail(MRE_ERR_ARG, w + ": null chan_src, chan_scale or chan_bias");
   bool colour = false;
@@ -670,23 +683,15 @@ extern "C" int mre_warp_inputs(void* stream, const float* hmap, const uint8_t* c
   // out may overlap no input byte range (samples <= 2^31, 8 channels, maps <= 2^24 cells, 4 B: below 2^60)
   const size_t in_cells = (size_t)n * in_h * in_w;
   const size_t out_bytes = (size_t)samples * channels * out_h * out_w * esize;
-  const std::pair<const void*, size_t> ins[4] = {{hmap, 4 * in_cells}, {cmap, 3 * in_cells},
-                                                 {index, 4 * (size_t)samples}, {mats, 24 * (size_t)samples}};
-  for (const auto& i : ins) {
-    if (!i.first || !i.second || !out_bytes) continue;
-    const uintptr_t o0 = (uintptr_t)out, i0 = (uintptr_t)i.first;
-    if (o0 < i0 + i.second && i0 < o0 + out_bytes) return fail(MRE_ERR_ARG, w + ": out overlaps an input");
-  }
+  const ByteRange ins[4] = {{hmap, 4 * in_cells}, {cmap, 3 * in_cells}, {index, 4 * (size_t)samples},
+                            {mats, 24 * (size_t)samples}};
+  const ByteRange outs[1] = {{out, out_bytes}};
+  if (ranges_overlap(ins, outs)) return fail(MRE_ERR_ARG, w + ": out overlaps an input");
   if (n == 0 || samples == 0) return MRE_OK;
   if (!is_device_ptr(hmap) || !is_device_ptr(mats) || !is_device_ptr(out) || (index && !is_device_ptr(index)) ||
       (colour && !is_device_ptr(cmap)))
     return fail(MRE_ERR_ARG, w + ": the maps, index, mats and out must be device pointers");
-  WarpInputArgs a;
-  memset(&a, 0, sizeof(a));
-  a.hmap = hmap; a.cmap = colour ? cmap : nullptr; a.index = index; a.mats = mats;
-  a.n = (uint32_t)n; a.in_h = (uint32_t)in_h; a.in_w = (uint32_t)in_w;
-  a.samples = (uint32_t)samples; a.out_h = (uint32_t)out_h; a.out_w = (uint32_t)out_w;
-  a.tiles_x = (a.out_w + WP_TILE_W - 1) / WP_TILE_W; a.tiles_y = (a.out_h + WP_TILE_H - 1) / WP_TILE_H;
+  if (!colour) a.source.cmap = nullptr;   // given, but no channel reads it
   // the wide stores: a lane's 4 cells of a channel at once need the width a multiple of 4 (every row and every channel
   // plane then starts at a multiple of 4 elements) and out aligned to those 4 elements
   a.vec = (out_w % 4 == 0 && ((size_t)out_h * out_w) % 4 == 0 && !((uintptr_t)out & (4 * esize - 1))) ? 1u : 0u;
@@ -745,16 +750,10 @@ extern "C" int mre_correlate(void* stream, const uint16_t* scene, const uint16_t
     return fail(MRE_ERR_ARG, wh + ": workspace must be non-NULL, 16-byte aligned and as large as mre_correlate_workspace says");
   // no output or workspace byte range may overlap an input (n < 2^31, 64 x 16 x 64 x 64 x 2 B per env: below 2^54)
   const size_t cells = (size_t)h * w;
-  const std::pair<const void*, size_t> ins[2] = {{scene, 2 * (size_t)n * depth * cells},
-                                                 {kern, 2 * (size_t)n * rotations * depth * crop * crop}};
-  const std::pair<const void*, size_t> outs[4] = {{logits, esize * (size_t)n * rotations * cells}, {best_index, 8 * (size_t)n},
-                                                  {best_value, 4 * (size_t)n}, {workspace, need}};
-  for (const auto& o : outs)
-    for (const auto& i : ins) {
-      if (!o.first || !o.second || !i.second) continue;
-      const uintptr_t o0 = (uintptr_t)o.first, i0 = (uintptr_t)i.first;
-      if (o0 < i0 + i.second && i0 < o0 + o.second) return fail(MRE_ERR_ARG, wh + ": an output or the workspace overlaps an input");
-    }
+  const ByteRange ins[2] = {{scene, 2 * (size_t)n * depth * cells}, {kern, 2 * (size_t)n * rotations * depth * crop * crop}};
+  const ByteRange outs[4] = {{logits, esize * (size_t)n * rotations * cells}, {best_index, 8 * (size_t)n},
+                             {best_value, 4 * (size_t)n}, {workspace, need}};
+  if (ranges_overlap(ins, outs)) return fail(MRE_ERR_ARG, wh + ": an output or the workspace overlaps an input");
   if (n == 0) return MRE_OK;
   if (!is_device_ptr(scene) || !is_device_ptr(kern) || !is_device_ptr(workspace) || (logits && !is_device_ptr(logits)) ||
       (best_index && (!is_device_ptr(best_index) || !is_device_ptr(best_value))))

@@ -15,14 +15,20 @@ constexpr int WP_TILE_W = 64;                // columns of it: 16 lanes x 4 cons
 constexpr uint32_t WP_MAX_DIM = 4096;        // rows / columns of a source or output map at most
 constexpr uint32_t WP_MAX_GRID = 1u << 20;   // workgroups of a launch at most; work items beyond are looped over
 
-struct WarpArgs {
+// What the map warp and the network inputs (csrc/mre_warp_inputs.h) gather from, and the shape of what they gather into:
+// filled once by the C ABI, read by the one statement of the gather (csrc/mre_warp_gather.h).
+struct WarpSource {
   const float* hmap;     // [n][in_h][in_w]
   const uint8_t* cmap;   // [n][in_h][in_w][3] or null
-  const uint8_t* smap;   // [n][in_h][in_w] or null
   const int32_t* index;  // [samples] or null (sample s reads map s)
   const float* mats;     // [samples][6]
   uint32_t n, in_h, in_w;
   uint32_t samples, out_h, out_w, tiles_x, tiles_y;
+};
+
+struct WarpArgs {
+  WarpSource source;
+  const uint8_t* smap;   // [n][in_h][in_w] or null
   uint32_t vec;          // out_w % 4 == 0 and every output base aligned for the wide stores
   float* out_h_;         // [samples][out_h][out_w]
   uint8_t* out_c;        // [samples][out_h][out_w][3] or null (with cmap)

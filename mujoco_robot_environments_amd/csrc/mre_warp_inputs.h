@@ -16,12 +16,7 @@ constexpr uint32_t WI_SRC_HEIGHT = 3;   // MRE_SRC_HEIGHT (include/mre.h); 0, 1,
 
 // The channel table travels by value: it is the same in every lane, so it lives in SGPRs.
 struct WarpInputArgs {
-  const float* hmap;     // [n][in_h][in_w]
-  const uint8_t* cmap;   // [n][in_h][in_w][3]; read only when a colour source is named
-  const int32_t* index;  // [samples] or null (sample s reads map s)
-  const float* mats;     // [samples][6]
-  uint32_t n, in_h, in_w;
-  uint32_t samples, out_h, out_w, tiles_x, tiles_y;
+  WarpSource source;     // cmap: read only when a colour source is named, null otherwise
   uint32_t vec;          // out_w % 4 == 0 and out aligned for a lane's 4 elements of every channel plane
   uint32_t colour;       // a channel reads a colour byte
   uint32_t bf16;         // out holds bfloat16, else float32

@@ -21,10 +21,10 @@ _HEADERS = ["mre_dev.h", "mre_math.h", "mre_collide.h", "mre_solver.h", "mre_new
 # The model builder and the launch scheduler are host code like mre_api.cpp: they decide what is uploaded and how
 # launches are issued, not what a launch executes.  The frame-label kernel (mre_labels.hip) reads rendered images and is
 # launched by neither the step nor the camera, and so are the heightmap kernel (mre_heightmap.hip), the map warp
-# (mre_warp.hip), the network inputs gathered like it (mre_warp_inputs.hip) and the place head's correlation
-# (mre_correlate.hip).
+# (mre_warp.hip) and the network inputs (mre_warp_inputs.hip) with the gather they share (mre_warp_gather.h), and the
+# place head's correlation (mre_correlate.hip).
 _UNHASHED_SOURCES = ["mre_records.hip", "mre_records.h", "mre_labels.hip", "mre_labels.h", "mre_heightmap.hip", "mre_heightmap.h",
-                     "mre_heightmap_point.h", "mre_warp.hip", "mre_warp.h", "mre_warp_point.h", "mre_warp_inputs.hip", "mre_warp_inputs.h",
+                     "mre_heightmap_point.h", "mre_warp.hip", "mre_warp.h", "mre_warp_point.h", "mre_warp_gather.h", "mre_warp_inputs.hip", "mre_warp_inputs.h",
                      "mre_warp_input_point.h", "mre_correlate.hip", "mre_correlate.h", "mre_model.cpp", "mre_model.h", "mre_sched.cpp", "mre_env.h",
                      "mre_policy.h", "mre_launch.h"]
 _LIB: Optional[C.CDLL] = None

@@ -32,6 +32,7 @@ The kernels are enqueued on torch's current stream; nothing here synchronises.
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes as C
 from typing import Optional
 
@@ -47,6 +48,20 @@ MAX_IDS = 8          # labels of one mre_seg_labels call
 # box int64 [N, nid, (xmin, ymin, xmax, ymax)] (-1 where the label is absent), count int64 [N, nid],
 # sum_xy int64 [N, nid, (sum of columns, sum of rows)], zmin float32 [N, nid] (+inf where absent) or None
 SegLabels = collections.namedtuple("SegLabels", ["box", "count", "sum_xy", "zmin"])
+
+
+@contextlib.contextmanager
+def _stream_on(dev):
+    """torch's current stream on ``dev`` as the C ABI takes it, with ``dev`` the current device while a kernel is enqueued."""
+    with torch.cuda.device(dev):
+        yield C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _maps_on_device(height, *companions) -> bool:
+    """What the warp kernels read in place: a contiguous CUDA float32 ``height`` with contiguous uint8 companions (or None)
+    on its device."""
+    return height.is_cuda and height.dtype == torch.float32 and height.is_contiguous() and all(
+        x is None or (x.device == height.device and x.dtype == torch.uint8 and x.is_contiguous()) for x in companions)
 
 
 def seg_labels_reference(seg: torch.Tensor, depth: Optional[torch.Tensor] = None, id0: int = PROP_GEOM_ID0,
@@ -104,8 +119,7 @@ def seg_labels(seg: torch.Tensor, depth: Optional[torch.Tensor] = None, id0: int
     stats = torch.empty((n, nid, 7), dtype=torch.int64, device=dev)
     zmin = None if depth is None else torch.empty((n, nid), dtype=torch.float32, device=dev)
     if n:
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with _stream_on(dev) as stream:
             _lib.check(_lib.lib().mre_seg_labels(stream, seg.data_ptr(), None if depth is None else depth.data_ptr(),
                                                  n, h, w, int(id0), int(nid), stats.data_ptr(),
                                                  None if zmin is None else zmin.data_ptr()), "mre_seg_labels")
@@ -252,8 +266,7 @@ def heightmap(depth: torch.Tensor, rgb: Optional[torch.Tensor] = None, seg: Opti
     if n:
         ptr = lambda t: None if t is None else t.data_ptr()
         b = np.ascontiguousarray(np.concatenate([lo, hi]), np.float32)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with _stream_on(dev) as stream:
             _lib.check(_lib.lib().mre_heightmap(stream, depth.data_ptr(), ptr(rgb), ptr(seg), n, h, w, cam.ctypes.data,
                                                 b.ctypes.data, float(inv_cell), float(np.float32(max_depth)), out_h, out_w,
                                                 height.data_ptr(), ptr(colour), ptr(smap), src.data_ptr()), "mre_heightmap")
@@ -467,9 +480,7 @@ def warp_maps(height: torch.Tensor, colour: Optional[torch.Tensor] = None, seg: 
     one launch of ``mre_warp_maps`` on torch's current stream, without a synchronise; anything else is computed by
     ``warp_maps_reference`` with the same return values."""
     dev = height.device
-    on_device = height.is_cuda and height.dtype == torch.float32 and height.is_contiguous() and all(
-        x is None or (x.device == dev and x.dtype == torch.uint8 and x.is_contiguous()) for x in (colour, seg))
-    if not on_device:
+    if not _maps_on_device(height, colour, seg):
         return warp_maps_reference(height, colour, seg, mats=mats, index=index, out_shape=out_shape,
                                    with_source=with_source)
     mats, index = _as_mats(mats, dev), _as_index(index, dev)
@@ -480,8 +491,7 @@ def warp_maps(height: torch.Tensor, colour: Optional[torch.Tensor] = None, seg: 
     source = torch.empty((samples, out_h, out_w), dtype=torch.int32, device=dev) if with_source else None
     if n and samples:
         ptr = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with _stream_on(dev) as stream:
             _lib.check(_lib.lib().mre_warp_maps(stream, height.data_ptr(), ptr(colour), ptr(seg), n, in_h, in_w, ptr(index),
                                                 mats.data_ptr(), samples, out_h, out_w, out_hz.data_ptr(), ptr(out_c),
                                                 ptr(out_s), ptr(source)), "mre_warp_maps")
@@ -637,9 +647,7 @@ def warp_inputs(height: torch.Tensor, colour: Optional[torch.Tensor] = None, *, 
     computed by ``warp_inputs_reference`` with the same result."""
     channels = _input_args(colour, channels, dtype)
     dev = height.device
-    on_device = height.is_cuda and height.dtype == torch.float32 and height.is_contiguous() and (
-        colour is None or (colour.device == dev and colour.dtype == torch.uint8 and colour.is_contiguous()))
-    if not on_device:
+    if not _maps_on_device(height, colour):
         return warp_inputs_reference(height, colour, mats=mats, index=index, out_shape=out_shape, channels=channels,
                                      dtype=dtype)
     mats, index = _as_mats(mats, dev), _as_index(index, dev)
@@ -649,8 +657,7 @@ def warp_inputs(height: torch.Tensor, colour: Optional[torch.Tensor] = None, *, 
     if n and samples:
         src = (C.c_int32 * nc)(*channels.sources)
         scale, bias = (C.c_float * nc)(*channels.scales), (C.c_float * nc)(*channels.biases)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with _stream_on(dev) as stream:
             _lib.check(_lib.lib().mre_warp_inputs(
                 stream, height.data_ptr(), colour.data_ptr() if channels.uses_colour else None, n, in_h, in_w,
                 None if index is None else index.data_ptr(), mats.data_ptr(), samples, out_h, out_w, nc,
@@ -765,8 +772,7 @@ def correlate(scene: torch.Tensor, kernels: torch.Tensor, *, logits=None, best: 
         nbytes = C.c_size_t(0)
         _lib.check(L.mre_correlate_workspace(n, rot, h, w, C.byref(nbytes)), "mre_correlate_workspace")
         work = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with _stream_on(dev) as stream:
             _lib.check(L.mre_correlate(
                 stream, scene.detach().data_ptr(), kernels.detach().data_ptr(), n, rot, depth, h, w, crop,
                 _DTYPES[logits if logits is not None else torch.float32], None if out is None else out.data_ptr(),

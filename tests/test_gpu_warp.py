@@ -27,7 +27,7 @@ from tests import warp_cases as WC
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-GUARD_H, GUARD_C, GUARD_S = 777.0, 251, 250       # no source map holds these (warp_cases.source_maps)
+GUARD_H = WC.GUARDS["hmap"]                       # no source map holds the guards (warp_cases.source_maps)
 SENT_H, SENT_B, SENT_I = -77.0, 253, -77          # nor does any result
 
 
@@ -45,24 +45,8 @@ def _call(a):
     return rc
 
 
-_GUARDED = {}
-
-
 def _guarded_maps(c):
-    """The source maps of a case on the device, one element into allocations filled with the guard values, with a whole
-    map of guards before and after them; shared by the cases of a shape.  {name: (buffer, view)}."""
-    key = (c["n"], c["in_h"], c["in_w"])
-    if key not in _GUARDED:
-        hw = c["in_h"] * c["in_w"]
-        out = {}
-        for name, fill, dtype, per in (("hmap", GUARD_H, torch.float32, 1), ("cmap", GUARD_C, torch.uint8, 3),
-                                       ("smap", GUARD_S, torch.uint8, 1)):
-            buf = torch.full(((c["n"] + 2) * hw * per + 2,), fill, dtype=dtype, device=DEV)
-            view = buf[hw * per + 1: hw * per + 1 + c["n"] * hw * per]
-            view.copy_(torch.from_numpy(c[name].copy()).to(DEV).reshape(-1))
-            out[name] = (buf, view)
-        _GUARDED[key] = out
-    return _GUARDED[key]
+    return WC.guarded_maps(c, ("hmap", "cmap", "smap"), DEV)
 
 
 def _raw(c, colour=True, seg=True, src=True, offset=0):
@@ -95,11 +79,7 @@ def _raw(c, colour=True, seg=True, src=True, offset=0):
         assert np.array_equal(as_bits(got[offset:offset + wanted.size]), as_bits(wanted)), (k,) + what
         rest = np.concatenate([got[:offset], got[offset + wanted.size:]])
         assert (rest == {"out_h_": SENT_H, "src": SENT_I}.get(k, SENT_B)).all(), (k,) + what
-    for name, fill in (("hmap", GUARD_H), ("cmap", GUARD_C), ("smap", GUARD_S)):
-        buf, view = g[name]
-        lead = view.data_ptr() - buf.data_ptr()
-        lead //= buf.element_size()
-        assert (buf[:lead] == fill).all() and (buf[lead + view.numel():] == fill).all(), name
+    WC.assert_guards(g)
 
 
 def _same(r, want, what):

@@ -28,7 +28,7 @@ from tests import warp_input_cases as IC
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-GUARD_H, GUARD_C = 777.0, 251          # no source map holds these (warp_cases.source_maps)
+GUARD_H = WC.GUARDS["hmap"]            # no source map holds the guards (warp_cases.source_maps)
 SENT32, SENT16 = -0x21524111, -0x2153  # the bits 0xDEADBEEF (-6.3e18) and 0xDEAD (-6.2e18): no result is near them
 DTYPES = (torch.float32, torch.bfloat16)
 
@@ -51,23 +51,8 @@ def _call(a):
     return rc
 
 
-_GUARDED = {}
-
-
 def _guarded_maps(c):
-    """The source maps of a case on the device, one element into allocations filled with the guard values, with a whole
-    map of guards before and after them; shared by the cases of a shape.  {name: (buffer, view)}."""
-    key = (c["n"], c["in_h"], c["in_w"], id(c["hmap"]) if c.get("own_maps") else 0)
-    if key not in _GUARDED:
-        hw = c["in_h"] * c["in_w"]
-        out = {}
-        for name, fill, dtype, per in (("hmap", GUARD_H, torch.float32, 1), ("cmap", GUARD_C, torch.uint8, 3)):
-            buf = torch.full(((c["n"] + 2) * hw * per + 2,), fill, dtype=dtype, device=DEV)
-            view = buf[hw * per + 1: hw * per + 1 + c["n"] * hw * per]
-            view.copy_(torch.from_numpy(np.array(c[name])).to(DEV).reshape(-1))
-            out[name] = (buf, view)
-        _GUARDED[key] = (c, out)
-    return _GUARDED[key][1]
+    return WC.guarded_maps(c, ("hmap", "cmap"), DEV)
 
 
 def _bits(t):
@@ -98,10 +83,7 @@ def _raw(c, name, ch, dtype, with_cmap=True, offset=0):
     IC.assert_same_bits(got[offset:offset + total] if bf16 else got[offset:offset + total].view(np.float32), want, what)
     rest = np.concatenate([got[:offset], got[offset + total:]])
     assert (rest == (0xDEAD if bf16 else 0xDEADBEEF)).all(), what
-    for key, fill in (("hmap", GUARD_H), ("cmap", GUARD_C)):
-        b, view = g[key]
-        lead = (view.data_ptr() - b.data_ptr()) // b.element_size()
-        assert (b[:lead] == fill).all() and (b[lead + view.numel():] == fill).all(), key
+    WC.assert_guards(g)
 
 
 def _cases(shape, out):

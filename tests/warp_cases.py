@@ -3,7 +3,8 @@ kernel's per-cell text compiled by g++, the torch fallback) and tests/test_gpu_w
 
 The statement is written with explicit float32 temporaries, one rounding per operation, exactly as the header states it.
 A case is a dict: name, n / in_h / in_w, hmap / cmap / smap (the source maps), mats float32 [S, 6], index int32 [S] or None,
-out = (out_h, out_w).
+out = (out_h, out_w).  `guarded_maps` / `assert_guards` put a case's maps between guard regions on the device for the GPU tests
+of both kernels that gather from them (tests/test_gpu_warp.py, tests/test_gpu_warp_inputs.py).
 """
 import functools
 
@@ -79,6 +80,36 @@ def statement(case, colour=True, seg=True):
         _STATEMENTS[key] = (case, full)
     full = _STATEMENTS[key][1]
     return full[0], full[1] if colour else None, full[2] if seg else None, full[3]
+
+
+GUARDS = {"hmap": 777.0, "cmap": 251, "smap": 250}   # no source map holds these (source_maps)
+_GUARDED = {}
+
+
+def guarded_maps(case, names, device="cuda"):
+    """The source maps `names` of a case on the device, one element into allocations filled with the guard values, with a
+    whole map of guards before and after them; shared by the cases of a shape (a case with `own_maps` has its own).
+    {name: (buffer, view)}."""
+    import torch
+    key = (case["n"], case["in_h"], case["in_w"], id(case["hmap"]) if case.get("own_maps") else 0, tuple(names))
+    if key not in _GUARDED:
+        hw = case["in_h"] * case["in_w"]
+        out = {}
+        for name in names:
+            dtype, per = (torch.float32, 1) if name == "hmap" else (torch.uint8, 3 if name == "cmap" else 1)
+            buf = torch.full(((case["n"] + 2) * hw * per + 2,), GUARDS[name], dtype=dtype, device=device)
+            view = buf[hw * per + 1: hw * per + 1 + case["n"] * hw * per]
+            view.copy_(torch.from_numpy(np.array(case[name])).to(device).reshape(-1))
+            out[name] = (buf, view)
+        _GUARDED[key] = (case, out)   # the case is kept: its id names the entry
+    return _GUARDED[key][1]
+
+
+def assert_guards(guarded):
+    """No element before or behind the maps of `guarded_maps` has changed."""
+    for name, (buf, view) in guarded.items():
+        lead = (view.data_ptr() - buf.data_ptr()) // buf.element_size()
+        assert (buf[:lead] == GUARDS[name]).all() and (buf[lead + view.numel():] == GUARDS[name]).all(), name
 
 
 @functools.lru_cache(maxsize=None)
