@@ -1,5 +1,5 @@
-// mre_api.cpp -- host side of the C ABI declared in include/mre.h.
-// Owns the device buffers and the HIP stream of a batch of environments,
+// mre_api.cpp -- the entry points of the C ABI (include/mre.h) that work on an mre_env handle; those that take a stream
+// and no handle are mre_stream_api.cpp's.  Owns the device buffers and the HIP stream of a batch of environments,
 // uploads the fp32 DevModel that mre_model.cpp builds from the model blob, and
 // enqueues kernels; how stepping launches are issued is mre_sched.cpp's.  No torch types; plain pointers and sizes only.
 #include <hip/hip_runtime.h>
@@ -13,14 +13,8 @@
 #include <vector>
 
 #include "mre_env.h"
-#include "mre_labels.h"
-#include "mre_heightmap.h"
-#include "mre_warp.h"
-#include "mre_warp_inputs.h"
-#include "mre_correlate.h"
 #include "mre_launch.h"
 #include "mre_model.h"
-#include "mre_records.h"
 
 using namespace mre;
 
@@ -235,11 +229,6 @@ extern "C" int mre_reset(mre_env* e, const uint8_t* mask) {
 
 // ---- batched overhead camera (csrc/mre_render.hip)
 static void fill_args(mre_env* e, StepArgs& a);
-static bool is_device_ptr(const void* p) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return at.type == hipMemoryTypeDevice;
-}
 
 extern "C" int mre_set_render_colours(mre_env* e, const uint8_t* prop_rgb, const float* geom_rgb) {
   if (!e) return fail(MRE_ERR_ARG, "null handle");
@@ -364,414 +353,6 @@ extern "C" int mre_set_fallback(mre_env* e, int mode) {
     e->h_large.assign((size_t)e->N, mode == 2 ? 1 : 0);
     HIPCHK(hipMemcpy(e->d_large, e->h_large.data(), (size_t)e->N, hipMemcpyHostToDevice));
   }
-  return MRE_OK;
-}
-
-// CRC-32C (Castagnoli) of a host buffer: the checksum of TFRecord framing (dataset.py writes the
-// reference's RLDS episodes, transporter_network_data_generation.py:56-111); slicing-by-8 tables
-namespace {
-struct Crc32cTables {   // built once, by the C++ runtime's thread-safe initialisation of the function-local static
-  uint32_t T[8][256];
-  Crc32cTables() {
-    for (uint32_t i = 0; i < 256; i++) {
-      uint32_t c = i;
-      for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((c & 1u) ? 0x82F63B78u : 0u);
-      T[0][i] = c;
-    }
-    for (int k = 1; k < 8; k++)
-      for (uint32_t i = 0; i < 256; i++) T[k][i] = (T[k - 1][i] >> 8) ^ T[0][T[k - 1][i] & 0xFFu];
-  }
-};
-}  // namespace
-extern "C" uint32_t mre_crc32c(const void* data, size_t n) {
-  static const Crc32cTables tables;
-  const uint32_t (*T)[256] = tables.T;
-  const unsigned char* p = (const unsigned char*)data;
-  uint32_t crc = 0xFFFFFFFFu;
-  while (n >= 8) {
-    uint32_t lo, hi;
-    memcpy(&lo, p, 4); memcpy(&hi, p + 4, 4);
-    lo ^= crc;
-    crc = T[7][lo & 0xFF] ^ T[6][(lo >> 8) & 0xFF] ^ T[5][(lo >> 16) & 0xFF] ^ T[4][lo >> 24] ^
-          T[3][hi & 0xFF] ^ T[2][(hi >> 8) & 0xFF] ^ T[1][(hi >> 16) & 0xFF] ^ T[0][hi >> 24];
-    p += 8; n -= 8;
-  }
-  while (n--) crc = T[0][(crc ^ *p++) & 0xFFu] ^ (crc >> 8);
-  return crc ^ 0xFFFFFFFFu;
-}
-
-// ---- episode records on the device (csrc/mre_records.hip): packed varints and CRC-32C of byte rows
-extern "C" uint32_t mre_crc32c_combine(uint32_t crc_a, uint32_t crc_b, size_t len_b) {
-  return mre_rec_crc32c_combine(crc_a, crc_b, len_b);
-}
-
-static size_t rec_segments(size_t row_bytes) { return (row_bytes + REC_PACK_SEG - 1) / REC_PACK_SEG; }
-
-extern "C" size_t mre_records_workspace_bytes(int rows, size_t row_bytes) {
-  if (rows <= 0 || row_bytes == 0 || row_bytes > REC_MAX_ROW_BYTES) return 0;
-  return 2 * (size_t)rows * rec_segments(row_bytes) * sizeof(uint32_t);   // segment offsets + segment CRCs
-}
-
-// the checks the two calls share; fills the row interface of RecArgs (nseg for `seg` bytes per segment)
-static int rec_args(const char* who, RecArgs& a, const uint8_t* src, size_t row_stride, size_t row_bytes,
-                    const int32_t* rows_idx, int src_rows, int rows, void* workspace, size_t workspace_bytes, size_t seg) {
-  const std::string w(who);
-  if (!src || rows <= 0 || src_rows <= 0 || row_bytes == 0 || !workspace)
-    return fail(MRE_ERR_ARG, w + ": null argument or empty row set");
-  if (row_bytes > REC_MAX_ROW_BYTES) return fail(MRE_ERR_ARG, w + ": row_bytes above 2^30");
-  if (row_stride < row_bytes && src_rows > 1) return fail(MRE_ERR_ARG, w + ": row_stride below row_bytes");
-  if (!rows_idx && rows > src_rows) return fail(MRE_ERR_ARG, w + ": more rows than the source holds and no index list");
-  const size_t nseg = (row_bytes + seg - 1) / seg;
-  if ((size_t)rows * nseg > 0x7FFFFFFFull) return fail(MRE_ERR_ARG, w + ": rows x segments above 2^31 - 1");
-  if (workspace_bytes < mre_records_workspace_bytes(rows, row_bytes) || ((uintptr_t)workspace & 3))
-    return fail(MRE_ERR_ARG, w + ": workspace smaller than mre_records_workspace_bytes() or not 4-byte aligned");
-  if (!is_device_ptr(src) || !is_device_ptr(workspace) || (rows_idx && !is_device_ptr(rows_idx)))
-    return fail(MRE_ERR_ARG, w + ": src, rows_idx and workspace must be device pointers");
-  memset(&a, 0, sizeof(a));
-  a.src = src; a.stride = row_stride; a.row_bytes = (uint32_t)row_bytes; a.idx = rows_idx;
-  a.src_rows = (uint32_t)src_rows; a.rows = (uint32_t)rows; a.nseg = (uint32_t)nseg;
-  a.segoff = (uint32_t*)workspace;
-  a.segcrc = a.segoff + (size_t)rows * rec_segments(row_bytes);
-  return MRE_OK;
-}
-
-extern "C" int mre_varint_pack_rows(void* stream, const uint8_t* src, size_t row_stride, size_t row_bytes,
-                                    const int32_t* rows_idx, int src_rows, int rows, uint8_t* out, size_t out_capacity,
-                                    int64_t* off, uint32_t* len, uint32_t* crc, void* workspace, size_t workspace_bytes) {
-  RecArgs a;
-  int rc = rec_args("mre_varint_pack_rows", a, src, row_stride, row_bytes, rows_idx, src_rows, rows, workspace,
-                    workspace_bytes, REC_PACK_SEG);
-  if (rc) return rc;
-  if (!off || !len || !is_device_ptr(off) || !is_device_ptr(len) || ((uintptr_t)off & 7) || ((uintptr_t)len & 3))
-    return fail(MRE_ERR_ARG, "mre_varint_pack_rows: off / len must be aligned device pointers");
-  if (out) {
-    // the worst case, not the actual length: the length is only known on the device, and nothing may be written
-    // beyond the caller's buffer whatever the rows hold
-    if (out_capacity / 2 / (size_t)rows < row_bytes)
-      return fail(MRE_ERR_ARG, "mre_varint_pack_rows: out_capacity below the worst case 2 * rows * row_bytes");
-    if (!crc || !is_device_ptr(out) || !is_device_ptr(crc) || ((uintptr_t)crc & 3))
-      return fail(MRE_ERR_ARG, "mre_varint_pack_rows: out / crc must be device pointers (crc 4-byte aligned)");
-  }
-  a.out = out; a.off = (long long*)off; a.len = len; a.crc = crc;
-  mre_launch_varint_size(&a, (hipStream_t)stream);
-  if (out) mre_launch_varint_pack(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
-}
-
-extern "C" int mre_crc32c_rows(void* stream, const uint8_t* src, size_t row_stride, size_t row_bytes,
-                               const int32_t* rows_idx, int src_rows, int rows, uint32_t* crc, void* workspace,
-                               size_t workspace_bytes) {
-  RecArgs a;
-  int rc = rec_args("mre_crc32c_rows", a, src, row_stride, row_bytes, rows_idx, src_rows, rows, workspace,
-                    workspace_bytes, REC_CRC_SEG);
-  if (rc) return rc;
-  if (!crc || !is_device_ptr(crc) || ((uintptr_t)crc & 3))
-    return fail(MRE_ERR_ARG, "mre_crc32c_rows: crc must be a 4-byte aligned device pointer");
-  a.crc = crc;
-  mre_launch_crc32c_rows(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
-}
-
-static size_t unpack_segments(size_t max_src_len) { return (max_src_len + REC_UNPACK_SEG - 1) / REC_UNPACK_SEG; }
-
-extern "C" size_t mre_varint_unpack_workspace_bytes(int rows, size_t max_src_len) {
-  if (rows <= 0 || max_src_len == 0 || max_src_len > REC_MAX_PACKED_BYTES) return 0;
-  return (size_t)rows * unpack_segments(max_src_len) * sizeof(uint32_t);   // start bytes per segment, then their scan
-}
-
-extern "C" int mre_varint_unpack_rows(void* stream, const uint8_t* src, size_t src_bytes, const int64_t* src_off,
-                                      const int64_t* src_len, const int64_t* nvalues, const int64_t* out_off, int rows,
-                                      size_t max_src_len, uint8_t* out, size_t out_capacity, uint32_t* status,
-                                      void* workspace, size_t workspace_bytes) {
-  const std::string w("mre_varint_unpack_rows");
-  if (!src || !src_off || !src_len || !nvalues || !out_off || !out || !status || !workspace || rows <= 0 ||
-      src_bytes == 0 || out_capacity == 0)
-    return fail(MRE_ERR_ARG, w + ": null argument, empty buffer or empty row set");
-  if (max_src_len == 0 || max_src_len > REC_MAX_PACKED_BYTES) return fail(MRE_ERR_ARG, w + ": max_src_len outside 1 .. 2^31");
-  const size_t nseg = unpack_segments(max_src_len);
-  if ((size_t)rows * nseg > 0x7FFFFFFFull) return fail(MRE_ERR_ARG, w + ": rows x segments above 2^31 - 1");
-  if (workspace_bytes < mre_varint_unpack_workspace_bytes(rows, max_src_len) || ((uintptr_t)workspace & 3))
-    return fail(MRE_ERR_ARG, w + ": workspace smaller than mre_varint_unpack_workspace_bytes() or not 4-byte aligned");
-  if ((((uintptr_t)src_off | (uintptr_t)src_len | (uintptr_t)nvalues | (uintptr_t)out_off) & 7) || ((uintptr_t)status & 3))
-    return fail(MRE_ERR_ARG, w + ": descriptors must be 8-byte aligned, status 4-byte aligned");
-  if (!is_device_ptr(src) || !is_device_ptr(src_off) || !is_device_ptr(src_len) || !is_device_ptr(nvalues) ||
-      !is_device_ptr(out_off) || !is_device_ptr(out) || !is_device_ptr(status) || !is_device_ptr(workspace))
-    return fail(MRE_ERR_ARG, w + ": src, the descriptors, out, status and workspace must be device pointers");
-  UnpackArgs a;
-  memset(&a, 0, sizeof(a));
-  a.src = src; a.src_bytes = src_bytes;
-  a.src_off = (const long long*)src_off; a.src_len = (const long long*)src_len;
-  a.nvalues = (const long long*)nvalues; a.out_off = (const long long*)out_off;
-  a.max_src_len = max_src_len; a.rows = (uint32_t)rows; a.nseg = (uint32_t)nseg;
-  a.out = out; a.out_capacity = out_capacity; a.status = status; a.segoff = (uint32_t*)workspace;
-  mre_launch_varint_unpack(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
-}
-
-// ---- frame labels on the device (csrc/mre_labels.hip): boxes, counts, coordinate sums and nearest depth per label
-extern "C" int mre_seg_labels(void* stream, const uint8_t* seg, const float* depth, int n, int height, int width,
-                              int id0, int nid, int64_t* stats, float* zmin) {
-  const std::string w("mre_seg_labels");
-  if (n < 0 || height < 1 || width < 1 || (long long)height * width >= (1ll << 31))
-    return fail(MRE_ERR_ARG, w + ": n >= 0, height and width >= 1, height * width < 2^31");
-  if (nid < 1 || nid > (int)LAB_MAX_IDS || id0 < 0 || id0 + nid > 256)
-    return fail(MRE_ERR_ARG, w + ": 1 <= nid <= 8 labels inside 0 .. 255");
-  if (!seg || !stats) return fail(MRE_ERR_ARG, w + ": null seg or stats");
-  if ((depth == nullptr) != (zmin == nullptr)) return fail(MRE_ERR_ARG, w + ": depth and zmin go together");
-  if (((uintptr_t)depth & 3) || ((uintptr_t)zmin & 3) || ((uintptr_t)stats & 7))
-    return fail(MRE_ERR_ARG, w + ": depth and zmin must be 4-byte aligned, stats 8-byte aligned");
-  if (n == 0) return MRE_OK;
-  if (!is_device_ptr(seg) || !is_device_ptr(stats) || (depth && (!is_device_ptr(depth) || !is_device_ptr(zmin))))
-    return fail(MRE_ERR_ARG, w + ": seg, depth, stats and zmin must be device pointers");
-  LabelArgs a;
-  memset(&a, 0, sizeof(a));
-  a.seg = seg; a.depth = depth; a.n = (uint32_t)n; a.hw = (uint32_t)(height * width); a.w = (uint32_t)width;
-  a.id0 = (uint32_t)id0; a.nid = (uint32_t)nid; a.chunks = label_chunks(a.n, a.hw);
-  a.stats = (unsigned long long*)stats; a.zmin = (uint32_t*)zmin;
-  mre_launch_seg_labels(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
-}
-
-// ---- orthographic heightmaps on the device (csrc/mre_heightmap.hip): height, colour, label and source pixel per cell
-extern "C" int mre_heightmap(void* stream, const float* depth, const uint8_t* rgb, const uint8_t* seg, int n, int height,
-                             int width, const float* cam, const float* bounds, float inv_cell, float max_depth, int out_h,
-                             int out_w, float* hmap, uint8_t* cmap, uint8_t* smap, int32_t* src) {
-  const std::string w("mre_heightmap");
-  if (n < 0 || height < 1 || width < 1 || (long long)height * width >= (1ll << 31))
-    return fail(MRE_ERR_ARG, w + ": n >= 0, height and width >= 1, height * width < 2^31");
-  if (out_h < 1 || out_w < 1 || out_h > (int)HM_MAX_OUT || out_w > (int)HM_MAX_OUT)
-    return fail(MRE_ERR_ARG, w + ": 1 <= out_h, out_w <= 4096");
-  if (!(inv_cell > 0.f) || !(max_depth > 0.f) || !std::isfinite(inv_cell) || !std::isfinite(max_depth))
-    return fail(MRE_ERR_ARG, w + ": inv_cell and max_depth must be positive and finite");
-  if (!cam || !bounds) return fail(MRE_ERR_ARG, w + ": null cam or bounds");
-  for (int k = 0; k < 3; k++)
-    if (!std::isfinite(bounds[k]) || !std::isfinite(bounds[3 + k]) || !(bounds[k] <= bounds[3 + k]))
-      return fail(MRE_ERR_ARG, w + ": bounds must be finite with lo <= hi");
-  if (!depth || !hmap) return fail(MRE_ERR_ARG, w + ": null depth or hmap");
-  if ((rgb == nullptr) != (cmap == nullptr)) return fail(MRE_ERR_ARG, w + ": rgb and cmap go together");
-  if ((seg == nullptr) != (smap == nullptr)) return fail(MRE_ERR_ARG, w + ": seg and smap go together");
-  if (((uintptr_t)depth & 3) || ((uintptr_t)hmap & 3) || ((uintptr_t)src & 3))
-    return fail(MRE_ERR_ARG, w + ": depth, hmap and src must be 4-byte aligned");
-  if (n == 0) return MRE_OK;
-  if (!is_device_ptr(depth) || !is_device_ptr(hmap) || (rgb && (!is_device_ptr(rgb) || !is_device_ptr(cmap))) ||
-      (seg && (!is_device_ptr(seg) || !is_device_ptr(smap))) || (src && !is_device_ptr(src)))
-    return fail(MRE_ERR_ARG, w + ": depth, rgb, seg, hmap, cmap, smap and src must be device pointers");
-  HeightmapArgs a;
-  memset(&a, 0, sizeof(a));
-  a.depth = depth; a.rgb = rgb; a.seg = seg; a.n = (uint32_t)n; a.h = (uint32_t)height; a.w = (uint32_t)width;
-  memcpy(a.g.cam, cam, sizeof(a.g.cam));
-  for (int k = 0; k < 3; k++) { a.g.lo[k] = bounds[k]; a.g.hi[k] = bounds[3 + k]; }
-  a.g.inv_cell = inv_cell; a.g.max_depth = max_depth; a.g.out_w = (float)out_w; a.g.out_h = (float)out_h;
-  a.cell = (float)(1.0 / (double)inv_cell);
-  // the inverse of A bounds the pixels a tile can take (the source rectangle); without one every tile scans the image
-  const double m[9] = {cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7], cam[8]};
-  const double co[9] = {m[4] * m[8] - m[5] * m[7], m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
-                        m[5] * m[6] - m[3] * m[8], m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
-                        m[3] * m[7] - m[4] * m[6], m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]};
-  const double det = m[0] * co[0] + m[1] * co[3] + m[2] * co[6];
-  double big = 0.0;
-  for (int k = 0; k < 9; k++) big = std::max(big, std::fabs(m[k]));
-  bool usable = std::isfinite(det) && std::fabs(det) > 1e-12 * big * big * big && std::isfinite(cam[9]) &&
-                std::isfinite(cam[10]) && std::isfinite(cam[11]);
-  for (int k = 0; k < 9; k++) {
-    a.inv[k] = (float)(co[k] / det);
-    usable = usable && std::isfinite(a.inv[k]);
-  }
-  a.whole_image = usable ? 0u : 1u;
-  a.out_h = (uint32_t)out_h; a.out_w = (uint32_t)out_w;
-  a.tiles_x = (a.out_w + HM_TILE - 1) / HM_TILE; a.tiles_y = (a.out_h + HM_TILE - 1) / HM_TILE;
-  a.hmap = hmap; a.cmap = cmap; a.smap = smap; a.src = src;
-  mre_launch_heightmap(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
-}
-
-// A base (or null) and a length in bytes.  Whether a range of `outs` overlaps one of `ins`; a null or empty range
-// overlaps nothing.  The callers' lengths cannot overflow: they state why.
-typedef std::pair<const void*, size_t> ByteRange;
-template <size_t I, size_t O>
-static bool ranges_overlap(const ByteRange (&ins)[I], const ByteRange (&outs)[O]) {
-  for (const auto& o : outs)
-    for (const auto& i : ins) {
-      if (!o.first || !i.first || !o.second || !i.second) continue;
-      const uintptr_t o0 = (uintptr_t)o.first, i0 = (uintptr_t)i.first;
-      if (o0 < i0 + i.second && i0 < o0 + o.second) return true;
-    }
-  return false;
-}
-
-// ---- what mre_warp_maps and mre_warp_inputs gather from (csrc/mre_warp_gather.h): the checks on the arguments they
-// share, in the name `w` of the entry point, and those arguments as the kernels read them
-static int warp_source(const std::string& w, const float* hmap, const uint8_t* cmap, int n, int in_h, int in_w,
-                       const int32_t* index, const float* mats, int samples, int out_h, int out_w, WarpSource* s) {
-  const int lim = (int)WP_MAX_DIM;
-  if (n < 0 || samples < 0) return fail(MRE_ERR_ARG, w + ": n >= 0 and samples >= 0");
-  if (in_h < 1 || in_w < 1 || out_h < 1 || out_w < 1 || in_h > lim || in_w > lim || out_h > lim || out_w > lim)
-    return fail(MRE_ERR_ARG, w + ": 1 <= in_h, in_w, out_h, out_w <= 4096");
-  if (!hmap || !mats) return fail(MRE_ERR_ARG, w + ": null hmap or mats");
-  if (((uintptr_t)hmap & 3) || ((uintptr_t)mats & 3) || ((uintptr_t)index & 3))
-    return fail(MRE_ERR_ARG, w + ": hmap, mats and index must be 4-byte aligned");
-  if (!index && samples > n) return fail(MRE_ERR_ARG, w + ": more samples than maps and no index");
-  s->hmap = hmap; s->cmap = cmap; s->index = index; s->mats = mats;
-  s->n = (uint32_t)n; s->in_h = (uint32_t)in_h; s->in_w = (uint32_t)in_w;
-  s->samples = (uint32_t)samples; s->out_h = (uint32_t)out_h; s->out_w = (uint32_t)out_w;
-  s->tiles_x = (s->out_w + WP_TILE_W - 1) / WP_TILE_W; s->tiles_y = (s->out_h + WP_TILE_H - 1) / WP_TILE_H;
-  return MRE_OK;
-}
-
-// ---- warped and cropped maps on the device (csrc/mre_warp.hip): a nearest-neighbour affine gather of the three maps
-extern "C" int mre_warp_maps(void* stream, const float* hmap, const uint8_t* cmap, const uint8_t* smap, int n, int in_h,
-                             int in_w, const int32_t* index, const float* mats, int samples, int out_h, int out_w,
-                             float* out_h_, uint8_t* out_c, uint8_t* out_s, int32_t* from) {
-  const std::string w("mre_warp_maps");
-  WarpArgs a;
-  memset(&a, 0, sizeof(a));
-  if (const int rc = warp_source(w, hmap, cmap, n, in_h, in_w, index, mats, samples, out_h, out_w, &a.source)) return rc;
-  if (!out_h_) return fail(MRE_ERR_ARG, w + ": null height output");
-  if ((cmap == nullptr) != (out_c == nullptr)) return fail(MRE_ERR_ARG, w + ": cmap and its output go together");
-  if ((smap == nullptr) != (out_s == nullptr)) return fail(MRE_ERR_ARG, w + ": smap and its output go together");
-  if (((uintptr_t)out_h_ & 3) || ((uintptr_t)from & 3))
-    return fail(MRE_ERR_ARG, w + ": the height output and from must be 4-byte aligned");
-  // no output byte range may overlap an input byte range (n, samples <= 2^31 and maps <= 2^24 cells: no overflow)
-  const size_t in_cells = (size_t)n * in_h * in_w, out_cells = (size_t)samples * out_h * out_w;
-  const ByteRange ins[5] = {{hmap, 4 * in_cells}, {cmap, 3 * in_cells}, {smap, in_cells},
-                            {index, 4 * (size_t)samples}, {mats, 24 * (size_t)samples}};
-  const ByteRange outs[4] = {{out_h_, 4 * out_cells}, {out_c, 3 * out_cells}, {out_s, out_cells}, {from, 4 * out_cells}};
-  if (ranges_overlap(ins, outs)) return fail(MRE_ERR_ARG, w + ": an output overlaps an input");
-  if (n == 0 || samples == 0) return MRE_OK;
-  if (!is_device_ptr(hmap) || !is_device_ptr(mats) || !is_device_ptr(out_h_) || (index && !is_device_ptr(index)) ||
-      (cmap && (!is_device_ptr(cmap) || !is_device_ptr(out_c))) ||
-      (smap && (!is_device_ptr(smap) || !is_device_ptr(out_s))) || (from && !is_device_ptr(from)))
-    return fail(MRE_ERR_ARG, w + ": the maps, index, mats and the outputs must be device pointers");
-  // the wide stores: 4 cells of a row at once need the width a multiple of 4 and bases aligned to what a lane stores
-  a.vec = (out_w % 4 == 0 && !((uintptr_t)out_h_ & 15) && !((uintptr_t)from & 15) && !((uintptr_t)out_c & 3) &&
-           !((uintptr_t)out_s & 3)) ? 1u : 0u;
-  a.smap = smap; a.out_h_ = out_h_; a.out_c = out_c; a.out_s = out_s; a.from = from;
-  mre_launch_warp_maps(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
-}
-
-// ---- network-ready inputs on the device (csrc/mre_warp_inputs.hip): the same gather, written planar and normalised
-extern "C" int mre_warp_inputs(void* stream, const float* hmap, const uint8_t* cmap, int n, int in_h, int in_w,
-                               const int32_t* index, const float* mats, int samples, int out_h, int out_w, int channels,
-                               const int32_t* chan_src, const float* chan_scale, const float* chan_bias, int dtype,
-                               void* out) {
-  const std::string w("mre_warp_inputs");
-  WarpInputArgs a;
-  memset(&a, 0, sizeof(a));
-  if (const int rc = warp_source(w, hmap, cmap, n, in_h, in_w, index, mats, samples, out_h, out_w, &a.source)) return rc;
-  if (!out) return fail(MRE_ERR_ARG, w + ": null out");
-  if (channels < 1 || channels > WI_MAX_CHANNELS) return fail(MRE_ERR_ARG, w + ": 1 <= channels <= 8");
-  if (!chan_src || !chan_scale || !chan_bias) return fail(MRE_ERR_ARG, w + ": null chan_src, chan_scale or chan_bias");
-  bool colour = false;
-  for (int k = 0; k < channels; k++) {
-    if (chan_src[k] < MRE_SRC_RED || chan_src[k] > MRE_SRC_HEIGHT)
-      return fail(MRE_ERR_ARG, w + ": chan_src must be 0 (red), 1 (green), 2 (blue) or 3 (height)");
-    colour = colour || chan_src[k] != MRE_SRC_HEIGHT;
-    if (!std::isfinite(chan_scale[k]) || !std::isfinite(chan_bias[k]))
-      return fail(MRE_ERR_ARG, w + ": chan_scale and chan_bias must be finite");
-  }
-  if (colour && !cmap) return fail(MRE_ERR_ARG, w + ": a colour source needs cmap");
-  if (dtype != MRE_F32 && dtype != MRE_BF16) return fail(MRE_ERR_ARG, w + ": dtype must be MRE_F32 or MRE_BF16");
-  const size_t esize = dtype == MRE_BF16 ? 2 : 4;
-  if ((uintptr_t)out & (esize - 1)) return fail(MRE_ERR_ARG, w + ": out must be aligned to its element size");
-  // out may overlap no input byte range (samples <= 2^31, 8 channels, maps <= 2^24 cells, 4 B: below 2^60)
-  const size_t in_cells = (size_t)n * in_h * in_w;
-  const size_t out_bytes = (size_t)samples * channels * out_h * out_w * esize;
-  const ByteRange ins[4] = {{hmap, 4 * in_cells}, {cmap, 3 * in_cells}, {index, 4 * (size_t)samples},
-                            {mats, 24 * (size_t)samples}};
-  const ByteRange outs[1] = {{out, out_bytes}};
-  if (ranges_overlap(ins, outs)) return fail(MRE_ERR_ARG, w + ": out overlaps an input");
-  if (n == 0 || samples == 0) return MRE_OK;
-  if (!is_device_ptr(hmap) || !is_device_ptr(mats) || !is_device_ptr(out) || (index && !is_device_ptr(index)) ||
-      (colour && !is_device_ptr(cmap)))
-    return fail(MRE_ERR_ARG, w + ": the maps, index, mats and out must be device pointers");
-  if (!colour) a.source.cmap = nullptr;   // given, but no channel reads it
-  // the wide stores: a lane's 4 cells of a channel at once need the width a multiple of 4 (every row and every channel
-  // plane then starts at a multiple of 4 elements) and out aligned to those 4 elements
-  a.vec = (out_w % 4 == 0 && ((size_t)out_h * out_w) % 4 == 0 && !((uintptr_t)out & (4 * esize - 1))) ? 1u : 0u;
-  a.colour = colour ? 1u : 0u; a.bf16 = dtype == MRE_BF16 ? 1u : 0u; a.channels = (uint32_t)channels;
-  for (int k = 0; k < channels; k++) {
-    a.src[k] = (uint32_t)chan_src[k]; a.scale[k] = chan_scale[k]; a.bias[k] = chan_bias[k];
-  }
-  a.out = out;
-  mre_launch_warp_inputs(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
-}
-
-// ---- the Transporter place head on the device (csrc/mre_correlate.hip): correlate the crops with the scene, best cell
-static bool correlate_shape_ok(int n, int rotations, int h, int w) {
-  return n >= 0 && rotations >= 1 && rotations <= CR_MAX_ROT && h >= 1 && w >= 1 && h <= CR_MAX_DIM && w <= CR_MAX_DIM &&
-         (long long)rotations * h * w < (1ll << 31);
-}
-
-static size_t correlate_workspace(int n, int h, int w) {
-  const size_t slots = (size_t)n * cr_tiles((uint32_t)h, CR_TILE_H) * cr_tiles((uint32_t)w, CR_TILE_W);
-  const size_t bytes = (slots * CR_SLOT_BYTES + 15) & ~(size_t)15;
-  return bytes ? bytes : 16;   // never 0: a workspace can always be allocated and passed
-}
-
-extern "C" int mre_correlate_workspace(int n, int rotations, int h, int w, size_t* bytes) {
-  const std::string wh("mre_correlate_workspace");
-  if (!bytes) return fail(MRE_ERR_ARG, wh + ": null bytes");
-  if (!correlate_shape_ok(n, rotations, h, w))
-    return fail(MRE_ERR_ARG, wh + ": n >= 0, 1 <= rotations <= 64, 1 <= h, w <= 4096, rotations * h * w < 2^31");
-  *bytes = correlate_workspace(n, h, w);
-  return MRE_OK;
-}
-
-extern "C" int mre_correlate(void* stream, const uint16_t* scene, const uint16_t* kern, int n, int rotations, int depth,
-                             int h, int w, int crop, int dtype, void* logits, int64_t* best_index, float* best_value,
-                             void* workspace, size_t workspace_bytes) {
-  const std::string wh("mre_correlate");
-  if (n < 0) return fail(MRE_ERR_ARG, wh + ": n >= 0");
-  if (rotations < 1 || rotations > CR_MAX_ROT) return fail(MRE_ERR_ARG, wh + ": 1 <= rotations <= 64");
-  if (depth < 1 || depth > CR_MAX_DEPTH) return fail(MRE_ERR_ARG, wh + ": 1 <= depth <= 16");
-  if (crop < 2 || crop > CR_MAX_CROP || (crop & 1)) return fail(MRE_ERR_ARG, wh + ": crop must be even, 2 <= crop <= 64");
-  if (h < 1 || w < 1 || h > CR_MAX_DIM || w > CR_MAX_DIM) return fail(MRE_ERR_ARG, wh + ": 1 <= h, w <= 4096");
-  if (!correlate_shape_ok(n, rotations, h, w)) return fail(MRE_ERR_ARG, wh + ": rotations * h * w must be below 2^31");
-  if (!scene || !kern) return fail(MRE_ERR_ARG, wh + ": null scene or kern");
-  if (((uintptr_t)scene & 1) || ((uintptr_t)kern & 1)) return fail(MRE_ERR_ARG, wh + ": scene and kern must be 2-byte aligned");
-  if (dtype != MRE_F32 && dtype != MRE_BF16) return fail(MRE_ERR_ARG, wh + ": dtype must be MRE_F32 or MRE_BF16");
-  const size_t esize = dtype == MRE_BF16 ? 2 : 4;
-  if ((uintptr_t)logits & (esize - 1)) return fail(MRE_ERR_ARG, wh + ": logits must be aligned to its element size");
-  if (!best_index != !best_value) return fail(MRE_ERR_ARG, wh + ": best_index and best_value are NULL together or not at all");
-  if (((uintptr_t)best_index & 7) || ((uintptr_t)best_value & 3))
-    return fail(MRE_ERR_ARG, wh + ": best_index must be 8-byte and best_value 4-byte aligned");
-  if (!logits && !best_index) return fail(MRE_ERR_ARG, wh + ": nothing to write: logits and best_* are all NULL");
-  const size_t need = correlate_workspace(n, h, w);
-  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need)
-    return fail(MRE_ERR_ARG, wh + ": workspace must be non-NULL, 16-byte aligned and as large as mre_correlate_workspace says");
-  // no output or workspace byte range may overlap an input (n < 2^31, 64 x 16 x 64 x 64 x 2 B per env: below 2^54)
-  const size_t cells = (size_t)h * w;
-  const ByteRange ins[2] = {{scene, 2 * (size_t)n * depth * cells}, {kern, 2 * (size_t)n * rotations * depth * crop * crop}};
-  const ByteRange outs[4] = {{logits, esize * (size_t)n * rotations * cells}, {best_index, 8 * (size_t)n},
-                             {best_value, 4 * (size_t)n}, {workspace, need}};
-  if (ranges_overlap(ins, outs)) return fail(MRE_ERR_ARG, wh + ": an output or the workspace overlaps an input");
-  if (n == 0) return MRE_OK;
-  if (!is_device_ptr(scene) || !is_device_ptr(kern) || !is_device_ptr(workspace) || (logits && !is_device_ptr(logits)) ||
-      (best_index && (!is_device_ptr(best_index) || !is_device_ptr(best_value))))
-    return fail(MRE_ERR_ARG, wh + ": scene, kern, the outputs and the workspace must be device pointers");
-  CorrelateArgs a;
-  memset(&a, 0, sizeof(a));
-  a.scene = scene; a.kern = kern; a.logits = logits; a.best_index = best_index; a.best_value = best_value;
-  a.workspace = workspace;
-  a.n = (uint32_t)n; a.rot = (uint32_t)rotations; a.depth = (uint32_t)depth; a.h = (uint32_t)h; a.w = (uint32_t)w;
-  a.crop = (uint32_t)crop;
-  a.tiles_x = cr_tiles(a.w, CR_TILE_W); a.tiles_y = cr_tiles(a.h, CR_TILE_H);
-  a.bf16 = dtype == MRE_BF16 ? 1u : 0u;
-  // the wide accesses: a lane's 8 taps of a kernel row (every row then starts at a multiple of 8 elements), and its 8
-  // logits of a pixel row
-  a.vec_kern = (crop % 8 == 0 && !((uintptr_t)kern & 15)) ? 1u : 0u;
-  a.vec_out = (logits && w % 8 == 0 && !((uintptr_t)logits & 15)) ? 1u : 0u;
-  mre_launch_correlate(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
   return MRE_OK;
 }
 

@@ -1,6 +1,6 @@
 // The Transporter place head on the device (csrc/mre_correlate.hip): every env's scene feature map cross-correlated with
 // that env's own rotated crop feature maps on the bf16 matrix cores, and the best (rotation, row, column) per env.
-// Shared between the kernel's translation unit and the C ABI (mre_api.cpp); NOT part of lib.source_hash(): nothing here
+// Shared between the kernel's translation unit and the C ABI (mre_stream_api.cpp); NOT part of lib.source_hash(): nothing here
 // is launched by the step or the camera.
 #ifndef MRE_CORRELATE_H
 #define MRE_CORRELATE_H

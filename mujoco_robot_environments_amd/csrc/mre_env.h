@@ -1,6 +1,6 @@
-// mre_env.h -- the handle behind the C ABI (struct mre_env) and what the two host units that work on it share: error
-// reporting, the drain of pending launches that every entry point starts with, and the scheduler's four entry points
-// (mre_sched.cpp).  Private to csrc/: mre_api.cpp and mre_sched.cpp include it, nothing else does.
+// mre_env.h -- the handle behind the C ABI (struct mre_env) and what the two host units that work on it share: the
+// drain of pending launches that every entry point starts with, and the scheduler's four entry points (mre_sched.cpp);
+// error reporting comes with mre_host.h.  Private to csrc/: mre_api.cpp and mre_sched.cpp include it, nothing else does.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,14 +10,8 @@
 
 #include "../../include/mre.h"
 #include "mre_dev.h"
+#include "mre_host.h"
 #include "mre_policy.h"
-
-#define HIPCHK(x)                                                                       \
-  do {                                                                                  \
-    hipError_t e_ = (x);                                                                \
-    if (e_ != hipSuccess)                                                               \
-      return mre::fail(MRE_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));    \
-  } while (0)
 
 struct mre_env {
   int N = 0, device = 0;
@@ -199,7 +193,6 @@ struct mre_env {
 };
 
 namespace mre {
-int fail(int code, const std::string& msg);   // records msg for mre_last_error() (mre_api.cpp) and returns code
 // ---- the launch scheduler (mre_sched.cpp)
 // the env groups, the queue state and their streams and events (from create_buffers / mre_destroy)
 int sched_create(mre_env* e);

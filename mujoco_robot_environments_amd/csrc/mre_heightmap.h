@@ -1,6 +1,6 @@
 // Orthographic heightmaps on the device (csrc/mre_heightmap.hip): the camera's depth / rgb / seg frames of every env
 // binned top-down into a height map, a colour map, a label map and the source pixel of every cell.  Shared between the
-// kernel's translation unit and the C ABI (mre_api.cpp); NOT part of lib.source_hash(): nothing here is launched by the
+// kernel's translation unit and the C ABI (mre_stream_api.cpp); NOT part of lib.source_hash(): nothing here is launched by the
 // step or the camera.
 #ifndef MRE_HEIGHTMAP_H
 #define MRE_HEIGHTMAP_H

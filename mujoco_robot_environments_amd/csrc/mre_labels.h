@@ -1,6 +1,6 @@
 // Frame labels on the device (csrc/mre_labels.hip): per env and per label of a segmentation image, the box, the pixel
 // count, the coordinate sums and the nearest depth of the label's pixels.  Shared between the kernels' translation unit
-// and the C ABI (mre_api.cpp); NOT part of lib.source_hash(): nothing here is launched by the step or the camera.
+// and the C ABI (mre_stream_api.cpp); NOT part of lib.source_hash(): nothing here is launched by the step or the camera.
 #ifndef MRE_LABELS_H
 #define MRE_LABELS_H
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // Episode-record encoding and decoding on the device (csrc/mre_records.hip): packed varints of uint8 rows,
 // their inverse, and CRC-32C of rows, for the TFRecord shards of dataset.py.  Shared between the kernels' translation
-// unit and the C ABI (mre_api.cpp); NOT part of lib.source_hash(): nothing here is launched by the
+// unit and the C ABI (mre_stream_api.cpp); NOT part of lib.source_hash(): nothing here is launched by the
 // step or the camera.
 #ifndef MRE_RECORDS_H
 #define MRE_RECORDS_H

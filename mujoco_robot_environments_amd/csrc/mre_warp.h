@@ -1,6 +1,6 @@
 // Warped and cropped maps on the device (csrc/mre_warp.hip): a nearest-neighbour affine gather of the height, colour and
 // label maps of mre_heightmap -- the SE(2) perturbation and the rotated pick crops of a Transporter training sample.
-// Shared between the kernel's translation unit and the C ABI (mre_api.cpp); NOT part of lib.source_hash(): nothing here
+// Shared between the kernel's translation unit and the C ABI (mre_stream_api.cpp); NOT part of lib.source_hash(): nothing here
 // is launched by the step or the camera.
 #ifndef MRE_WARP_H
 #define MRE_WARP_H

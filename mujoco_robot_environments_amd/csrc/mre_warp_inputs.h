@@ -1,6 +1,6 @@
 // Network-ready inputs on the device (csrc/mre_warp_inputs.hip): the nearest-neighbour affine gather of mre_warp_maps
 // written as a planar, per-channel normalised float32 or bfloat16 tensor -- what a convolution consumes.
-// Shared between the kernel's translation unit and the C ABI (mre_api.cpp); NOT part of lib.source_hash(): nothing here
+// Shared between the kernel's translation unit and the C ABI (mre_stream_api.cpp); NOT part of lib.source_hash(): nothing here
 // is launched by the step or the camera.
 #ifndef MRE_WARP_INPUTS_H
 #define MRE_WARP_INPUTS_H

@@ -31,6 +31,30 @@ def test_python_binding_lists_all(libmre):
     assert names == set(lib.EXPORTS)
 
 
+def test_diagnostic_build_loads():
+    """tools/build_variant.py builds what lib.build() builds: its library loads and exports every name of the binding
+    (with unit lists of their own, the diagnostic builds lacked the newer units and could not be loaded)."""
+    import subprocess
+    import sys
+    from mujoco_robot_environments_amd import lib
+    name = "abi_test_throwaway"
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "tools", "build_variant.py"), name], text=True)
+    so = out.split()[-1]
+    try:
+        assert so == os.path.join(ROOT, "tools", "_diag", f"libmre_{name}.so")
+        import torch  # noqa: F401  (one HIP runtime per process: lib.lib())
+        diag = C.CDLL(so)
+        missing = [n for n in lib.EXPORTS if not hasattr(diag, n)]
+        assert not missing, missing
+    finally:
+        for n, _, _ in lib.UNITS:
+            p = os.path.join(ROOT, "tools", "_diag", f"{n}_{name}.o")
+            if os.path.exists(p):
+                os.remove(p)
+        if os.path.exists(so):
+            os.remove(so)
+
+
 def test_bad_blob_rejected(libmre):
     h = C.c_void_p()
     rc = libmre.mre_create(b"\0" * 64, 64, 4, 0, C.byref(h))

@@ -6,7 +6,6 @@ The product library never carries the stamps (MRE_PHASE_STAMPS is undefined in l
 """
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mujoco_robot_environments_amd", "csrc")
 DIAG = os.path.join(ROOT, "tools", "_diag")
 NAMES = ["position+crb+factor", "velocity", "collide", "assemble", "control", "smooth", "solve", "integrate+io",
          "newton: setup", "newton: direction (H, factor, solves)", "newton: direction (factor re-used)", "newton: line search + move + update",
@@ -30,25 +29,11 @@ NAMES = ["position+crb+factor", "velocity", "collide", "assemble", "control", "s
          "  setup: calls", "  setup: calls won by qacc_smooth", "  (unused)", "  (unused)"]
 
 if sys.argv[1] == "build":
-    os.makedirs(DIAG, exist_ok=True)
-    for k in ([int(x) for x in sys.argv[2:]] or (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11)):
-        base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-ffp-contract=on",
-                "-fno-hip-fp32-correctly-rounded-divide-sqrt"]
-        objs = []
-        for name, src, flags in (("k", "mre_kernels.hip", [f"-DMRE_PHASE_STAMPS={k}"]),
-                                 ("kl", "mre_kernels.hip", ["-DMRE_LARGE_CAPS", f"-DMRE_PHASE_STAMPS={k}"]),
-                                 ("kn", "mre_kernels.hip", ["-DMRE_NEWTON", f"-DMRE_PHASE_STAMPS={k}"]),
-                                 ("kln", "mre_kernels.hip", ["-DMRE_LARGE_CAPS", "-DMRE_NEWTON", f"-DMRE_PHASE_STAMPS={k}"]),
-                                 ("r", "mre_render.hip", []),
-                                 ("rec", "mre_records.hip", []), ("lab", "mre_labels.hip", []),
-                                 ("hm", "mre_heightmap.hip", []), ("warp", "mre_warp.hip", []),
-                                 ("wi", "mre_warp_inputs.hip", []),
-                                 ("api", "mre_api.cpp", []), ("sched", "mre_sched.cpp", []),
-                                 ("model", "mre_model.cpp", [])):
-            objs.append(os.path.join(DIAG, f"{name}{k}.o"))
-            subprocess.check_call(base + flags + ["-c", os.path.join(CSRC, src), "-o", objs[-1]])
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o",
-                               os.path.join(DIAG, f"libmre_stamps{k}.so")] + objs)
+    sys.path.insert(0, ROOT)
+    from mujoco_robot_environments_amd import lib
+    for k in ([int(x) for x in sys.argv[2:]] or (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11)):   # the flags and units of lib.build()
+        lib.compile_and_link(os.path.join(DIAG, f"libmre_stamps{k}.so"), DIAG, suffix=str(k),
+                             step_extra=[f"-DMRE_PHASE_STAMPS={k}"])
 elif sys.argv[1] == "run":
     if "MRE_LIB" not in os.environ:
         solver = sys.argv[3] if len(sys.argv) > 3 else "PGS"

@@ -13,12 +13,12 @@ measurement.
 import argparse, os, re, shutil, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from mujoco_robot_environments_amd import lib
 CSRC = os.path.join(ROOT, "mujoco_robot_environments_amd", "csrc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-ffp-contract=on",
-         "-fno-hip-fp32-correctly-rounded-divide-sqrt"]   # lib.build()
-UNITS = [("kernels (compact PGS)", []), ("kernels_large (large PGS)", ["-DMRE_LARGE_CAPS"]),
-         ("kernels_newton (compact Newton)", ["-DMRE_NEWTON"]),
-         ("kernels_large_newton (large Newton)", ["-DMRE_LARGE_CAPS", "-DMRE_NEWTON"])]
+# the step kernel's instantiations as lib.build() compiles them, in the order of its table
+UNITS = [(f"{name} ({what})", defines) for (name, src, defines), what in
+         zip([u for u in lib.UNITS if u[1] == lib.STEP_SOURCE], ("compact PGS", "large PGS", "compact Newton", "large Newton"))]
 # the phases one step of the flagship (Newton) workload runs outside the solver, in the order of the step
 STEP_PHASES = ["position_stage", "gripper_local", "connect_rows_local", "velocity_stage", "finger_bias", "collide_broad",
                "collide_narrow",
@@ -94,8 +94,8 @@ def main():
         procs = []
         for k, (name, flags) in enumerate(UNITS):
             s = os.path.join(td, f"u{k}.s")
-            procs.append((name, s, subprocess.Popen([hipcc] + FLAGS + flags + ["--cuda-device-only", "-S",
-                                                    os.path.join(CSRC, "mre_kernels.hip"), "-o", s],
+            procs.append((name, s, subprocess.Popen([hipcc] + lib.FLAGS + flags + ["--cuda-device-only", "-S",
+                                                    os.path.join(CSRC, lib.STEP_SOURCE), "-o", s],
                                                     stderr=subprocess.DEVNULL)))
         for name, s, p in procs:
             if p.wait() != 0:
