@@ -493,6 +493,48 @@ int mre_correlate(void* stream, const uint16_t* scene, const uint16_t* kern, int
                   int h, int w, int crop, int dtype, void* logits, int64_t* best_index, float* best_value,
                   void* workspace, size_t workspace_bytes);
 
+/* Training the place head on the device (csrc/mre_correlate_grad.hip): the softmax cross-entropy of every
+ * env's logits against a target cell, its gradient with respect to the logits, and the gradients of any g with respect to
+ * the scene and the kernels.  scene, kern, n, rotations (R), depth, h, w, crop and logit[e] = l are those of mre_correlate;
+ * no logit is ever stored.  With t = target[e], a flat index (r * h + y) * w + x, and the sums over all R * h * w cells:
+ *   lse[e]  = log sum_cells exp(l)          target_logit[e] = l[t]          loss[e] = lse[e] - l[t]
+ *   g[e][cell] = weight[e] * (exp(l[cell] - lse[e]) - [cell == t])      rounded to bfloat16 as mre_warp_inputs rounds
+ *   grad_kern[e][r][d][i][j] = sum_y sum_x g[e][r][y][x] * scene[e][d][y + i - crop/2][x + j - crop/2]
+ *   grad_scene[e][d][v][u]   = sum_r sum_i sum_j g[e][r][v - i + crop/2][u - j + crop/2] * kern[e][r][d][i][j]
+ * where a scene cell or a g cell outside [0, h) x [0, w) counts as 0: the two gradients of sum_cells g * l.
+ * A t outside [0, R * h * w) gives target_logit[e] = loss[e] = NaN, lse[e] as ever, and a g that is the weighted softmax
+ * alone.  The host never reads target.
+ *   target        device i64 [n], 8-byte aligned
+ *   lse, target_logit, loss   device f32 [n]; lse is an output of mre_correlate_loss and an input of mre_correlate_dlogits
+ *   weight        NULL (1 for every env) or device f32 [n]
+ *   g             device bfloat16 [n][R][h][w]: the output of mre_correlate_dlogits, and an INPUT of the two gradient entries,
+ *                 which therefore serve any loss
+ *   grad_scene    device f32 [n][depth][h][w];  grad_kern  device f32 [n][R][depth][crop][crop]
+ *   workspace     device, 16-byte aligned: for mre_correlate_loss at least what mre_correlate_workspace answers, for the two
+ *                 gradient entries at least what mre_correlate_grad_workspace answers (the larger of the flipped kernels,
+ *                 2 B, and min(ceil(h / 64), 4) partial grad_kern per env, 4 B, the latter only when h > 64: 7 MB per env at
+ *                 36 x 3 x 64 x 64 and h = 320 -- split a large batch); its contents before and after mean nothing
+ * lse is accumulated as an online (max, sum of exp2) in float32: within 2^-15 + 2^-22 |lse| of the exact value of the
+ * float32 logits.  The sums of the gradients are accumulated in float32 on the matrix cores in the kernels' own fixed order.
+ * Every output element is written exactly once and nothing else but the workspace is; no atomics; the same bytes on every
+ * run, and an env's bytes depend neither on n nor on its place in the batch.  g is stored 8 columns at a time where w is a
+ * multiple of 8 and g is 16-byte aligned, else element by element, with the same bits.  Enqueued on `stream` of the current
+ * device (loss: 2 launches, dlogits: 1, grad_scene: 2, grad_kern: 1, or 2 when h > 64); nothing synchronises.
+ * MRE_ERR_ARG, with nothing launched and no byte touched, unless the shape is in mre_correlate's ranges (n == 0: MRE_OK,
+ * nothing launched), the bfloat16 pointers are non-NULL and 2-byte aligned, target is non-NULL and 8-byte aligned, the
+ * float32 pointers are 4-byte aligned and (weight apart) non-NULL, workspace is non-NULL, 16-byte aligned and large enough,
+ * every pointer is a device pointer, and no output or workspace byte range overlaps an input. */
+int mre_correlate_loss(void* stream, const uint16_t* scene, const uint16_t* kern, int n, int rotations, int depth,
+                       int h, int w, int crop, const int64_t* target, float* lse, float* target_logit, float* loss,
+                       void* workspace, size_t workspace_bytes);
+int mre_correlate_dlogits(void* stream, const uint16_t* scene, const uint16_t* kern, int n, int rotations, int depth,
+                          int h, int w, int crop, const int64_t* target, const float* lse, const float* weight, uint16_t* g);
+int mre_correlate_grad_workspace(int n, int rotations, int depth, int h, int w, int crop, size_t* bytes);
+int mre_correlate_grad_scene(void* stream, const uint16_t* g, const uint16_t* kern, int n, int rotations, int depth,
+                             int h, int w, int crop, float* grad_scene, void* workspace, size_t workspace_bytes);
+int mre_correlate_grad_kern(void* stream, const uint16_t* g, const uint16_t* scene, int n, int rotations, int depth,
+                            int h, int w, int crop, float* grad_kern, void* workspace, size_t workspace_bytes);
+
 #define MRE_SOLVER_PGS 0
 #define MRE_SOLVER_NEWTON 2
 int mre_set_solver(mre_env*, int solver);

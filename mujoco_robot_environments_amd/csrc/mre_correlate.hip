@@ -1,6 +1,8 @@
 // The Transporter place head on the device (include/mre.h, mre_correlate): per env an implicit GEMM
 //   logit[r][y][x] = sum_d sum_i sum_j scene[d][y + i - crop/2][x + j - crop/2] * kern[r][d][i][j]
-// on v_mfma_f32_16x16x32_bf16, and the largest sum of the env with its flat index.
+// on v_mfma_f32_16x16x32_bf16, and the largest sum of the env with its flat index.  The main loop described below is
+// cr_forward / cr_slice of mre_correlate_core.h, which the training kernels (mre_correlate_grad.hip) share; with the pivot
+// at crop - 1 - crop/2 and flipped kernels this kernel is also grad_scene.
 //
 //   k_correlate<RT, VK>   one workgroup of 256 lanes (4 waves) per (env, tile of 16 pixel rows x 32 pixel columns); a wave
 //                      owns 8 consecutive columns of the 16 rows.
@@ -29,22 +31,13 @@
 // `Better` is a total order on (value, index) -- greater value, then lower index -- so the reductions give the first
 // occurrence of the maximum in whatever order they combine; a NaN is never better than anything.  No atomics; every
 // output element and every slot is written exactly once.  Offsets into logits and kern are formed in 64 bits.
-#include "mre_correlate.h"
+#include "mre_correlate_core.h"
 
 #include "mre_warp_input_point.h"
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int PITCH = 112;                              // bf16 elements of a patch row: 14 slots of 16 bytes
-constexpr int PCOLS = 96;                               // staged columns: 24 (wave) + 32 (j0) + 24 (g) + 15 (window) + 1
-constexpr int PROWS = CR_TILE_H + CR_MAX_CROP - 1;      // 79
 constexpr int NO_INDEX = 0x7FFFFFFF;
-constexpr uint32_t MAX_GRID_Y = 65535, MAX_GRID = 1u << 20;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct Best {
   float v;
@@ -63,37 +56,6 @@ __device__ __forceinline__ Best wave_best(Best b) {
   return b;
 }
 
-__device__ __forceinline__ bf16x8 frag(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-  const u32x4 u = {a, b, c, d};
-  return __builtin_bit_cast(bf16x8, u);
-}
-
-// A fragments of one step: the lane's 8 taps j .. j + 7 of row `krow` of each of its RT rotations.  A tap past the row's
-// end is zero (the scene values it would meet are real).  A padded rotation reads the last real one's row, clamped by
-// rot_off: its sums reach no output, so they need not be zero.
-template <int RT, bool VK>
-__device__ __forceinline__ void load_rows(bf16x8 (&fa)[RT], const uint16_t* krow, const size_t (&rot_off)[RT], int j, int c) {
-#pragma unroll
-  for (int rt = 0; rt < RT; rt++) {
-    if (VK) {
-      const bool ok = j < c;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(krow + rot_off[rt] + (ok ? j : 0));
-      fa[rt] = frag(ok ? v.x : 0u, ok ? v.y : 0u, ok ? v.z : 0u, ok ? v.w : 0u);
-    } else {
-      // c and j are even: the taps of a pair are inside the row together or not at all (four masks, not eight)
-      uint32_t v[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const bool ok = j + 2 * k < c;
-        const uint16_t* src = krow + rot_off[rt] + (ok ? j + 2 * k : 0);
-        const uint32_t lo = src[0], hi = src[1];
-        v[k] = ok ? (lo | (hi << 16)) : 0u;
-      }
-      fa[rt] = frag(v[0], v[1], v[2], v[3]);
-    }
-  }
-}
-
 template <int RT, bool VK>
 __global__ void __launch_bounds__(NT, 2) k_correlate(CorrelateArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t patch[PROWS * PITCH];
@@ -101,9 +63,8 @@ __global__ void __launch_bounds__(NT, 2) k_correlate(CorrelateArgs a) {
   const uint32_t t = threadIdx.x, lane = t & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(t >> 6));   // the same in every lane of a wave: scalar
   const uint32_t lr = lane & 15, g = lane >> 4;
-  const int R = (int)a.rot, D = (int)a.depth, H = (int)a.h, W = (int)a.w, c = (int)a.crop, half = c / 2;
+  const int R = (int)a.rot, H = (int)a.h, W = (int)a.w;
   const uint32_t tiles = a.tiles_x * a.tiles_y;
-  const int prow_n = CR_TILE_H + c - 1;
   // one workgroup per (tile, env): blockIdx.x the tile, y and z the env (no loop over items: what it would keep alive
   // across the body does not fit the scalar registers)
   const uint32_t e = blockIdx.z * gridDim.y + blockIdx.y, tile = blockIdx.x;
@@ -111,68 +72,8 @@ __global__ void __launch_bounds__(NT, 2) k_correlate(CorrelateArgs a) {
   {
     const int y0 = (int)(tile / a.tiles_x) * CR_TILE_H, x0 = (int)(tile % a.tiles_x) * CR_TILE_W;
     const int xw = x0 + 8 * wv;   // the wave's first pixel column
-    const uint16_t* scene_e = a.scene + (size_t)e * D * H * W;
-    const uint16_t* kern_e = a.kern + (size_t)e * R * D * c * c;
-    // taps that can meet the scene: rows i of the tile, chunks j0 of the wave
-    const int i_lo = max(0, half - y0 - (CR_TILE_H - 1)), i_hi = min(c, H + half - y0);
     f32x4 acc[RT][8];
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-      for (int p = 0; p < 8; p++) acc[rt][p] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // rows of kern of this lane's rotations (clamped: a padded rotation reads a real row)
-    size_t rot_off[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++) rot_off[rt] = (size_t)min(16 * rt + (int)lr, R - 1) * D * c * c;
-    for (int d = 0; d < D; d++) {
-      __syncthreads();   // the patch of the slice before is no longer read
-      const uint16_t* plane = scene_e + (size_t)d * H * W;
-      for (int q = (int)t; q < prow_n * (PCOLS / 2); q += NT) {
-        const int pr = q / (PCOLS / 2), pc = 2 * (q - pr * (PCOLS / 2));
-        const int y = y0 - half + pr, x = x0 - half + pc;
-        const bool row_in = y >= 0 && y < H;
-        const bool in0 = row_in && x >= 0 && x < W, in1 = row_in && x + 1 >= 0 && x + 1 < W;
-        const uint16_t* src = plane + (size_t)(row_in ? y : 0) * W;   // a cell outside reads cell 0 of a row that exists
-        const uint32_t lo = src[in0 ? x : 0], hi = src[in1 ? x + 1 : 0];
-        *reinterpret_cast<uint32_t*>(patch + pr * PITCH + pc) = (in0 ? lo : 0u) | ((in1 ? hi : 0u) << 16);
-      }
-      __syncthreads();
-      const uint16_t* kd = kern_e + (size_t)d * c * c;
-      // the steps (i, j0) of this slice, flattened, so that the kernel rows of a step are loaded one step ahead of the
-      // MFMAs that use them (a chunk the wave skips still loads: the loads stay in bounds and cost nothing beside it)
-      const int chunks = (c + 31) / 32, steps = (i_hi - i_lo) * chunks;
-      bf16x8 fa[RT];
-      if (steps > 0) load_rows<RT, VK>(fa, kd + (size_t)i_lo * c, rot_off, 8 * (int)g, c);
-      for (int s = 0, i = i_lo, j0 = 0; s < steps; s++) {
-        int i_next = i, j_next = j0 + 32;
-        if (j_next >= c) { j_next = 0; i_next = i + 1; }
-        bf16x8 fn[RT];
-        load_rows<RT, VK>(fn, kd + (size_t)min(i_next, i_hi - 1) * c, rot_off, j_next + 8 * (int)g, c);
-        // the chunk's taps meet columns xw + j0 - half .. + 38 of the scene
-        if (xw + j0 - half + 38 >= 0 && xw + j0 - half < W) {
-          const uint16_t* prow = patch + ((int)lr + i) * PITCH + 8 * wv + 8 * (int)g + j0;
-          const u32x4 w0 = *reinterpret_cast<const u32x4*>(prow);
-          const u32x4 w1 = *reinterpret_cast<const u32x4*>(prow + 8);
-          const uint32_t win[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-#pragma unroll
-          for (int p = 0; p < 8; p++) {
-            const int q = p >> 1;
-            bf16x8 fb;
-            if (p & 1)
-              fb = frag(__builtin_amdgcn_alignbit(win[q + 1], win[q], 16), __builtin_amdgcn_alignbit(win[q + 2], win[q + 1], 16),
-                        __builtin_amdgcn_alignbit(win[q + 3], win[q + 2], 16), __builtin_amdgcn_alignbit(win[q + 4], win[q + 3], 16));
-            else
-              fb = frag(win[q], win[q + 1], win[q + 2], win[q + 3]);
-#pragma unroll
-            for (int rt = 0; rt < RT; rt++)
-              acc[rt][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[rt], fb, acc[rt][p], 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int rt = 0; rt < RT; rt++) fa[rt] = fn[rt];
-        i = i_next; j0 = j_next;
-      }
-    }
+    cr_forward<RT, VK>(acc, patch, a, e, y0, x0, t, wv, lr, g);
     // epilogue: lane (lr, g) holds rotations 16 rt + 4 g + q, pixel row y0 + lr, columns xw .. xw + 7
     const int y = y0 + (int)lr;
     Best b = {-__builtin_inff(), NO_INDEX};

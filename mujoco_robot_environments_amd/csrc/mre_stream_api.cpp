@@ -402,7 +402,7 @@ extern "C" int mre_correlate(void* stream, const uint16_t* scene, const uint16_t
   a.scene = scene; a.kern = kern; a.logits = logits; a.best_index = best_index; a.best_value = best_value;
   a.workspace = workspace;
   a.n = (uint32_t)n; a.rot = (uint32_t)rotations; a.depth = (uint32_t)depth; a.h = (uint32_t)h; a.w = (uint32_t)w;
-  a.crop = (uint32_t)crop;
+  a.crop = (uint32_t)crop; a.pivot = (uint32_t)crop / 2;
   a.tiles_x = cr_tiles(a.w, CR_TILE_W); a.tiles_y = cr_tiles(a.h, CR_TILE_H);
   a.bf16 = dtype == MRE_BF16 ? 1u : 0u;
   // the wide accesses: a lane's 8 taps of a kernel row (every row then starts at a multiple of 8 elements), and its 8
@@ -410,6 +410,168 @@ extern "C" int mre_correlate(void* stream, const uint16_t* scene, const uint16_t
   a.vec_kern = (crop % 8 == 0 && !((uintptr_t)kern & 15)) ? 1u : 0u;
   a.vec_out = (logits && w % 8 == 0 && !((uintptr_t)logits & 15)) ? 1u : 0u;
   mre_launch_correlate(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+// ---- training the place head (csrc/mre_correlate_grad.hip): the loss, its gradient g, and the gradients of any g
+// the ranges the five entries share with mre_correlate; an empty string when they hold
+static std::string correlate_ranges(int n, int rotations, int depth, int h, int w, int crop) {
+  if (n < 0) return ": n >= 0";
+  if (rotations < 1 || rotations > CR_MAX_ROT) return ": 1 <= rotations <= 64";
+  if (depth < 1 || depth > CR_MAX_DEPTH) return ": 1 <= depth <= 16";
+  if (crop < 2 || crop > CR_MAX_CROP || (crop & 1)) return ": crop must be even, 2 <= crop <= 64";
+  if (h < 1 || w < 1 || h > CR_MAX_DIM || w > CR_MAX_DIM) return ": 1 <= h, w <= 4096";
+  if (!correlate_shape_ok(n, rotations, h, w)) return ": rotations * h * w must be below 2^31";
+  return "";
+}
+
+static void correlate_forward_args(CorrelateArgs& a, const uint16_t* scene, const uint16_t* kern, int n, int rotations,
+                                   int depth, int h, int w, int crop, void* workspace) {
+  memset(&a, 0, sizeof(a));
+  a.scene = scene; a.kern = kern; a.workspace = workspace;
+  a.n = (uint32_t)n; a.rot = (uint32_t)rotations; a.depth = (uint32_t)depth; a.h = (uint32_t)h; a.w = (uint32_t)w;
+  a.crop = (uint32_t)crop; a.pivot = (uint32_t)crop / 2;
+  a.tiles_x = cr_tiles(a.w, CR_TILE_W); a.tiles_y = cr_tiles(a.h, CR_TILE_H);
+  a.vec_kern = (crop % 8 == 0 && !((uintptr_t)kern & 15)) ? 1u : 0u;
+}
+
+extern "C" int mre_correlate_loss(void* stream, const uint16_t* scene, const uint16_t* kern, int n, int rotations, int depth,
+                                  int h, int w, int crop, const int64_t* target, float* lse, float* target_logit,
+                                  float* loss, void* workspace, size_t workspace_bytes) {
+  const std::string wh("mre_correlate_loss");
+  const std::string bad = correlate_ranges(n, rotations, depth, h, w, crop);
+  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  if (!scene || !kern || !target) return fail(MRE_ERR_ARG, wh + ": null scene, kern or target");
+  if (((uintptr_t)scene & 1) || ((uintptr_t)kern & 1)) return fail(MRE_ERR_ARG, wh + ": scene and kern must be 2-byte aligned");
+  if ((uintptr_t)target & 7) return fail(MRE_ERR_ARG, wh + ": target must be 8-byte aligned");
+  if (!lse || !target_logit || !loss) return fail(MRE_ERR_ARG, wh + ": null lse, target_logit or loss");
+  if (((uintptr_t)lse & 3) || ((uintptr_t)target_logit & 3) || ((uintptr_t)loss & 3))
+    return fail(MRE_ERR_ARG, wh + ": lse, target_logit and loss must be 4-byte aligned");
+  const size_t need = correlate_workspace(n, h, w);
+  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need)
+    return fail(MRE_ERR_ARG, wh + ": workspace must be non-NULL, 16-byte aligned and as large as mre_correlate_workspace says");
+  // (lengths below 2^54, as in mre_correlate)
+  const size_t cells = (size_t)h * w;
+  const ByteRange ins[3] = {{scene, 2 * (size_t)n * depth * cells}, {kern, 2 * (size_t)n * rotations * depth * crop * crop},
+                            {target, 8 * (size_t)n}};
+  const ByteRange outs[4] = {{lse, 4 * (size_t)n}, {target_logit, 4 * (size_t)n}, {loss, 4 * (size_t)n}, {workspace, need}};
+  if (ranges_overlap(ins, outs)) return fail(MRE_ERR_ARG, wh + ": an output or the workspace overlaps an input");
+  if (n == 0) return MRE_OK;
+  if (!is_device_ptr(scene) || !is_device_ptr(kern) || !is_device_ptr(target) || !is_device_ptr(lse) ||
+      !is_device_ptr(target_logit) || !is_device_ptr(loss) || !is_device_ptr(workspace))
+    return fail(MRE_ERR_ARG, wh + ": scene, kern, target, the outputs and the workspace must be device pointers");
+  CorrelateLossArgs a;
+  memset(&a, 0, sizeof(a));
+  correlate_forward_args(a.fwd, scene, kern, n, rotations, depth, h, w, crop, workspace);
+  a.target = target; a.lse = lse; a.target_logit = target_logit; a.loss = loss;
+  mre_launch_correlate_loss(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+extern "C" int mre_correlate_dlogits(void* stream, const uint16_t* scene, const uint16_t* kern, int n, int rotations,
+                                     int depth, int h, int w, int crop, const int64_t* target, const float* lse,
+                                     const float* weight, uint16_t* g) {
+  const std::string wh("mre_correlate_dlogits");
+  const std::string bad = correlate_ranges(n, rotations, depth, h, w, crop);
+  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  if (!scene || !kern || !target || !lse) return fail(MRE_ERR_ARG, wh + ": null scene, kern, target or lse");
+  if (((uintptr_t)scene & 1) || ((uintptr_t)kern & 1)) return fail(MRE_ERR_ARG, wh + ": scene and kern must be 2-byte aligned");
+  if ((uintptr_t)target & 7) return fail(MRE_ERR_ARG, wh + ": target must be 8-byte aligned");
+  if (((uintptr_t)lse & 3) || ((uintptr_t)weight & 3)) return fail(MRE_ERR_ARG, wh + ": lse and weight must be 4-byte aligned");
+  if (!g || ((uintptr_t)g & 1)) return fail(MRE_ERR_ARG, wh + ": g must be non-NULL and 2-byte aligned");
+  const size_t cells = (size_t)h * w;
+  const ByteRange ins[5] = {{scene, 2 * (size_t)n * depth * cells}, {kern, 2 * (size_t)n * rotations * depth * crop * crop},
+                            {target, 8 * (size_t)n}, {lse, 4 * (size_t)n}, {weight, 4 * (size_t)n}};
+  const ByteRange outs[1] = {{g, 2 * (size_t)n * rotations * cells}};
+  if (ranges_overlap(ins, outs)) return fail(MRE_ERR_ARG, wh + ": g overlaps an input");
+  if (n == 0) return MRE_OK;
+  if (!is_device_ptr(scene) || !is_device_ptr(kern) || !is_device_ptr(target) || !is_device_ptr(lse) ||
+      (weight && !is_device_ptr(weight)) || !is_device_ptr(g))
+    return fail(MRE_ERR_ARG, wh + ": scene, kern, target, lse, weight and g must be device pointers");
+  CorrelateLossArgs a;
+  memset(&a, 0, sizeof(a));
+  correlate_forward_args(a.fwd, scene, kern, n, rotations, depth, h, w, crop, nullptr);
+  a.target = target; a.lse_in = lse; a.weight = weight; a.g = g;
+  a.vec_g = (w % 8 == 0 && !((uintptr_t)g & 15)) ? 1u : 0u;
+  mre_launch_correlate_dlogits(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+// grad_scene keeps the flipped kernels (bfloat16) there, grad_kern the partial tiles of its cr_split(h) workgroups (float32)
+static size_t correlate_grad_workspace(int n, int rotations, int depth, int h, int crop) {
+  const size_t per = (size_t)n * rotations * depth * crop * crop, split = cr_split((uint32_t)h);
+  const size_t bytes = (std::max(2 * per, split > 1 ? 4 * split * per : (size_t)0) + 15) & ~(size_t)15;
+  return bytes ? bytes : 16;
+}
+
+extern "C" int mre_correlate_grad_workspace(int n, int rotations, int depth, int h, int w, int crop, size_t* bytes) {
+  const std::string wh("mre_correlate_grad_workspace");
+  if (!bytes) return fail(MRE_ERR_ARG, wh + ": null bytes");
+  const std::string bad = correlate_ranges(n, rotations, depth, h, w, crop);
+  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  *bytes = correlate_grad_workspace(n, rotations, depth, h, crop);
+  return MRE_OK;
+}
+
+// the checks the two gradient entries share: `other` is scene (grad_kern) or kern (grad_scene), of other_bytes
+static int correlate_grad_check(const std::string& wh, const char* other_name, const uint16_t* g, const uint16_t* other,
+                                size_t other_bytes, int n, int rotations, int depth, int h, int w, int crop, float* out,
+                                size_t out_bytes, void* workspace, size_t workspace_bytes) {
+  const std::string bad = correlate_ranges(n, rotations, depth, h, w, crop);
+  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  if (!g || !other) return fail(MRE_ERR_ARG, wh + ": null g or " + other_name);
+  if (((uintptr_t)g & 1) || ((uintptr_t)other & 1)) return fail(MRE_ERR_ARG, wh + ": g and " + other_name + " must be 2-byte aligned");
+  if (!out || ((uintptr_t)out & 3)) return fail(MRE_ERR_ARG, wh + ": the output must be non-NULL and 4-byte aligned");
+  const size_t need = correlate_grad_workspace(n, rotations, depth, h, crop);
+  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need)
+    return fail(MRE_ERR_ARG, wh + ": workspace must be non-NULL, 16-byte aligned and as large as mre_correlate_grad_workspace says");
+  // (n < 2^31 envs of at most 4 x 4 x 64 x 16 x 64 x 64 B of workspace: below 2^60)
+  const ByteRange ins[2] = {{g, 2 * (size_t)n * rotations * h * w}, {other, other_bytes}};
+  const ByteRange outs[2] = {{out, out_bytes}, {workspace, need}};
+  if (ranges_overlap(ins, outs)) return fail(MRE_ERR_ARG, wh + ": the output or the workspace overlaps an input");
+  if (n == 0) return MRE_OK;
+  if (!is_device_ptr(g) || !is_device_ptr(other) || !is_device_ptr(out) || !is_device_ptr(workspace))
+    return fail(MRE_ERR_ARG, wh + ": g, " + other_name + ", the output and the workspace must be device pointers");
+  return MRE_OK;
+}
+
+static void correlate_grad_args(CorrelateGradArgs& a, const uint16_t* g, int n, int rotations, int depth, int h, int w, int crop,
+                                float* out, void* workspace) {
+  memset(&a, 0, sizeof(a));
+  a.g = g; a.out = out; a.workspace = workspace;
+  a.n = (uint32_t)n; a.rot = (uint32_t)rotations; a.depth = (uint32_t)depth; a.h = (uint32_t)h; a.w = (uint32_t)w;
+  a.crop = (uint32_t)crop;
+}
+
+extern "C" int mre_correlate_grad_scene(void* stream, const uint16_t* g, const uint16_t* kern, int n, int rotations, int depth,
+                                        int h, int w, int crop, float* grad_scene, void* workspace, size_t workspace_bytes) {
+  const int rc = correlate_grad_check("mre_correlate_grad_scene", "kern", g, kern,
+                                      2 * (size_t)std::max(n, 0) * rotations * depth * crop * crop, n, rotations, depth, h, w,
+                                      crop, grad_scene, 4 * (size_t)std::max(n, 0) * depth * h * w, workspace, workspace_bytes);
+  if (rc != MRE_OK || n == 0) return rc;
+  CorrelateGradArgs a;
+  correlate_grad_args(a, g, n, rotations, depth, h, w, crop, grad_scene, workspace);
+  a.kern = kern;
+  a.vec_out = (w % 8 == 0 && !((uintptr_t)grad_scene & 15)) ? 1u : 0u;
+  mre_launch_correlate_grad_scene(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+extern "C" int mre_correlate_grad_kern(void* stream, const uint16_t* g, const uint16_t* scene, int n, int rotations, int depth,
+                                       int h, int w, int crop, float* grad_kern, void* workspace, size_t workspace_bytes) {
+  const int rc = correlate_grad_check("mre_correlate_grad_kern", "scene", g, scene, 2 * (size_t)std::max(n, 0) * depth * h * w, n,
+                                      rotations, depth, h, w, crop, grad_kern,
+                                      4 * (size_t)std::max(n, 0) * rotations * depth * crop * crop, workspace, workspace_bytes);
+  if (rc != MRE_OK || n == 0) return rc;
+  CorrelateGradArgs a;
+  correlate_grad_args(a, g, n, rotations, depth, h, w, crop, grad_kern, workspace);
+  a.scene = scene;
+  a.vec_g = (w % 8 == 0 && !((uintptr_t)g & 15)) ? 1u : 0u;
+  mre_launch_correlate_grad_kern(&a, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
 }

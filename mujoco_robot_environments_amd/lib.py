@@ -36,7 +36,7 @@ UNITS = [("kernels", STEP_SOURCE, []), ("kernels_large", STEP_SOURCE, ["-DMRE_LA
          ("render", "mre_render.hip", []), ("records", "mre_records.hip", []),
          ("labels", "mre_labels.hip", []), ("heightmap", "mre_heightmap.hip", []),
          ("warp", "mre_warp.hip", []), ("warp_inputs", "mre_warp_inputs.hip", []),
-         ("correlate", "mre_correlate.hip", []), ("api", "mre_api.cpp", []), ("stream_api", "mre_stream_api.cpp", []),
+         ("correlate", "mre_correlate.hip", []), ("correlate_grad", "mre_correlate_grad.hip", []), ("api", "mre_api.cpp", []), ("stream_api", "mre_stream_api.cpp", []),
          ("sched", "mre_sched.cpp", []), ("model", "mre_model.cpp", [])]
 
 MRE_NQ, MRE_NV, MRE_NU, MRE_NQ_PAD, MRE_NV_PAD, MRE_MAX_PROPS = 43, 39, 8, 44, 40, 4
@@ -82,6 +82,11 @@ _SIGNATURES = {
     "mre_warp_inputs": [vp, fp, fp, ci, ci, ci, fp, fp, ci, ci, ci, ci, fp, fp, fp, ci, fp],
     "mre_correlate_workspace": [ci, ci, ci, ci, C.POINTER(sz)],
     "mre_correlate": [vp, fp, fp, ci, ci, ci, ci, ci, ci, ci, fp, fp, fp, fp, sz],
+    "mre_correlate_loss": [vp, fp, fp, ci, ci, ci, ci, ci, ci, fp, fp, fp, fp, fp, sz],
+    "mre_correlate_dlogits": [vp, fp, fp, ci, ci, ci, ci, ci, ci, fp, fp, fp, fp],
+    "mre_correlate_grad_workspace": [ci, ci, ci, ci, ci, ci, C.POINTER(sz)],
+    "mre_correlate_grad_scene": [vp, fp, fp, ci, ci, ci, ci, ci, ci, fp, fp, sz],
+    "mre_correlate_grad_kern": [vp, fp, fp, ci, ci, ci, ci, ci, ci, fp, fp, sz],
 }
 EXPORTS = list(_SIGNATURES)
 # status bits of mre_varint_unpack_rows (include/mre.h)
@@ -117,7 +122,7 @@ def needs_build() -> bool:
 
 def compile_and_link(so: str, objdir: str, suffix: str = "", csrc: Optional[str] = None, extra=(), step_extra=(),
                      verbose: bool = False) -> str:
-    """Compile UNITS for gfx950, all at once (15 compilers: below the 16 CPUs a build may count on), and link them to `so`.
+    """Compile UNITS for gfx950, all at once (16 compilers: the 16 CPUs a build may count on), and link them to `so`.
     Objects go to objdir as NAME + suffix + .o; `extra` flags go to every unit, `step_extra` to the instantiations of
     the step kernel only.  csrc may be another checkout's sources: units that checkout lacks are skipped."""
     csrc = csrc or _CSRC

@@ -27,6 +27,11 @@ cross-correlated with its own rotated crop features by ``mre_correlate`` (csrc/m
 best (rotation, row, column) per env without the logits ever being written; ``decode_place`` and ``cell_2_world`` turn it
 into cells, rotation bins and world positions (``BatchedRearrangementEnv.transporter_place``).
 
+``place_loss``: what trains that head -- the softmax cross-entropy of every env's logits against a target cell
+(``encode_place``) as a ``torch.autograd.Function`` over ``mre_correlate_loss``, ``mre_correlate_dlogits``,
+``mre_correlate_grad_scene`` and ``mre_correlate_grad_kern`` (csrc/mre_correlate_grad.hip), without a logit stored;
+``correlate_backward`` is the gradient pair alone, for any loss (``BatchedRearrangementEnv.transporter_loss``).
+
 The kernels are enqueued on torch's current stream; nothing here synchronises.
 """
 from __future__ import annotations
@@ -758,7 +763,7 @@ def correlate(scene: torch.Tensor, kernels: torch.Tensor, *, logits=None, best: 
 
     Contiguous CUDA bfloat16 inputs are one call of ``mre_correlate`` (csrc/mre_correlate.hip, bf16 matrix cores, float32
     accumulation) on torch's current stream with a ``torch.empty`` workspace, without a synchronise; anything else is
-    computed by ``correlate_reference``.  No autograd."""
+    computed by ``correlate_reference``.  No autograd: ``place_loss`` and ``correlate_backward`` are the training path."""
     n, rot, depth, h, w, crop = _correlate_args(scene, kernels, logits, best)
     on_device = all(t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() for t in (scene, kernels))
     if not on_device:
@@ -798,6 +803,203 @@ def decode_place(index, shape, n_rotations: int):
     if is_tensor:
         return cells, bins, angles
     return cells.numpy(), bins.numpy(), angles.numpy()
+
+
+def encode_place(cells, bins, shape):
+    """The inverse of ``decode_place``: the flat index (bin * rows + row) * columns + column [N] of ``cells`` [N, 2]
+    (column, row) at rotation ``bins`` [N] over ``shape`` = (rows, columns) -- the target ``place_loss`` takes.  A cell
+    outside the map gives -1, which ``place_loss`` answers with NaN.  A torch tensor for tensors, a numpy array for
+    anything else."""
+    rows, cols = int(shape[0]), int(shape[1])
+    is_tensor = isinstance(cells, torch.Tensor)
+    c = cells.to(torch.int64) if is_tensor else torch.as_tensor(np.asarray(cells, np.int64))
+    b = torch.as_tensor(bins if isinstance(bins, torch.Tensor) else np.asarray(bins, np.int64)).to(torch.int64).to(c.device)
+    col, row = c[..., 0], c[..., 1]
+    inside = (col >= 0) & (col < cols) & (row >= 0) & (row < rows) & (b >= 0)
+    index = torch.where(inside, (b * rows + row) * cols + col, torch.full_like(col, -1))
+    return index if is_tensor else index.numpy()
+
+
+# ------------------------------------------------------------------------------------------- training the place head
+def _place_args(scene, kernels):
+    return _correlate_args(scene, kernels, None, True)
+
+
+def _as_target(target, n, dev):
+    t = torch.as_tensor(target).to(device=dev, dtype=torch.int64).contiguous()
+    if tuple(t.shape) != (n,):
+        raise ValueError("target must be [N]")
+    return t
+
+
+def _as_weight(weight, n, dev):
+    if weight is None:
+        return None
+    w = torch.as_tensor(weight).to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(w.shape) != (n,):
+        raise ValueError("weight must be [N]")
+    return w
+
+
+def _logits_f32(scene, kernels, n, rot, depth, h, w, crop):
+    """The conv2d line of ``correlate_reference``, differentiable: float32 [n, rot, h, w]"""
+    x = scene.to(torch.float32).reshape(1, n * depth, h, w)
+    k = kernels.to(torch.float32).reshape(n * rot, depth, crop, crop)
+    if n == 0:   # (conv2d takes no empty group; the sums keep the empty result in the graph)
+        return (x.sum() + k.sum()) * torch.zeros((0, rot, h, w), dtype=torch.float32, device=scene.device)
+    return torch.nn.functional.conv2d(x, k, padding=crop // 2, groups=n)[..., :h, :w].reshape(n, rot, h, w)
+
+
+def place_loss_reference(scene: torch.Tensor, kernels: torch.Tensor, target, weight=None) -> torch.Tensor:
+    """The statement of ``place_loss`` (include/mre.h, mre_correlate_loss) in plain float32 torch, on any device and for
+    any dtype and strides, differentiable by torch itself: weight * (logsumexp of the env's R * rows * columns logits
+    minus the logit at flat index ``target``), float32 [N]; NaN where ``target`` is outside, and the gradient is then that
+    of the logsumexp alone.  The fallback of ``place_loss``."""
+    n, rot, depth, h, w, crop = _place_args(scene, kernels)
+    t = _as_target(target, n, scene.device)
+    wgt = _as_weight(weight, n, scene.device)
+    flat = _logits_f32(scene, kernels, n, rot, depth, h, w, crop).reshape(n, rot * h * w)
+    inside = (t >= 0) & (t < rot * h * w)
+    at = flat.gather(1, torch.where(inside, t, torch.zeros_like(t))[:, None])[:, 0]
+    loss = torch.logsumexp(flat, dim=1) - torch.where(inside, at, torch.full_like(at, float("nan")))
+    return loss if wgt is None else wgt * loss
+
+
+def _backward_args(scene, kernels, dlogits):
+    n, rot, depth, h, w, crop = _place_args(scene, kernels)
+    if tuple(dlogits.shape) != (n, rot, h, w) or dlogits.device != scene.device:
+        raise ValueError("dlogits must be [N, R, rows, columns] on the device of scene")
+    return n, rot, depth, h, w, crop
+
+
+def correlate_backward_reference(scene: torch.Tensor, kernels: torch.Tensor, dlogits: torch.Tensor):
+    """The statement of ``correlate_backward`` (include/mre.h, mre_correlate_grad_scene / _kern) in plain float32 torch:
+    torch's own gradients of sum(dlogits * logits) through the ``conv2d`` of ``correlate_reference``, for any device,
+    dtype and strides.  (grad_scene [N, D, rows, columns], grad_kernels [N, R, D, crop, crop]), float32."""
+    n, rot, depth, h, w, crop = _backward_args(scene, kernels, dlogits)
+    with torch.enable_grad():
+        s = scene.detach().to(torch.float32).clone().requires_grad_(True)
+        k = kernels.detach().to(torch.float32).clone().requires_grad_(True)
+        out = _logits_f32(s, k, n, rot, depth, h, w, crop)
+        gs, gk = torch.autograd.grad(out, (s, k), dlogits.detach().to(torch.float32))
+    return gs, gk
+
+
+def _on_device(*tensors) -> bool:
+    return all(t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() for t in tensors)
+
+
+def correlate_backward(scene: torch.Tensor, kernels: torch.Tensor, dlogits: torch.Tensor):
+    """The gradients of sum(dlogits * logits) of ``correlate`` with respect to ``scene`` and ``kernels``, for any
+    ``dlogits`` [N, R, rows, columns]: (grad_scene float32 [N, D, rows, columns], grad_kernels float32 [N, R, D, crop,
+    crop]),
+      grad_kernels[e, r, d, i, j] = sum over y, x of dlogits[e, r, y, x] * scene[e, d, y + i - crop/2, x + j - crop/2]
+      grad_scene[e, d, v, u] = sum over r, i, j of dlogits[e, r, v - i + crop/2, u - j + crop/2] * kernels[e, r, d, i, j]
+    with cells outside counting as 0.  Contiguous CUDA bfloat16 tensors are one call each of ``mre_correlate_grad_scene``
+    and ``mre_correlate_grad_kern`` (csrc/mre_correlate_grad.hip: the forward's implicit GEMM with the operands in other
+    roles) on torch's current stream with a ``torch.empty`` workspace they share (7 MB per env at the workload's shape),
+    without a synchronise; anything else is computed by ``correlate_backward_reference``."""
+    n, rot, depth, h, w, crop = _backward_args(scene, kernels, dlogits)
+    if not _on_device(scene, kernels, dlogits):
+        return correlate_backward_reference(scene, kernels, dlogits)
+    return _grad_scene(scene, kernels, dlogits), _grad_kernels(scene, kernels, dlogits)
+
+
+def _grad_call(name, g, other, out, shape):
+    n, rot, depth, h, w, crop = shape
+    if n:
+        L = _lib.lib()
+        nbytes = C.c_size_t(0)
+        _lib.check(L.mre_correlate_grad_workspace(n, rot, depth, h, w, crop, C.byref(nbytes)), "mre_correlate_grad_workspace")
+        work = torch.empty((nbytes.value,), dtype=torch.uint8, device=g.device)
+        with _stream_on(g.device) as stream:
+            _lib.check(getattr(L, name)(stream, g.data_ptr(), other.data_ptr(), n, rot, depth, h, w, crop, out.data_ptr(),
+                                        work.data_ptr(), nbytes.value), name)
+    return out
+
+
+def _grad_scene(scene, kernels, g):
+    shape = _place_args(scene, kernels)
+    out = torch.empty(tuple(scene.shape), dtype=torch.float32, device=scene.device)
+    return _grad_call("mre_correlate_grad_scene", g.detach(), kernels.detach(), out, shape)
+
+
+def _grad_kernels(scene, kernels, g):
+    shape = _place_args(scene, kernels)
+    out = torch.empty(tuple(kernels.shape), dtype=torch.float32, device=scene.device)
+    return _grad_call("mre_correlate_grad_kern", g.detach(), scene.detach(), out, shape)
+
+
+# lse, target_logit and loss float32 [N] of mre_correlate_loss (unweighted)
+PlaceLoss = collections.namedtuple("PlaceLoss", ["lse", "target_logit", "loss"])
+
+
+def place_loss_forward(scene, kernels, target) -> PlaceLoss:
+    """``mre_correlate_loss`` on contiguous CUDA bfloat16 ``scene`` and ``kernels`` and an int64 CUDA ``target`` [N]: the
+    logsumexp of every env's logits, the logit at ``target`` and their difference, without a logit being stored."""
+    n, rot, depth, h, w, crop = _place_args(scene, kernels)
+    dev = scene.device
+    out = torch.empty((3, n), dtype=torch.float32, device=dev)
+    if n:
+        L = _lib.lib()
+        nbytes = C.c_size_t(0)
+        _lib.check(L.mre_correlate_workspace(n, rot, h, w, C.byref(nbytes)), "mre_correlate_workspace")
+        work = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+        with _stream_on(dev) as stream:
+            _lib.check(L.mre_correlate_loss(stream, scene.detach().data_ptr(), kernels.detach().data_ptr(), n, rot, depth, h, w,
+                                            crop, target.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                            work.data_ptr(), nbytes.value), "mre_correlate_loss")
+    return PlaceLoss(out[0], out[1], out[2])
+
+
+def place_dlogits(scene, kernels, target, lse, weight=None) -> torch.Tensor:
+    """``mre_correlate_dlogits``: g = weight * (softmax - one-hot of ``target``) as bfloat16 [N, R, rows, columns], from
+    the ``lse`` of ``place_loss_forward``; the logits are computed again, not kept."""
+    n, rot, depth, h, w, crop = _place_args(scene, kernels)
+    g = torch.empty((n, rot, h, w), dtype=torch.bfloat16, device=scene.device)
+    if n:
+        with _stream_on(scene.device) as stream:
+            _lib.check(_lib.lib().mre_correlate_dlogits(
+                stream, scene.detach().data_ptr(), kernels.detach().data_ptr(), n, rot, depth, h, w, crop, target.data_ptr(),
+                lse.data_ptr(), None if weight is None else weight.data_ptr(), g.data_ptr()), "mre_correlate_dlogits")
+    return g
+
+
+class _PlaceLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scene, kernels, target, weight):
+        out = place_loss_forward(scene, kernels, target)
+        ctx.save_for_backward(scene, kernels, target, out.lse)
+        ctx.weight = weight
+        return out.loss if weight is None else weight * out.loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        scene, kernels, target, lse = ctx.saved_tensors
+        wgt = grad.to(torch.float32) if ctx.weight is None else grad.to(torch.float32) * ctx.weight
+        g = place_dlogits(scene, kernels, target, lse, wgt.contiguous())
+        gs = _grad_scene(scene, kernels, g) if ctx.needs_input_grad[0] else None
+        gk = _grad_kernels(scene, kernels, g) if ctx.needs_input_grad[1] else None
+        return gs, gk, None, None
+
+
+def place_loss(scene: torch.Tensor, kernels: torch.Tensor, target, weight=None) -> torch.Tensor:
+    """The training loss of a Transporter's place head, float32 [N]: per env the softmax cross-entropy of the R * rows *
+    columns logits of ``correlate`` against the cell ``target`` [N] (int64 flat index (r * rows + y) * columns + x, as
+    ``encode_place`` makes it), times ``weight`` [N] (None: 1),
+      loss[e] = weight[e] * (log sum over cells of exp(logit[e, cell]) - logit[e, target[e]])
+    and NaN where ``target`` is outside (the gradient is then that of the logsumexp alone).  Differentiable with respect to
+    ``scene`` and ``kernels``.
+
+    Contiguous CUDA bfloat16 inputs take the kernels of csrc/mre_correlate_grad.hip on torch's current stream, without a
+    synchronise and without a logit stored: forward is ``mre_correlate_loss`` and keeps scene, kernels, target and the
+    logsumexp; backward computes the logits again for g = weight * grad * (softmax - one-hot) in bfloat16
+    (``mre_correlate_dlogits``) and hands g to ``mre_correlate_grad_scene`` and ``mre_correlate_grad_kern``, whose float32
+    results autograd casts to the inputs' dtype.  Anything else goes through ``place_loss_reference``."""
+    n, rot, depth, h, w, crop = _place_args(scene, kernels)
+    if not _on_device(scene, kernels):
+        return place_loss_reference(scene, kernels, target, weight)
+    return _PlaceLoss.apply(scene, kernels, _as_target(target, n, scene.device), _as_weight(weight, n, scene.device))
 
 
 def cell_2_world(cells, bounds, cell: float):

@@ -289,6 +289,17 @@ class BatchedRearrangementEnv:
         cells, bins, angles = perception.decode_place(best.index, (rows, cols), n_rotations)
         return PlaceDecision(cells, bins, angles, perception.cell_2_world(cells, HEIGHTMAP_BOUNDS, cell), best.value)
 
+    def transporter_loss(self, scene_features, crop_features, batch, weight=None):
+        """The training loss of a Transporter's place head for every env, float32 [N], on the device:
+        ``perception.place_loss`` of ``scene_features`` [N, D, rows, columns] and ``crop_features`` [N, R, D, crop, crop]
+        (the network's outputs on ``batch.scene`` and ``batch.crops``) against the target of ``batch``, a
+        ``perception.TransporterBatch``: its moved place cell at its rotation bin (``perception.encode_place``).
+        Differentiable with respect to both feature tensors; NaN for an env whose place cell lies outside the map (where
+        ``batch.tries`` is 0).  No logits are written and no state of the env changes."""
+        rows, cols = int(scene_features.shape[2]), int(scene_features.shape[3])
+        target = perception.encode_place(np.asarray(batch.place), np.asarray(batch.rotation_index), (rows, cols))
+        return perception.place_loss(scene_features, crop_features, torch.from_numpy(target).to(scene_features.device), weight)
+
     def _compute_observation(self):
         if not self.render_observations:
             return self._zeros_obs()
