@@ -535,6 +535,50 @@ int mre_correlate_grad_scene(void* stream, const uint16_t* g, const uint16_t* ke
 int mre_correlate_grad_kern(void* stream, const uint16_t* g, const uint16_t* scene, int n, int rotations, int depth,
                             int h, int w, int crop, float* grad_kern, void* workspace, size_t workspace_bytes);
 
+/* The Transporter pick head on the device (csrc/mre_attend.hip): what turns an attention network's
+ * per-cell logits into a pick cell, and what trains that network.
+ *   logits   device [n][rotations][h][w] of `dtype` (MRE_F32 or MRE_BF16), aligned to its element size; rotations (K) is
+ *            the number of pick rotations, 1 for a classic Transporter.  The flat index of a cell is (k * h + y) * w + x, as
+ *            in mre_correlate; l is the env's K * h * w logits as float32 (a bfloat16 widened exactly).
+ * mre_attend, in one pass over the logits, per env e:
+ *   best_index  device i64 [n], best_value device f32 [n] (NULL together): the largest logit and its flat index, by
+ *               mre_correlate's rule: the first cell is the initial candidate and a later cell replaces it only when it is
+ *               strictly greater: ties go to the lowest flat index, and a NaN never wins.
+ *   target      device i64 [n], 8-byte aligned, or NULL; with it, and NULL together with it,
+ *   lse, target_logit, loss   device f32 [n]:  lse[e] = log sum_cells exp(l),  target_logit[e] = l[t],  loss[e] = lse[e] - l[t]
+ *               with t = target[e].  A t outside [0, K * h * w) gives target_logit[e] = loss[e] = NaN and lse[e] as ever.
+ *               The host never reads target.
+ *   workspace   device, 16-byte aligned, at least the bytes mre_attend_workspace answers for (n, rotations, h, w): 16 bytes
+ *               for each of the S = min(ceil(K h w / 2048), 16) workgroups of an env; its contents mean nothing
+ * target and best_* may not all be NULL.  What the decision and the loss share is the same bits whether they are asked for
+ * together or alone.
+ * mre_attend_dlogits, in one read and one write:
+ *   g[e][cell] = weight[e] * (exp(l[cell] - lse[e]) - [cell == t])     device [n][rotations][h][w] of `dtype`
+ * float32, or rounded to bfloat16 as mre_warp_inputs rounds.  lse is what mre_attend wrote; weight is NULL (1 for every env)
+ * or device f32 [n]; a t outside gives the weighted softmax alone.
+ * -inf is a valid logit: a masked cell.  It never is the best cell while the env has a finite one, it adds 0 to the sum and
+ * its g is 0.  An env whose cells are all -inf has lse = -inf, loss = NaN, best_index = 0, best_value = -inf and g = 0 in
+ * every cell; it puts no NaN into another env, and no -inf cell puts one into its own.  +inf and NaN logits do not fault,
+ * and beyond that their results are unspecified.
+ * lse is accumulated as an online (max, sum of exp2) in float32: within 2^-15 + 2^-22 |lse| of the exact value, as
+ * mre_correlate_loss has it.  Every output element is written exactly once and nothing else but the workspace is; no
+ * atomics; the same bytes on every run; an env's bytes depend neither on n nor on its place in the batch nor on the
+ * alignment of its first byte.  Logits are read, and g is written, 16 bytes at a time where the env's first byte is 16-byte
+ * aligned, except for a last partial vector; any other env element by element, with the same bits.  Enqueued on `stream`
+ * of the current device (mre_attend: 2 launches, mre_attend_dlogits: 1); nothing synchronises.
+ * MRE_ERR_ARG, with nothing launched and no byte touched, unless n >= 0 (0: MRE_OK, nothing launched),
+ * 1 <= rotations <= 64, 1 <= h, w <= 4096, rotations * h * w < 2^31, dtype is one of the two codes, logits (and g) are
+ * non-NULL and aligned to the element size, the i64 pointers are 8-byte and the f32 pointers 4-byte aligned, the NULL rules
+ * above hold (mre_attend_dlogits: target and lse non-NULL), workspace is non-NULL, 16-byte aligned and large enough, every
+ * pointer is a device pointer, and no output or workspace byte range overlaps an input.
+ * mre_attend_workspace: MRE_ERR_ARG unless bytes is non-NULL and n, rotations, h, w are in those ranges; at least 16. */
+int mre_attend_workspace(int n, int rotations, int h, int w, size_t* bytes);
+int mre_attend(void* stream, const void* logits, int n, int rotations, int h, int w, int dtype, const int64_t* target,
+               int64_t* best_index, float* best_value, float* lse, float* target_logit, float* loss,
+               void* workspace, size_t workspace_bytes);
+int mre_attend_dlogits(void* stream, const void* logits, int n, int rotations, int h, int w, int dtype,
+                       const int64_t* target, const float* lse, const float* weight, void* g);
+
 #define MRE_SOLVER_PGS 0
 #define MRE_SOLVER_NEWTON 2
 int mre_set_solver(mre_env*, int solver);

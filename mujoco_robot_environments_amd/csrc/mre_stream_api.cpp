@@ -1,5 +1,5 @@
 // mre_stream_api.cpp -- the entry points of the C ABI (include/mre.h) that take a stream and no handle: CRC-32C and the
-// episode records, frame labels, heightmaps, the map warp, the network inputs and the place head.  They check their
+// episode records, frame labels, heightmaps, the map warp, the network inputs, the place head and the pick head.  They check their
 // arguments, fill the unit's argument struct and enqueue its launch on the caller's stream; they own no buffer and never
 // see an mre_env (mre_api.cpp has those that do).  No torch types; plain pointers and sizes only.
 #include <hip/hip_runtime.h>
@@ -17,6 +17,7 @@
 #include "mre_warp.h"
 #include "mre_warp_inputs.h"
 #include "mre_correlate.h"
+#include "mre_attend.h"
 
 using namespace mre;
 
@@ -572,6 +573,102 @@ extern "C" int mre_correlate_grad_kern(void* stream, const uint16_t* g, const ui
   a.scene = scene;
   a.vec_g = (w % 8 == 0 && !((uintptr_t)g & 15)) ? 1u : 0u;
   mre_launch_correlate_grad_kern(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+// ---- the Transporter pick head on the device (csrc/mre_attend.hip): best cell, loss and gradient from stored logits
+static std::string attend_ranges(int n, int rotations, int h, int w, int dtype) {
+  if (n < 0) return ": n >= 0";
+  if (rotations < 1 || rotations > AT_MAX_ROT) return ": 1 <= rotations <= 64";
+  if (h < 1 || w < 1 || h > AT_MAX_DIM || w > AT_MAX_DIM) return ": 1 <= h, w <= 4096";
+  if ((long long)rotations * h * w >= (1ll << 31)) return ": rotations * h * w must be below 2^31";
+  if (dtype != MRE_F32 && dtype != MRE_BF16) return ": dtype must be MRE_F32 or MRE_BF16";
+  return "";
+}
+
+static size_t attend_workspace(int n, int rotations, int h, int w) {
+  const size_t bytes = (size_t)n * at_split((uint32_t)(rotations * h * w)) * AT_SLOT_BYTES;   // a multiple of 16
+  return bytes ? bytes : 16;
+}
+
+extern "C" int mre_attend_workspace(int n, int rotations, int h, int w, size_t* bytes) {
+  const std::string wh("mre_attend_workspace");
+  if (!bytes) return fail(MRE_ERR_ARG, wh + ": null bytes");
+  const std::string bad = attend_ranges(n, rotations, h, w, MRE_F32);
+  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  *bytes = attend_workspace(n, rotations, h, w);
+  return MRE_OK;
+}
+
+extern "C" int mre_attend(void* stream, const void* logits, int n, int rotations, int h, int w, int dtype,
+                          const int64_t* target, int64_t* best_index, float* best_value, float* lse, float* target_logit,
+                          float* loss, void* workspace, size_t workspace_bytes) {
+  const std::string wh("mre_attend");
+  const std::string bad = attend_ranges(n, rotations, h, w, dtype);
+  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  const size_t esize = dtype == MRE_BF16 ? 2 : 4;
+  if (!logits || ((uintptr_t)logits & (esize - 1)))
+    return fail(MRE_ERR_ARG, wh + ": logits must be non-NULL and aligned to its element size");
+  if (!best_index != !best_value) return fail(MRE_ERR_ARG, wh + ": best_index and best_value are NULL together or not at all");
+  if (((uintptr_t)best_index & 7) || ((uintptr_t)best_value & 3))
+    return fail(MRE_ERR_ARG, wh + ": best_index must be 8-byte and best_value 4-byte aligned");
+  if (!target != !lse || !target != !target_logit || !target != !loss)
+    return fail(MRE_ERR_ARG, wh + ": target, lse, target_logit and loss are NULL together or not at all");
+  if ((uintptr_t)target & 7) return fail(MRE_ERR_ARG, wh + ": target must be 8-byte aligned");
+  if (((uintptr_t)lse & 3) || ((uintptr_t)target_logit & 3) || ((uintptr_t)loss & 3))
+    return fail(MRE_ERR_ARG, wh + ": lse, target_logit and loss must be 4-byte aligned");
+  if (!target && !best_index) return fail(MRE_ERR_ARG, wh + ": nothing to write: target and best_* are all NULL");
+  const size_t need = attend_workspace(n, rotations, h, w);
+  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need)
+    return fail(MRE_ERR_ARG, wh + ": workspace must be non-NULL, 16-byte aligned and as large as mre_attend_workspace says");
+  // no output or workspace byte range may overlap an input (n < 2^31 envs of fewer than 2^31 cells of 4 B: below 2^64)
+  const size_t cells = (size_t)rotations * h * w;
+  const ByteRange ins[2] = {{logits, esize * (size_t)n * cells}, {target, 8 * (size_t)n}};
+  const ByteRange outs[6] = {{best_index, 8 * (size_t)n}, {best_value, 4 * (size_t)n}, {lse, 4 * (size_t)n},
+                             {target_logit, 4 * (size_t)n}, {loss, 4 * (size_t)n}, {workspace, need}};
+  if (ranges_overlap(ins, outs)) return fail(MRE_ERR_ARG, wh + ": an output or the workspace overlaps an input");
+  if (n == 0) return MRE_OK;
+  if (!is_device_ptr(logits) || !is_device_ptr(workspace) ||
+      (best_index && (!is_device_ptr(best_index) || !is_device_ptr(best_value))) ||
+      (target && (!is_device_ptr(target) || !is_device_ptr(lse) || !is_device_ptr(target_logit) || !is_device_ptr(loss))))
+    return fail(MRE_ERR_ARG, wh + ": logits, target, the outputs and the workspace must be device pointers");
+  AttendArgs a;
+  memset(&a, 0, sizeof(a));
+  a.logits = logits; a.target = target; a.best_index = best_index; a.best_value = best_value;
+  a.lse = lse; a.target_logit = target_logit; a.loss = loss; a.workspace = workspace;
+  a.n = (uint32_t)n; a.cells = (uint32_t)cells; a.bf16 = dtype == MRE_BF16 ? 1u : 0u;
+  mre_launch_attend(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+extern "C" int mre_attend_dlogits(void* stream, const void* logits, int n, int rotations, int h, int w, int dtype,
+                                  const int64_t* target, const float* lse, const float* weight, void* g) {
+  const std::string wh("mre_attend_dlogits");
+  const std::string bad = attend_ranges(n, rotations, h, w, dtype);
+  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  const size_t esize = dtype == MRE_BF16 ? 2 : 4;
+  if (!logits || !target || !lse) return fail(MRE_ERR_ARG, wh + ": null logits, target or lse");
+  if ((uintptr_t)logits & (esize - 1)) return fail(MRE_ERR_ARG, wh + ": logits must be aligned to its element size");
+  if ((uintptr_t)target & 7) return fail(MRE_ERR_ARG, wh + ": target must be 8-byte aligned");
+  if (((uintptr_t)lse & 3) || ((uintptr_t)weight & 3)) return fail(MRE_ERR_ARG, wh + ": lse and weight must be 4-byte aligned");
+  if (!g || ((uintptr_t)g & (esize - 1))) return fail(MRE_ERR_ARG, wh + ": g must be non-NULL and aligned to its element size");
+  // (lengths below 2^64, as in mre_attend)
+  const size_t cells = (size_t)rotations * h * w;
+  const ByteRange ins[4] = {{logits, esize * (size_t)n * cells}, {target, 8 * (size_t)n}, {lse, 4 * (size_t)n},
+                            {weight, 4 * (size_t)n}};
+  const ByteRange outs[1] = {{g, esize * (size_t)n * cells}};
+  if (ranges_overlap(ins, outs)) return fail(MRE_ERR_ARG, wh + ": g overlaps an input");
+  if (n == 0) return MRE_OK;
+  if (!is_device_ptr(logits) || !is_device_ptr(target) || !is_device_ptr(lse) || (weight && !is_device_ptr(weight)) ||
+      !is_device_ptr(g))
+    return fail(MRE_ERR_ARG, wh + ": logits, target, lse, weight and g must be device pointers");
+  AttendGradArgs a;
+  memset(&a, 0, sizeof(a));
+  a.logits = logits; a.target = target; a.lse = lse; a.weight = weight; a.g = g;
+  a.n = (uint32_t)n; a.cells = (uint32_t)cells; a.bf16 = dtype == MRE_BF16 ? 1u : 0u;
+  mre_launch_attend_dlogits(&a, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
 }

@@ -36,7 +36,8 @@ UNITS = [("kernels", STEP_SOURCE, []), ("kernels_large", STEP_SOURCE, ["-DMRE_LA
          ("render", "mre_render.hip", []), ("records", "mre_records.hip", []),
          ("labels", "mre_labels.hip", []), ("heightmap", "mre_heightmap.hip", []),
          ("warp", "mre_warp.hip", []), ("warp_inputs", "mre_warp_inputs.hip", []),
-         ("correlate", "mre_correlate.hip", []), ("correlate_grad", "mre_correlate_grad.hip", []), ("api", "mre_api.cpp", []), ("stream_api", "mre_stream_api.cpp", []),
+         ("correlate", "mre_correlate.hip", []), ("correlate_grad", "mre_correlate_grad.hip", []),
+         ("attend", "mre_attend.hip", []), ("api", "mre_api.cpp", []), ("stream_api", "mre_stream_api.cpp", []),
          ("sched", "mre_sched.cpp", []), ("model", "mre_model.cpp", [])]
 
 MRE_NQ, MRE_NV, MRE_NU, MRE_NQ_PAD, MRE_NV_PAD, MRE_MAX_PROPS = 43, 39, 8, 44, 40, 4
@@ -87,6 +88,9 @@ _SIGNATURES = {
     "mre_correlate_grad_workspace": [ci, ci, ci, ci, ci, ci, C.POINTER(sz)],
     "mre_correlate_grad_scene": [vp, fp, fp, ci, ci, ci, ci, ci, ci, fp, fp, sz],
     "mre_correlate_grad_kern": [vp, fp, fp, ci, ci, ci, ci, ci, ci, fp, fp, sz],
+    "mre_attend_workspace": [ci, ci, ci, ci, C.POINTER(sz)],
+    "mre_attend": [vp, fp, ci, ci, ci, ci, ci, fp, fp, fp, fp, fp, fp, fp, sz],
+    "mre_attend_dlogits": [vp, fp, ci, ci, ci, ci, ci, fp, fp, fp, fp],
 }
 EXPORTS = list(_SIGNATURES)
 # status bits of mre_varint_unpack_rows (include/mre.h)

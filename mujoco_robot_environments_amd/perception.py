@@ -32,6 +32,11 @@ into cells, rotation bins and world positions (``BatchedRearrangementEnv.transpo
 ``mre_correlate_grad_scene`` and ``mre_correlate_grad_kern`` (csrc/mre_correlate_grad.hip), without a logit stored;
 ``correlate_backward`` is the gradient pair alone, for any loss (``BatchedRearrangementEnv.transporter_loss``).
 
+``attend`` and ``pick_loss``: the other head -- from the logits of an attention network the pick cell of every env
+(``mre_attend``, csrc/mre_attend.hip: one read of the logits) and the loss that trains that network with its gradient
+(``mre_attend_dlogits``); ``crop_matrices_device`` centres the rotated crops on pick cells that live on the device, so
+that ``BatchedRearrangementEnv.transporter_act`` runs observation -> pick -> crops -> place without a synchronise.
+
 The kernels are enqueued on torch's current stream; nothing here synchronises.
 """
 from __future__ import annotations
@@ -39,6 +44,7 @@ from __future__ import annotations
 import collections
 import contextlib
 import ctypes as C
+import functools
 from typing import Optional
 
 import numpy as np
@@ -786,14 +792,15 @@ def correlate(scene: torch.Tensor, kernels: torch.Tensor, *, logits=None, best: 
     return Correlation(out, index, value)
 
 
-def decode_place(index, shape, n_rotations: int):
+def decode_place(index, shape, n_rotations: int, check: bool = True):
     """The flat indices of ``correlate`` [N] over ``shape`` = (rows, columns) as (cells int64 [N, 2] (column, row), rotation
     bins int64 [N], angles float64 [N] = 2 pi bin / n_rotations, the turn of ``crop_matrices``' sample ``bin``).  Torch
-    tensors for a tensor, numpy arrays for anything else."""
+    tensors for a tensor, numpy arrays for anything else.  ``check=False`` leaves out the range check, which reads the
+    indices on the host: for indices a kernel has just written, which are in range, and which nothing should wait for."""
     rows, cols = int(shape[0]), int(shape[1])
     is_tensor = isinstance(index, torch.Tensor)
     idx = index.to(torch.int64) if is_tensor else torch.as_tensor(np.asarray(index, np.int64))
-    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_rotations * rows * cols):
+    if check and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= n_rotations * rows * cols):
         raise ValueError("an index outside n_rotations * rows * columns")
     bins = torch.div(idx, rows * cols, rounding_mode="floor")
     rest = idx - bins * (rows * cols)
@@ -1012,3 +1019,192 @@ def cell_2_world(cells, bounds, cell: float):
     lo2 = torch.tensor([float(lo[0]), float(lo[1])], dtype=torch.float64, device=c.device)
     out = lo2 + (c + 0.5) * float(cell)
     return out if is_tensor else out.numpy()
+
+
+# ------------------------------------------------------------------------------------------- the pick head
+# index int64 [N], the flat (k * rows + y) * columns + x of the largest logit of every env (ties: the lowest), and value
+# float32 [N], that logit (both None when not asked for); lse, target_logit and loss float32 [N] (None without a target)
+Attention = collections.namedtuple("Attention", ["index", "value", "lse", "target_logit", "loss"])
+
+
+def _attend_args(logits):
+    if logits.dim() != 4:
+        raise ValueError("logits must be [N, K, rows, columns]")
+    n, rot, h, w = (int(x) for x in logits.shape)
+    if not (1 <= rot <= MAX_ROTATIONS and 1 <= h <= MAX_MAP and 1 <= w <= MAX_MAP and rot * h * w < 2 ** 31):
+        raise ValueError("1 <= K <= 64, 1 <= rows, columns <= 4096 and K * rows * columns < 2^31")
+    return n, rot, h, w
+
+
+def _logits_on_device(*tensors) -> bool:
+    """What the pick head's kernels read in place: contiguous CUDA float32 or bfloat16"""
+    return all(t.is_cuda and t.dtype in _DTYPES and t.is_contiguous() for t in tensors)
+
+
+def attend_reference(logits: torch.Tensor, target=None, best: bool = True) -> Attention:
+    """The statement of ``attend`` (include/mre.h, mre_attend) in plain float32 torch, on any device and for any dtype and
+    strides: the first occurrence of the largest logit (a NaN counts as -inf), and with ``target`` the logsumexp of the
+    env's K * rows * columns logits, the logit at ``target`` and their difference (NaN where ``target`` is outside).
+    -inf is a masked cell; an env of nothing else has lse = -inf and loss = NaN.  ``lse`` and ``loss`` are differentiable
+    by torch itself, and an all -inf env then gets a zero gradient, as ``mre_attend_dlogits`` gives it.  The fallback of
+    ``attend`` and ``pick_loss``."""
+    n, rot, h, w = _attend_args(logits)
+    flat = logits.to(torch.float32).reshape(n, rot * h * w)
+    index = value = lse = at = loss = None
+    if best:
+        index = torch.where(torch.isnan(flat), torch.full_like(flat, float("-inf")), flat).detach().argmax(dim=1)
+        value = flat.detach().gather(1, index[:, None])[:, 0]
+    if target is not None:
+        t = _as_target(target, n, logits.device)
+        ninf = torch.full((n,), float("-inf"), dtype=torch.float32, device=logits.device)
+        dead = (flat == float("-inf")).all(dim=1)
+        lse = torch.where(dead, ninf, torch.logsumexp(torch.where(dead[:, None], torch.zeros_like(flat), flat), dim=1))
+        inside = (t >= 0) & (t < rot * h * w)
+        at = flat.gather(1, torch.where(inside, t, torch.zeros_like(t))[:, None])[:, 0]
+        at = torch.where(inside, torch.where(dead, ninf, at), torch.full_like(at, float("nan")))
+        loss = lse - at
+    elif not best:
+        raise ValueError("nothing asked for: target is None and best is False")
+    return Attention(index, value, lse, at, loss)
+
+
+@functools.lru_cache(maxsize=64)
+def _attend_workspace(n, rot, h, w) -> int:
+    nbytes = C.c_size_t(0)
+    _lib.check(_lib.lib().mre_attend_workspace(n, rot, h, w, C.byref(nbytes)), "mre_attend_workspace")
+    return int(nbytes.value)
+
+
+def attend(logits: torch.Tensor, target=None, best: bool = True) -> Attention:
+    """A Transporter's pick head: from the ``logits`` [N, K, rows, columns] of an attention network (K pick rotations, 1
+    for a classic Transporter), per env the largest logit with its flat index (k * rows + y) * columns + x (``best``), and
+    with ``target`` [N] (int64 flat indices, as ``encode_pick`` makes them) the softmax cross-entropy against that cell:
+    ``lse``, ``target_logit`` and ``loss`` = lse - logit[target], NaN where ``target`` is outside.  An ``Attention``.
+    -inf logits are masked cells.  ``decode_pick`` turns ``index`` into cells and rotation bins.
+
+    Contiguous CUDA float32 or bfloat16 logits are one call of ``mre_attend`` (csrc/mre_attend.hip: one read of the
+    logits, no float32 copy) on torch's current stream with a ``torch.empty`` workspace, without a synchronise; anything
+    else is computed by ``attend_reference``.  No autograd on the device path: ``pick_loss`` is the training path."""
+    n, rot, h, w = _attend_args(logits)
+    if target is None and not best:
+        raise ValueError("nothing asked for: target is None and best is False")
+    if not _logits_on_device(logits):
+        return attend_reference(logits, target, best)
+    dev = logits.device
+    t = None if target is None else _as_target(target, n, dev)
+    index = torch.empty((n,), dtype=torch.int64, device=dev) if best else None
+    # the four float32 rows and, behind them, the workspace (a multiple of 16 bytes per env, 16 n bytes in): one allocation
+    nbytes = _attend_workspace(n, rot, h, w) if n else 0
+    out = torch.empty((4 + nbytes // (4 * n) if n else 4, n), dtype=torch.float32, device=dev)
+    if n:
+        first = out.data_ptr()
+        ptr = lambda k, on: first + 4 * n * k if on else None
+        with _stream_on(dev) as stream:
+            _lib.check(_lib.lib().mre_attend(stream, logits.data_ptr(), n, rot, h, w, _DTYPES[logits.dtype],
+                                             None if t is None else t.data_ptr(), index.data_ptr() if best else None,
+                                             ptr(0, best), ptr(1, t is not None), ptr(2, t is not None), ptr(3, t is not None),
+                                             first + 16 * n, nbytes), "mre_attend")
+    given = lambda k, on: out[k] if on else None
+    return Attention(index, given(0, best), given(1, t is not None), given(2, t is not None), given(3, t is not None))
+
+
+def attend_dlogits(logits: torch.Tensor, target, lse: torch.Tensor, weight=None) -> torch.Tensor:
+    """``mre_attend_dlogits``: g = weight * (softmax - one-hot of ``target``) in the logits' dtype and shape, from the
+    ``lse`` of ``attend``; one read and one write.  ``logits`` must be what the kernels read in place (contiguous CUDA
+    float32 or bfloat16: ``pick_loss_reference`` serves anything else), ``lse`` float32 [N] on its device; ``target`` [N] and
+    ``weight`` [N] or None are brought to int64 and float32 there."""
+    n, rot, h, w = _attend_args(logits)
+    if not _logits_on_device(logits):
+        raise ValueError("logits must be a contiguous CUDA float32 or bfloat16 tensor")
+    dev = logits.device
+    if lse.dtype != torch.float32 or lse.device != dev or tuple(lse.shape) != (n,):
+        raise ValueError("lse must be float32 [N] on the device of logits")
+    lse, target, weight = lse.contiguous(), _as_target(target, n, dev), _as_weight(weight, n, dev)
+    g = torch.empty_like(logits)
+    if n:
+        with _stream_on(dev) as stream:
+            _lib.check(_lib.lib().mre_attend_dlogits(
+                stream, logits.data_ptr(), n, rot, h, w, _DTYPES[logits.dtype], target.data_ptr(), lse.data_ptr(),
+                None if weight is None else weight.data_ptr(), g.data_ptr()), "mre_attend_dlogits")
+    return g
+
+
+class _PickLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, weight):
+        out = attend(logits, target, best=False)
+        ctx.save_for_backward(logits, target, out.lse)
+        ctx.weight = weight
+        return out.loss if weight is None else weight * out.loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        logits, target, lse = ctx.saved_tensors
+        wgt = grad.to(torch.float32) if ctx.weight is None else grad.to(torch.float32) * ctx.weight
+        return attend_dlogits(logits, target, lse, wgt.contiguous()), None, None
+
+
+def pick_loss_reference(logits: torch.Tensor, target, weight=None) -> torch.Tensor:
+    """The statement of ``pick_loss`` in plain float32 torch (``attend_reference``), differentiable by torch itself:
+    weight * (logsumexp of the env's logits minus the logit at ``target``), float32 [N]; NaN where ``target`` is outside,
+    and the gradient is then that of the logsumexp alone.  The fallback of ``pick_loss``."""
+    n = _attend_args(logits)[0]
+    loss = attend_reference(logits, target, best=False).loss
+    wgt = _as_weight(weight, n, logits.device)
+    return loss if wgt is None else wgt * loss
+
+
+def pick_loss(logits: torch.Tensor, target, weight=None) -> torch.Tensor:
+    """The training loss of a Transporter's pick head, float32 [N]: per env the softmax cross-entropy of the K * rows *
+    columns ``logits`` against the cell ``target`` [N] (``encode_pick``), times ``weight`` [N] (None: 1); NaN where
+    ``target`` is outside (the gradient is then that of the logsumexp alone).  Differentiable with respect to ``logits``.
+
+    Contiguous CUDA float32 or bfloat16 logits take the kernels of csrc/mre_attend.hip on torch's current stream, without
+    a synchronise: forward is ``mre_attend`` without the decision and keeps logits, target and the logsumexp (one float per
+    env); backward is ``mre_attend_dlogits`` with weight * the incoming gradient, which writes the gradient in the logits'
+    dtype in one read and one write.  Anything else goes through ``pick_loss_reference``."""
+    n = _attend_args(logits)[0]
+    if not _logits_on_device(logits):
+        return pick_loss_reference(logits, target, weight)
+    return _PickLoss.apply(logits, _as_target(target, n, logits.device), _as_weight(weight, n, logits.device))
+
+
+def decode_pick(index, shape, n_rotations: int = 1, check: bool = True):
+    """``decode_place`` under the pick head's name: pick and place share one index convention."""
+    return decode_place(index, shape, n_rotations, check)
+
+
+def encode_pick(cells, bins, shape):
+    """``encode_place`` under the pick head's name: the target ``pick_loss`` takes."""
+    return encode_place(cells, bins, shape)
+
+
+@functools.lru_cache(maxsize=16)
+def _crop_table(n_rotations: int, crop: int, device: str) -> torch.Tensor:
+    """float64 [n_rotations, 6] on ``device``: (cos, -sin, (R @ half)_x, sin, cos, (R @ half)_y) by the expressions of
+    ``crop_matrices``; built and uploaded once per (n_rotations, crop, device)"""
+    half = np.array([crop / 2.0, crop / 2.0])
+    table = np.empty((n_rotations, 6), np.float64)
+    for k in range(n_rotations):
+        cos, sin = _quarter_exact(k, n_rotations)
+        R = np.array([[cos, -sin], [sin, cos]])
+        table[k, [0, 1, 3, 4]] = R.reshape(4)
+        table[k, [2, 5]] = R @ half
+    return torch.from_numpy(table).to(device)
+
+
+def crop_matrices_device(cells: torch.Tensor, n_rotations: int = 36, crop: int = 64):
+    """``crop_matrices`` for pivots ``cells`` [N, 2] (column, row) that are a tensor, on its device and without a
+    synchronise: (mats float32 [N * n_rotations, 6], index int32 [N * n_rotations]), bit for bit what ``crop_matrices``
+    gives for the same cells.  The per-rotation entries and R @ half are formed on the host in float64 by the same
+    expressions, once per (n_rotations, crop, device), and kept on the device; a call performs p - R @ half in float64 there,
+    one correctly rounded operation, and rounds to float32 once: no copy from the host."""
+    if n_rotations < 1 or crop < 1:
+        raise ValueError("n_rotations and crop must be at least 1")
+    p = cells.reshape(-1, 2).to(torch.float64)
+    table = _crop_table(int(n_rotations), int(crop), str(p.device))
+    mats = table[None].repeat(p.shape[0], 1, 1)
+    mats[:, :, 2] = p[:, None, 0] - table[None, :, 2]
+    mats[:, :, 5] = p[:, None, 1] - table[None, :, 5]
+    index = torch.arange(p.shape[0], dtype=torch.int32, device=p.device).repeat_interleave(n_rotations)
+    return mats.to(torch.float32).reshape(-1, 6).contiguous(), index

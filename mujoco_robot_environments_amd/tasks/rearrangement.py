@@ -75,6 +75,10 @@ OVERHEAD = "overhead_camera/overhead_camera"
 HEIGHTMAP_BOUNDS = ((0.2, -0.4, TABLE_TOP_Z - 0.01), (0.8, 0.4, TABLE_TOP_Z + 0.29))
 # what BatchedRearrangementEnv.transporter_place decides for every env
 PlaceDecision = collections.namedtuple("PlaceDecision", ["cells", "rotation", "angle", "xy", "value"])
+# what BatchedRearrangementEnv.transporter_pick decides for every env: cells int64 [N, 2] (column, row), rotation bins int64
+# [N], angles float64 [N] (radians), xy float64 [N, 2] (world) and the logit float32 [N], on the logits' device.  (`bins` and
+# `angles` are what PlaceDecision, which is older, calls `rotation` and `angle`: transporter_act returns one of each.)
+PickDecision = collections.namedtuple("PickDecision", ["cells", "bins", "angles", "xy", "value"])
 
 
 def mat2quat(mat3x3) -> np.ndarray:
@@ -85,6 +89,37 @@ def mat2quat(mat3x3) -> np.ndarray:
 def home_quat() -> np.ndarray:
     """mju_mat2Quat(R.from_euler('xyz',[0,180,0])) (tasks/rearrangement.py:391-393)."""
     return mat2quat(R.from_euler("xyz", [0, 180, 0], degrees=True).as_matrix())
+
+
+def quat_mul(a, b) -> np.ndarray:
+    """Hamilton product of quaternions (w, x, y, z) [..., 4]: the rotation b, then the rotation a."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    aw, ax, ay, az = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+    bw, bx, by, bz = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+    return np.stack([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw], axis=-1)
+
+
+def transporter_poses(pick_xy, place_xy, place_angle, pick_quat=None, height: float = PICK_HEIGHT):
+    """The two poses ``step()`` takes from a Transporter's decisions: (pick_pose, place_pose), float64 [N, 7] each
+    (position, quaternion (w, x, y, z)).  ``pick_xy`` and ``place_xy`` [N, 2] are world positions, ``place_angle`` [N] the
+    angle of the place head's rotation bin (``perception.decode_place``), ``pick_quat`` the gripper's orientation at the pick
+    (default ``home_quat()``).
+
+    The sign of the turn: crop k of ``crop_matrices`` reads the map at p + R(a) u for the offset u from its
+    pivot, a = 2 pi k / n_rotations, R = [[cos, -sin], [sin, cos]] in (column, row) -- and column runs along world x, row
+    along world y, so R(a) is a turn by +a about world z.  A point of the picked object at p + v therefore shows in crop k
+    at u = R(-a) v: laid over the place cell c, crop k shows the object at c + R(-a) v, turned by -a.  The place quaternion
+    is the pick quaternion turned about world z by -place_angle (taken into (-pi, pi])."""
+    pick_xy, place_xy = np.asarray(pick_xy, np.float64).reshape(-1, 2), np.asarray(place_xy, np.float64).reshape(-1, 2)
+    n = len(pick_xy)
+    q0 = np.broadcast_to(home_quat() if pick_quat is None else np.asarray(pick_quat, np.float64), (n, 4))
+    turn = -np.asarray(place_angle, np.float64).reshape(n)
+    turn = turn - 2.0 * np.pi * np.floor(turn / (2.0 * np.pi) + 0.5)          # [-pi, pi)
+    turn = np.where(turn == -np.pi, np.pi, turn)
+    qz = np.stack([np.cos(turn / 2), np.zeros(n), np.zeros(n), np.sin(turn / 2)], axis=-1)
+    z = np.full((n, 1), float(height))
+    return np.concatenate([pick_xy, z, q0], axis=1), np.concatenate([place_xy, z, quat_mul(qz, q0)], axis=1)
 
 
 class BatchedRearrangementEnv:
@@ -286,7 +321,7 @@ class BatchedRearrangementEnv:
         rows, cols = int(scene_features.shape[2]), int(scene_features.shape[3])
         n_rotations = int(crop_features.shape[1])
         best = perception.correlate(scene_features, crop_features)
-        cells, bins, angles = perception.decode_place(best.index, (rows, cols), n_rotations)
+        cells, bins, angles = perception.decode_place(best.index, (rows, cols), n_rotations, check=False)
         return PlaceDecision(cells, bins, angles, perception.cell_2_world(cells, HEIGHTMAP_BOUNDS, cell), best.value)
 
     def transporter_loss(self, scene_features, crop_features, batch, weight=None):
@@ -299,6 +334,60 @@ class BatchedRearrangementEnv:
         rows, cols = int(scene_features.shape[2]), int(scene_features.shape[3])
         target = perception.encode_place(np.asarray(batch.place), np.asarray(batch.rotation_index), (rows, cols))
         return perception.place_loss(scene_features, crop_features, torch.from_numpy(target).to(scene_features.device), weight)
+
+    def transporter_pick(self, logits, cell: float = 0.0025):
+        """The pick decision of a Transporter's attention head for every env, on the device: the best cell and rotation bin
+        of ``logits`` [N, K, rows, columns] (the network's output on the scene; K pick rotations, 1 for a classic
+        Transporter; -inf masks a cell) by ``perception.attend`` and ``perception.decode_pick``, and that cell's centre in
+        the world by ``perception.cell_2_world`` on ``HEIGHTMAP_BOUNDS`` at ``cell`` metres per cell.  A ``PickDecision`` on
+        the logits' device; nothing synchronises and no state of the env changes."""
+        rot, rows, cols = (int(x) for x in logits.shape[1:])
+        best = perception.attend(logits)
+        cells, bins, angles = perception.decode_pick(best.index, (rows, cols), rot, check=False)
+        return PickDecision(cells, bins, angles, perception.cell_2_world(cells, HEIGHTMAP_BOUNDS, cell), best.value)
+
+    def transporter_pick_loss(self, logits, batch, weight=None):
+        """The training loss of a Transporter's attention head for every env, float32 [N], on the device:
+        ``perception.pick_loss`` of ``logits`` [N, K, rows, columns] (the network's output on ``batch.scene``) against the
+        target of ``batch``, a ``perception.TransporterBatch``: its moved pick cell at rotation bin 0
+        (``perception.encode_pick``).  Differentiable with respect to ``logits``.  An env whose pick cell lies outside the
+        map has no label: its loss is NaN and its gradient that of the logsumexp alone, so the caller gives such envs
+        ``weight`` 0 (the gradient is then exactly 0) and leaves them out of the sum.  No state of the env changes."""
+        rows, cols = int(logits.shape[2]), int(logits.shape[3])
+        pick = np.asarray(batch.pick)
+        target = perception.encode_pick(pick, np.zeros(len(pick), np.int64), (rows, cols))
+        return perception.pick_loss(logits, torch.from_numpy(target).to(logits.device), weight)
+
+    def transporter_act(self, attention, query, key, *, channels, dtype, n_rotations: int = 36, crop: int = 64,
+                        cell: float = 0.0025, depth=None, rgb=None, seg=None):
+        """One decision of a Transporter policy for every env, from the observation to the two poses ``step()`` takes:
+        (pick_pose [N, 7], place_pose [N, 7], ``PickDecision``, ``PlaceDecision``).  ``attention``, ``query`` and ``key`` are
+        the caller's networks: ``attention(scene)`` -> pick logits [N, K, rows, columns], ``key(scene)`` -> [N, D, rows,
+        columns] and ``query(crops)`` -> [N * n_rotations, D, crop, crop] on crops [N * n_rotations, C, crop, crop].
+
+        ``heightmap(depth, rgb, seg, cell=cell)``; ``scene`` = one ``perception.warp_inputs`` of the maps under the identity
+        (``channels``, ``dtype``); ``transporter_pick`` of ``attention(scene)``; ``perception.crop_matrices_device`` at the
+        predicted cells and one ``warp_inputs`` for the rotated crops around them; ``transporter_place`` of ``key(scene)``
+        and ``query(crops)``; ``transporter_poses``.  Everything up to the poses stays on the device and nothing waits for
+        it; the poses are numpy because ``step()`` takes numpy.  The pick quaternion is ``home_quat()``, the place
+        quaternion that turned about world z by the place decision (``transporter_poses`` has the sign).  No state of the env
+        changes: the caller passes the poses to ``step()``."""
+        maps = self.heightmap(depth, rgb, seg, cell=cell)
+        height, colour = maps[0], maps[1]
+        n, dev = int(height.shape[0]), height.device
+        kw = dict(channels=channels, dtype=dtype)
+        identity = torch.zeros((n, 6), dtype=torch.float32, device=dev)   # filled on the device: no copy from the host
+        identity[:, 0] = 1.0
+        identity[:, 4] = 1.0
+        scene = perception.warp_inputs(height, colour, mats=identity, **kw)
+        pick = self.transporter_pick(attention(scene), cell)
+        mats, index = perception.crop_matrices_device(pick.cells, n_rotations, crop)
+        crops = perception.warp_inputs(height, colour, mats=mats, index=index, out_shape=(crop, crop), **kw)
+        features = query(crops)
+        place = self.transporter_place(key(scene), features.reshape((n, n_rotations) + tuple(features.shape[1:])), cell)
+        packed = torch.cat([pick.xy, place.xy, place.angle[:, None]], dim=1).cpu().numpy()   # the one wait
+        pick_pose, place_pose = transporter_poses(packed[:, 0:2], packed[:, 2:4], packed[:, 4])
+        return pick_pose, place_pose, pick, place
 
     def _compute_observation(self):
         if not self.render_observations:
