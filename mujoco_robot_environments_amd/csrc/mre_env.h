@@ -133,7 +133,9 @@ struct mre_env {
   // waves of the large kernel beyond the envs flagged large (MRE_QUEUE_SPARE_LARGE): they wait for hand-overs, and each
   // holds the LDS of 1.3 compact waves while it does -- measured on the benchmark (2 hand-overs per 200 ticks): 8 / 32 / 96
   // spare waves = 26.3 / 25.9 / 24.8 M env-steps/s.  Hand-overs beyond the spare waves queue up behind them.
-  int queue_spare_large = 8;
+  // < 0 (MRE_QUEUE_SPARE_LARGE not set): by need -- 1 after a launch without hand-overs, 8 after one with
+  // (policy::queue_spare_large)
+  int queue_spare_large = -1;
   // mre_run_controller's queue launches are shorter than a rollout's: a scripted phase moves hundreds of envs towards
   // the compact capacities at once (the grasp closes), and the host's 7/8 rule moves them at launch boundaries, before
   // they overflow -- measured on bench.py's pick_place leg: 50 / 100 / 200 ticks = 24.7 / 25.0 / 22.8 M (no queue: 21.8 M)

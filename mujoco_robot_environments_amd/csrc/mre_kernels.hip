@@ -1307,6 +1307,30 @@ MRE_PHASE_FN void integrate_setup(ModelP M, Sm& s, int l, unsigned act_clamped) 
   MRE_SYNC();
 }
 
+// Stores of the words that travel with an env from one wave to the next inside a queue launch (step_body<QUEUE>,
+// queue_push): write-through at agent scope (`sc1`: the bytes leave the XCD's L2 for memory with the store, no L2
+// write-back before the env is listed).  One word, and a row of n words (n % 4 == 0, 16-byte aligned, the same row for
+// every lane) at 16 bytes per lane from LDS.
+MRE_DEV void q_store(float* p, float v) {
+  __hip_atomic_store(reinterpret_cast<int*>(p), __float_as_int(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+MRE_DEV void q_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <bool WT>
+MRE_DEV void travel_store(float* p, float v) {
+  if (WT) q_store(p, v); else *p = v;
+}
+typedef unsigned q_u32x4 __attribute__((ext_vector_type(4)));
+// (zero_last: the row's last word is stored as zero -- the warm start's padding)
+MRE_DEV void q_store_row(float* row, const float* src, int n, int l, bool zero_last = false) {
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(row, 0, n * 4, 0x00020000);
+  if (4 * l < n) {
+    q_u32x4 v;
+    v.x = __float_as_uint(src[4 * l]); v.y = __float_as_uint(src[4 * l + 1]); v.z = __float_as_uint(src[4 * l + 2]);
+    v.w = zero_last && 4 * l + 4 == n ? 0u : __float_as_uint(src[4 * l + 3]);
+    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, 16 * l, 0, 16 /* sc1 */);
+  }
+}
+
 // part 2 (after the solve of MH x = f, also run from the kernel body): advance velocities and positions
 // clo: the cubes' low-order state words of this env in HBM (row of StepArgs::qfine from QFINE_CUBE_Q on) or null.
 // With them a cube's pose and velocity advance in fp64 on the double-float pair, like the robot's joints: a float32
@@ -1314,6 +1338,9 @@ MRE_PHASE_FN void integrate_setup(ModelP M, Sm& s, int l, unsigned act_clamped) 
 // difference a hundredfold (cubes knocked flying by the arm) take past the 1e-4 bar -- the fp64 oracle with ONLY the
 // cubes' state rounded to float32 leaves it in exactly the two cube exits of the 256-env sample, and with the cubes'
 // state in double it does not (profiles/NOTES.md, round 4).
+// WT (queue launches): the cubes' low words are stored write-through at agent scope -- they travel with the env to the
+// wave that steps its next tick (queue_push: the list of travelling words).  Same arithmetic either way.
+template <bool WT>
 MRE_PHASE_FN void integrate(ModelP M, Sm& s, int l, unsigned flags, bool polished, float* clo) {
   // the time step, the lane's dof record (first part: lane = dof) and body record (second part: lane = body)
   const float h = M->opt_rec.timestep;
@@ -1352,7 +1379,7 @@ MRE_PHASE_FN void integrate(ModelP M, Sm& s, int l, unsigned flags, bool polishe
         float* const vl = clo + (QFINE_CUBE_V - QFINE_CUBE_Q) + (l - NRV);
         const double v = (double)s.qvel[l] + (double)vl_in + (double)h * (double)s.qacc[l];
         const float hi = (float)v, lo = (float)(v - (double)hi);
-        s.qvel[l] = hi; *vl = lo;
+        s.qvel[l] = hi; travel_store<WT>(vl, lo);
         s.scratch[l] = lo;   // (scratch[NRV ..]: free here; the body lanes below read the new low words from it)
       } else {
         s.qvel[l] += h * s.qacc[l];
@@ -1376,7 +1403,7 @@ MRE_PHASE_FN void integrate(ModelP M, Sm& s, int l, unsigned flags, bool polishe
       for (int k = 0; k < 3; k++) {
         const double x = (double)s.qpos[qa + k] + (double)ql_in[k] + (double)h * vv[k];
         const float hi = (float)x;
-        s.qpos[qa + k] = hi; ql[k] = (float)(x - (double)hi);
+        s.qpos[qa + k] = hi; travel_store<WT>(ql + k, (float)(x - (double)hi));
       }
       double q0[4], qn[4];
       for (int k = 0; k < 4; k++) q0[k] = (double)s.qpos[qa + 3 + k] + (double)ql_in[3 + k];
@@ -1398,7 +1425,7 @@ MRE_PHASE_FN void integrate(ModelP M, Sm& s, int l, unsigned flags, bool polishe
       for (int k = 0; k < 4; k++) {
         const double x = qn[k] * sc;
         const float hi = (float)x;
-        s.qpos[qa + 3 + k] = hi; ql[3 + k] = (float)(x - (double)hi);
+        s.qpos[qa + 3 + k] = hi; travel_store<WT>(ql + 3 + k, (float)(x - (double)hi));
       }
     } else if (prop_is_active(s, body_pid)) {
       for (int k = 0; k < 3; k++) s.qpos[qa + k] += h * s.qvel[da + k];
@@ -1436,10 +1463,11 @@ MRE_PHASE_FN void integrate(ModelP M, Sm& s, int l, unsigned flags, bool polishe
 //
 // QUEUE (k_step_queue, StepArgs::q_head): the workgroup is a persistent wave that steps ONE control tick of one env per
 // pass of the loop below and takes its (env, tick) from the launch's ready lists; the rows it stores at the end of a pass
-// are the rows another wave -- on any CU of any XCD -- loads at the start of the env's next tick, so a pass ends with
-// an agent-scope release before the env is listed and starts with an agent-scope acquire after it was taken
-// (MI355X_MICROARCH.md, inter-workgroup visibility: plain payload -> release fence -> vmcnt(0) -> atomic flag; atomic
-// poll -> acquire fence -> plain loads).  Per tick the arithmetic is that of a one-tick launch: results are bit-identical.
+// are the rows another wave -- on any CU of any XCD -- loads when it takes the env for its next tick, so the rows are
+// published before the env is listed (queue_push: write-through stores -> vmcnt(0) -> atomic list entry in the Newton
+// kernels, plain stores -> release fence -> vmcnt(0) -> atomic list entry in the PGS ones) and loaded behind an
+// agent-scope acquire after it was taken (queue_take; MI355X_MICROARCH.md, inter-workgroup visibility).  Per tick the
+// arithmetic is that of a one-tick launch: results are bit-identical.
 MRE_DEV int q_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // The ready lists are kept per SHARD (StepArgs::q_shards): wave w belongs to shard w % q_shards, entry i of the launch's
@@ -1530,7 +1558,8 @@ MRE_DEV int queue_pop_shard(const StepArgs& a, int l, int sh, int& env, int& tic
 // before it leaves); false when no shard has.  A compact wave that finds nothing leaves: every env that is not listed is
 // held by a wave that will list it and then look here itself, so work never waits for a wave that has left, and no
 // compact wave ever waits for work.  Large waves: the large shard only, and they wait -- see above.
-MRE_DEV bool queue_pop(const StepArgs& a, int l, int home, int& env, int& tick, int& shard) {
+// (wait = false, the early take of step_body: one look at every shard, large waves included)
+MRE_DEV bool queue_pop(const StepArgs& a, int l, int home, int& env, int& tick, int& shard, bool wait = true) {
   const int S = a.q_shards;
   if (Q_LARGE) {
     // the large kernel's own shards (q_lshards of them, numbered from S; an env handed over goes to S + env % q_lshards):
@@ -1549,7 +1578,7 @@ MRE_DEV bool queue_pop(const StepArgs& a, int l, int home, int& env, int& tick, 
       // (q_wait == 0: it takes what is listed and leaves), so whatever this launch leaves undone is done there.  It
       // leaves when every env is through; when no compact wave has shown up after ~3 ms (the two kernels are not
       // running side by side: a profiler that serialises dispatches, two streams on one hardware queue); after ~2 s.
-      if (a.q_wait == 0 || q_load(a.q_done) >= a.N) return false;
+      if (!wait || a.q_wait == 0 || q_load(a.q_done) >= a.N) return false;
       if (idle > 512u && q_load(a.q_started) == 0) return false;
       if (idle > (1u << 18)) return false;
       __builtin_amdgcn_s_sleep(127);
@@ -1563,13 +1592,74 @@ MRE_DEV bool queue_pop(const StepArgs& a, int l, int home, int& env, int& tick, 
   return false;
 }
 // List the env as ready for `tick` in `shard` (its rows are stored).
+//
+// No release fence: every word that another wave of the launch reads after taking the env is stored WRITE-THROUGH at
+// agent scope by the one wave that holds the env (q_store / q_store_row, agent-scope atomics), this wave waits for all
+// its stores (vmcnt(0)) and only then lists the env with agent-scope atomics; the taking wave's agent-scope acquire drops
+// its compute unit's stale lines (MI355X_MICROARCH.md, inter-workgroup visibility: write-through payload, every storing
+// wave drained, atomic flag).  The words that travel, and who stores them:
+//   qpos, qvel, qacc_ws, qfine[0 .. QFINE), ctrl          rows, 16 bytes per lane, first thing after the tick's last step
+//   qfine[QFINE_CUBE_Q ..): the cubes' low words          integrate<true>, every step; put back from cube_lo_keep when the
+//                                                         tick is abandoned
+//   converged                                             one byte, lane 0 (controller launches)
+//   q_acc[env][0 .. 4)                                    lane 0: high-water marks, duration, `moved`
+//   nstep, status                                         agent-scope atomic add / or
+// A plain store to any of them under QUEUE would be a bug: it may still sit in this XCD's L2 when the env is taken on
+// another.  What only the host reads, after the launch, is stored plainly only where ONE wave stores it in a launch:
+// launch_info and sites by the env's last tick.  A trace row (diagnostic) is stored write-through: the rows of an
+// abandoned tick are written a second time by the large kernel's wave.  Stats by the last tick only (stored every tick, the
+// host read an earlier tick's words for envs that had changed XCDs: a dirty line left in one XCD's L2 is written back
+// whenever, possibly after the last tick's store from another; profiles/NOTES.md, round 19).
+//
+// Q_WRITE_THROUGH says which instantiations publish this way: the Newton ones.  The PGS queue kernels sit at 256 VGPRs
+// with scratch, and the 16-byte row stores added scratch to the large one (profiles/NOTES.md, round 19): they keep plain
+// stores where they were and the agent-scope release fence here.  Both kernels of a launch are of one solver, so a launch
+// never mixes the two forms.
+#ifdef MRE_NEWTON
+constexpr bool Q_WRITE_THROUGH = true;
+#else
+constexpr bool Q_WRITE_THROUGH = false;
+#endif
 MRE_DEV void queue_push(const StepArgs& a, int l, int env, int tick, int shard) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the compiler may drop the fence's own wait: guide, compiler hazard)
+  if (!Q_WRITE_THROUGH) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  // every store of this wave has left for memory (after the fence: the compiler may drop the fence's own wait)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (l == 0) {
     const int i = __hip_atomic_fetch_add(a.q_tail + shard * QUEUE_TICKS_MAX + tick, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(q_bucket(a, tick, shard) + i, env + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+// An item as a queue wave takes it: the (env, tick) and the env's rows in registers, one word per lane and array.  The
+// take needs nothing from the item the wave is working on, and that item's stores need nothing from the take -- so a wave
+// takes its NEXT item while the current one finishes (step_body: after the solver of the tick's last step), and the
+// atomics, the acquire and the first-touch loads of the rows run under the integrator and the epilogue instead of in
+// front of an idle SIMD slot.  The rows go to LDS at the start of the next pass (the current item still uses Sm).
+struct QueueItem {
+  bool have = false;
+  int env = 0, tick = 0, shard = 0, nprops = 0;
+  float qpos = 0.f, qvel = 0.f, qacc = 0.f, qfine = 0.f, ctrl = 0.f, prop_size = 0.f;
+};
+// Which kernels take early: the Newton instantiations (profiles/r19a_kernel_resource_usage.txt: no scratch beyond the
+// parent's 8 bytes, two waves per SIMD).  The PGS queue kernels sit at 256 VGPRs with scratch already and keep the
+// serial take.
+#ifdef MRE_NEWTON
+constexpr bool Q_EARLY_TAKE = true;
+#else
+constexpr bool Q_EARLY_TAKE = false;
+#endif
+MRE_DEV void queue_take(const StepArgs& a, int l, int home, bool wait, QueueItem& it) {
+  it.have = queue_pop(a, l, home, it.env, it.tick, it.shard, wait);
+  if (!it.have) return;
+  if (it.tick > 0 || Q_LARGE) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  const size_t e = (size_t)it.env;
+  it.qpos = l < NQP ? a.qpos[e * NQP + l] : 0.f;
+  it.qvel = l < NVP ? a.qvel[e * NVP + l] : 0.f;
+  it.qacc = l < NVP ? a.qacc_ws[e * NVP + l] : 0.f;
+  it.qfine = l < QFINE && a.qfine != nullptr ? a.qfine[e * QFINE_ROW + l] : 0.f;
+  it.ctrl = l < NU ? a.ctrl[e * NU + l] : 0.f;
+  it.prop_size = l < NPROP * 3 ? a.prop_size[e * NPROP * 3 + l] : 0.f;
+  it.nprops = a.nprops[e];
 }
 
 template <bool QUEUE>
@@ -1592,10 +1682,17 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
       __builtin_amdgcn_s_sleep(127);
     }
   }
+  const int qhome = QUEUE ? (int)(blockIdx.x % (unsigned)(Q_LARGE ? a.q_lshards : a.q_shards)) : 0;
+  QueueItem next;   // QUEUE: the item of the pass to come (taken early, or here)
  for (;;) {
   if (QUEUE) {
-    if (!queue_pop(a, l, (int)(blockIdx.x % (unsigned)(Q_LARGE ? a.q_lshards : a.q_shards)), env, qtick, qshard)) return;
-    if (qtick > 0 || Q_LARGE) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    // Nothing taken early -- the first pass, nothing was ready then, or a kernel that takes serially: the look of a wave
+    // that has listed its own env ("a wave that finds nothing ready leaves"; large waves wait as they always did).  The
+    // env this wave has just listed is in the lists by now, so it is found here if no other wave took it.
+    if (!next.have) queue_take(a, l, qhome, true, next);
+    if (!next.have) return;
+    env = next.env; qtick = next.tick; qshard = next.shard;
+    next.have = false;
   }
   const int step_lo = QUEUE ? qtick * a.control_steps : 0, step_hi = QUEUE ? step_lo + a.control_steps : a.nsteps;
   if (QUEUE && !Q_LARGE && qtick == 0 && a.large != nullptr && a.large[env] != 0) continue;   // (in the large shard's list)
@@ -1620,21 +1717,22 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
 
   // ---- load state (one coalesced row per array); with a save area, the rows as they were before this launch are
   // copied aside on the way (the host puts an env that overflows the compact capacities back to them and re-runs it)
-  const bool save = a.sv_qpos != nullptr && step_lo == 0;
+  // (QUEUE: nothing is re-run, so no save area; the rows were loaded into registers when the item was taken: queue_take)
+  const bool save = !QUEUE && a.sv_qpos != nullptr && step_lo == 0;
   if (l < NQP) {
-    const float v = a.qpos[(size_t)env * NQP + l];
+    const float v = QUEUE ? next.qpos : a.qpos[(size_t)env * NQP + l];
     s.qpos[l] = v;
     if (save) a.sv_qpos[(size_t)env * NQP + l] = v;
   }
   if (l < NVP) {
-    const float v = a.qvel[(size_t)env * NVP + l], w = a.qacc_ws[(size_t)env * NVP + l];
+    const float v = QUEUE ? next.qvel : a.qvel[(size_t)env * NVP + l], w = QUEUE ? next.qacc : a.qacc_ws[(size_t)env * NVP + l];
     s.qvel[l] = v;
     s.qacc[l] = w;      // warm start (see Sm)
     s.qfrc_con[l] = 0.f;
     if (save) { a.sv_qvel[(size_t)env * NVP + l] = v; a.sv_qacc_ws[(size_t)env * NVP + l] = w; }
   }
   if (l < QFINE) {
-    const float v = a.qfine != nullptr ? a.qfine[(size_t)env * QFINE_ROW + l] : 0.f;
+    const float v = QUEUE ? next.qfine : a.qfine != nullptr ? a.qfine[(size_t)env * QFINE_ROW + l] : 0.f;
     s.qlo[l] = v;
     if (save && a.qfine != nullptr) a.sv_qfine[(size_t)env * QFINE_ROW + l] = v;
   }
@@ -1644,7 +1742,7 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
   float cube_lo_keep = 0.f;
   if (QUEUE && !Q_LARGE && a.qfine != nullptr && l < QFINE_ROW - QFINE) cube_lo_keep = a.qfine[(size_t)env * QFINE_ROW + QFINE + l];
   if (l < NU) {
-    const float v = a.ctrl[(size_t)env * NU + l];
+    const float v = QUEUE ? next.ctrl : a.ctrl[(size_t)env * NU + l];
     s.ctrl[l] = v;
     if (save) a.sv_ctrl[(size_t)env * NU + l] = v;
   }
@@ -1653,12 +1751,12 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
     a.sv_status[env] = a.status[env];
     a.sv_converged[env] = a.converged != nullptr ? a.converged[env] : (uint8_t)0;
   }
-  if (l == 0) { s.nprops = a.nprops[env]; s.overflow = 0; s.ncon = 0; s.nefc = 0; s.solver_iters = 0; }
+  if (l == 0) { s.nprops = QUEUE ? next.nprops : a.nprops[env]; s.overflow = 0; s.ncon = 0; s.nefc = 0; s.solver_iters = 0; }
 #ifdef MRE_NEWTON
   if (l < 24) s.zrow[l] = 0.f;
 #endif
   if (l < NPROP * 3) {
-    const float sz = a.prop_size[(size_t)env * NPROP * 3 + l];
+    const float sz = QUEUE ? next.prop_size : a.prop_size[(size_t)env * NPROP * 3 + l];
     s.prop_size[l / 3][l % 3] = sz;
   }
   MRE_SYNC();
@@ -1773,9 +1871,17 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
       MRE_SYNC();
     }
 
+    // QUEUE: the next item, while this one finishes (QueueItem).  One look, never a wait; nothing ready: the wave looks
+    // again after it has listed this env, at the top of the loop.
+    if (QUEUE && Q_EARLY_TAKE && step + 1 == step_hi) queue_take(a, l, qhome, false, next);
+    // (QUEUE: the cubes' low words were stored write-through by the last step's integrator, which drops them from this
+    //  XCD's L2 -- one load per lane brings their lines back while the set-up below runs, for the integrator's reads)
+    float cube_lo_warm = 0.f;
+    if (QUEUE && Q_WRITE_THROUGH && a.qfine != nullptr && l < QFINE_ROW - QFINE) cube_lo_warm = a.qfine[(size_t)env * QFINE_ROW + QFINE + l];
     integrate_setup(M, s, l, clamped);
     factor_solve_robot(mh_store(s), s.scratch, l);
-    integrate(M, s, l, a.flags, polished, a.qfine != nullptr ? a.qfine + (size_t)env * QFINE_ROW + QFINE_CUBE_Q : nullptr);
+    if (QUEUE && Q_WRITE_THROUGH) keep_live(cube_lo_warm);
+    integrate<QUEUE && Q_WRITE_THROUGH>(M, s, l, a.flags, polished, a.qfine != nullptr ? a.qfine + (size_t)env * QFINE_ROW + QFINE_CUBE_Q : nullptr);
     steps_done = step + 1 - step_lo;
     if ((a.flags & F_SETTLE_EXIT) != 0) {
       // PropPlacer's settle test on this env's own cubes (prop_initializer.py:247-258)
@@ -1826,10 +1932,14 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
           }
           v = (float)(h & 0x3FFFFFu);
         }
-        a.trace[((size_t)(a.trace_base + step) * a.trace_nenv + env) * TRACE_W + l] = v;
+        // (QUEUE, write-through: an abandoned tick's rows are written again by the large kernel's wave -- this wave's
+        //  stores must have left for memory before the env is listed there, like the words that travel: queue_push)
+        travel_store<QUEUE && Q_WRITE_THROUGH>(&a.trace[((size_t)(a.trace_base + step) * a.trace_nenv + env) * TRACE_W + l], v);
       }
       // columns TRACE_QVEL .. TRACE_QVEL + 38: qvel after the step (north_star compares qpos AND qvel; the float32 words)
-      if (l < NVP) a.trace[((size_t)(a.trace_base + step) * a.trace_nenv + env) * TRACE_W + TRACE_QVEL + l] = l < NV ? s.qvel[l] : 0.f;
+      if (l < NVP)
+        travel_store<QUEUE && Q_WRITE_THROUGH>(&a.trace[((size_t)(a.trace_base + step) * a.trace_nenv + env) * TRACE_W + TRACE_QVEL + l],
+                                               l < NV ? s.qvel[l] : 0.f);
     }
     if (settled) break;
   }
@@ -1837,6 +1947,20 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
   if (a.settle_steps != nullptr && l == 0) a.settle_steps[env] = settled ? steps_done : -steps_done;
   // QUEUE, compact kernel: a tick that overflowed is abandoned and the env handed over to the large shard (queue_pop)
   const bool hand_over = QUEUE && !Q_LARGE && s.overflow != 0;
+  if (QUEUE && Q_WRITE_THROUGH) {
+    // ---- store state, first: the rows travel with the env (queue_push), write-through; they drain while the rest of the
+    // epilogue runs, and the env is listed after this wave's vmcnt(0).  (Nothing below changes a row: the final
+    // kinematics reads them.)
+    if (hand_over) {
+      if (a.qfine != nullptr && l < QFINE_ROW - QFINE) q_store(a.qfine + (size_t)env * QFINE_ROW + QFINE + l, cube_lo_keep);
+    } else {
+      q_store_row(a.qpos + (size_t)env * NQP, s.qpos, NQP, l);
+      q_store_row(a.qvel + (size_t)env * NVP, s.qvel, NVP, l);
+      q_store_row(a.qacc_ws + (size_t)env * NVP, s.qacc, NVP, l, true);
+      if (a.qfine != nullptr) q_store_row(a.qfine + (size_t)env * QFINE_ROW, s.qlo, QFINE, l);
+      q_store_row(a.ctrl + (size_t)env * NU, s.ctrl, NU, l);
+    }
+  }
   if (a.nstep != nullptr && l == 0 && !hand_over) {   // physics.data.time advances by steps_done * timestep
     // (QUEUE: words one wave after another updates are updated where every XCD sees them)
     if (QUEUE) __hip_atomic_fetch_add(a.nstep + env, steps_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1882,7 +2006,11 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
   if (a.mode == CTRL_OSC && a.nsteps > 0 && !hand_over) {
     if (q_last && osc_converged(M, s, oscp, s.osc_tgt)) arm_converged = true;
     if (l == 0) {
-      if (a.converged != nullptr) a.converged[env] = arm_converged ? 1 : 0;
+      if (a.converged != nullptr) {
+        // (QUEUE: travels with the env -- queue_push)
+        if (QUEUE && Q_WRITE_THROUGH) __hip_atomic_store(a.converged + env, (uint8_t)(arm_converged ? 1 : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else a.converged[env] = arm_converged ? 1 : 0;
+      }
       if (q_last && !arm_converged && a.status != nullptr && (a.flags & F_CONV_OPEN) == 0) {
         if (QUEUE) __hip_atomic_fetch_or(a.status + env, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else a.status[env] |= 1u;
@@ -1910,8 +2038,9 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
       o[6] = q[0]; o[7] = q[1]; o[8] = q[2]; o[9] = q[3];
     }
   }
-  // ---- store state
-  if (hand_over) {
+  // ---- store state (QUEUE, write-through: done above)
+  if (QUEUE && Q_WRITE_THROUGH) {
+  } else if (hand_over) {
     if (a.qfine != nullptr && l < QFINE_ROW - QFINE) a.qfine[(size_t)env * QFINE_ROW + QFINE + l] = cube_lo_keep;
   } else {
     if (l < NQP) a.qpos[(size_t)env * NQP + l] = s.qpos[l];
@@ -1939,7 +2068,11 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
         moved = q_load(qa + 0) >> 16;
       }
       if (hand_over) moved = 1;
-      if (q_more || hand_over) { qa[0] = hw_ncon | (moved << 16); qa[1] = hw_nefc; qa[2] = hw_nrrow | (hw_npp << 16); qa[3] = (int)dt; }
+      if ((q_more || hand_over) && Q_WRITE_THROUGH) {
+        q_store(qa + 0, hw_ncon | (moved << 16)); q_store(qa + 1, hw_nefc); q_store(qa + 2, hw_nrrow | (hw_npp << 16)); q_store(qa + 3, (int)dt);
+      } else if (q_more || hand_over) {
+        qa[0] = hw_ncon | (moved << 16); qa[1] = hw_nefc; qa[2] = hw_nrrow | (hw_npp << 16); qa[3] = (int)dt;
+      }
       else dt /= (unsigned long long)(qtick + 1);
     }
     if (!q_more && !hand_over) {
@@ -1961,7 +2094,9 @@ MRE_DEV void step_body(const StepArgs& a, Sm& s) {
     if (s.overflow) st |= 4u;
     if (QUEUE) { if (st) __hip_atomic_fetch_or(a.status + env, st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     else a.status[env] |= st;
-    if (a.stats != nullptr && a.nsteps > 0) {
+    // (QUEUE, write-through: the host reads the last tick's; a plain store per tick, from a wave on another XCD each
+    //  time and with no write-back in between, could reach memory after a later tick's)
+    if (a.stats != nullptr && a.nsteps > 0 && !(QUEUE && Q_WRITE_THROUGH && q_more)) {
       a.stats[env * 4 + 0] = s.ncon; a.stats[env * 4 + 1] = s.nefc;
       a.stats[env * 4 + 2] = s.solver_iters; a.stats[env * 4 + 3] = s.nl;
 #ifdef MRE_PHASE_STAMPS

@@ -108,6 +108,18 @@ inline int free_stage(int cur, const int* younger_stages, int nyounger) {
   return fs;
 }
 
+// Spare waves of the large kernel's WAITING launch (queue_large_waves below: `spare_large`), by need.  Each spare wave
+// holds 26.5 KB of LDS on its compute unit for the whole launch (room for six compact waves there instead of eight) and
+// is of use only when a compact wave hands an env over.  A launch that follows one without a hand-over keeps ONE; a
+// launch that follows hand-overs keeps the 8 measured in mre_env.h.  MRE_QUEUE_SPARE_LARGE (`forced` >= 0) overrides
+// both.  Results never depend on the count: whatever the waiting launch leaves is done by the large launch behind the
+// compact kernel (mre_sched.cpp); only WHERE a hand-over waits does.
+constexpr int QUEUE_SPARE_LARGE_QUIET = 1, QUEUE_SPARE_LARGE_BUSY = 8;
+inline int queue_spare_large(int last_handovers, int forced) {
+  if (forced >= 0) return forced;
+  return last_handovers > 0 ? QUEUE_SPARE_LARGE_BUSY : QUEUE_SPARE_LARGE_QUIET;
+}
+
 // Waves of the large kernel's WAITING launch in a queue launch over the envs [lo, lo + n), `nl` of them flagged large
 // (`large`: the flags the kernels will read; `info_last`: every env's latest record).
 // A wave per env that is large already and some for those that come over (the spare waves, or as many as the launch

@@ -220,7 +220,8 @@ static int launch_group_enqueue(mre_env* e, mre_env::Group& G, const StepArgs& a
     // 1. the large kernel's waiting launch, first: see step_body (q_gen)
     StepArgs al = ac;
     al.want_large = 1; al.q_wait = 1;
-    const int lw = policy::queue_large_waves(e->h_info_last, fl, G.lo, G.n, nl, e->queue_last_handovers, e->queue_spare_large,
+    const int lw = policy::queue_large_waves(e->h_info_last, fl, G.lo, G.n, nl, e->queue_last_handovers,
+                                             policy::queue_spare_large(e->queue_last_handovers, e->queue_spare_large),
                                              e->queue_large_waves_max);
     // (test knob MRE_QUEUE_TEST_SERIAL=1: on the compact kernel's own stream, i.e. strictly before it -- what a profiler
     //  that serialises dispatches makes of the two streams; the launch then leaves after its bounded wait and the one
