@@ -391,6 +391,34 @@ int mre_heightmap(void* stream, const float* depth, const uint8_t* rgb, const ui
                   const float* cam, const float* bounds, float inv_cell, float max_depth, int out_h, int out_w,
                   float* hmap, uint8_t* cmap, uint8_t* smap, int32_t* src);
 
+/* The same maps from several cameras in one pass (csrc/mre_heightmap_views.hip): the pixels of `views`
+ * views compete for the cells of one set of maps, so that what one camera cannot see another fills in.
+ *   depth, rgb, seg  HOST arrays of `views` device pointers, view i holding n frames [n][height[i]][width[i]] with the
+ *                    layouts and alignments of mre_heightmap; rgb and seg may be NULL, and when one is given every one
+ *                    of its `views` entries is non-NULL
+ *   height, width    HOST i32 [views]: the views may differ in size
+ *   cam              HOST f32 [views][12]: cam of mre_heightmap for every view
+ *   bounds, inv_cell, max_depth, out_h, out_w: those of mre_heightmap, shared by all views
+ * Per pixel of every view the statement of mre_heightmap holds word for word.  Cell (row cy, column cx) of env e takes
+ * the valid pixel with the largest hz over all views, among equal hz the one of the smallest view index i, inside that
+ * view the smallest index v * width[i] + u.  Equivalently: the result is the merge of the `views` single-view maps of
+ * mre_heightmap -- per cell the largest hz among the views that filled it, the lowest view among equal hz.
+ *   hmap, cmap, smap, src  as mre_heightmap's, with the same values for an empty cell; src is the index inside the
+ *                    winning view's image; cmap NULL if and only if rgb is NULL, smap NULL if and only if seg is NULL
+ *   view   device u8 [n][out_h][out_w]     the winning view    255            or NULL
+ * With views == 1 every output it shares with mre_heightmap equals that call's bit for bit.  Every element of every
+ * non-NULL output is written exactly once by the call and nothing else is; no byte outside the views' images is read; the
+ * outputs are the same bits on every run; no global atomics, no init pass, no workspace.  Enqueued on `stream` of the
+ * current device; nothing synchronises.
+ * MRE_ERR_ARG, with nothing launched, unless 1 <= views <= MRE_HM_MAX_VIEWS, the conditions of mre_heightmap hold for
+ * every view and for the shared arguments, every height[i] * width[i] < 2^28 (view and index then fit the low word of
+ * one 64-bit key, and no key is 0), and view is NULL or a device pointer.  n == 0: MRE_OK, nothing launched. */
+#define MRE_HM_MAX_VIEWS 8
+int mre_heightmap_views(void* stream, int views, const float* const* depth, const uint8_t* const* rgb,
+                        const uint8_t* const* seg, int n, const int32_t* height, const int32_t* width, const float* cam,
+                        const float* bounds, float inv_cell, float max_depth, int out_h, int out_w, float* hmap,
+                        uint8_t* cmap, uint8_t* smap, int32_t* src, uint8_t* view);
+
 /* Warped and cropped maps on the device (csrc/mre_warp.hip): a nearest-neighbour affine gather of the
  * maps of mre_heightmap (or any maps of that layout) -- the SE(2) perturbation and the rotated pick crops of a Transporter
  * training sample are both calls of it.

@@ -5,7 +5,8 @@
 //
 //   k_heightmap   one workgroup per (env, tile of T x T cells, T = HM_TILE).  The tile's cells are 64-bit keys in LDS
 //                 ((height bits << 32) | ~index: hm_key), 0 = empty.  The workgroup projects the 8 corners of the
-//                 tile's box [x range] x [y range] x [lo_z, hi_z] into the image, scans the bounding rectangle of the
+//                 tile's box [x range] x [y range] x [lo_z, hi_z] into the image (tile_rect of csrc/mre_heightmap.h, which
+//                 csrc/mre_heightmap_views.hip shares), scans the bounding rectangle of the
 //                 projections widened by 2 pixels (the whole image when a corner is not in front of the camera), does
 //                 one LDS atomicMax for every pixel that lands in its own tile, and then writes the tile: rgb and seg
 //                 are read for the winners only.
@@ -22,42 +23,6 @@ namespace {
 constexpr int NT = 256;     // threads per workgroup
 constexpr int UNROLL = 4;   // depth loads a lane has in flight
 constexpr int T = HM_TILE;
-
-struct Rect { uint32_t u0, v0, rw, count; };   // first column and row, columns, pixels (0: nothing to scan)
-
-// the source rectangle of the tile whose cells are columns [cx0, cx1) and rows [cy0, cy1)
-__device__ __forceinline__ Rect tile_rect(const HeightmapArgs& a, uint32_t cx0, uint32_t cx1, uint32_t cy0, uint32_t cy1) {
-  const float wm = (float)(a.w - 1), hm = (float)(a.h - 1);
-  bool whole = a.whole_image != 0;
-  float umin = 3.0e38f, umax = -3.0e38f, vmin = 3.0e38f, vmax = -3.0e38f;
-  const float xs[2] = {a.g.lo[0] + (float)cx0 * a.cell, a.g.lo[0] + (float)cx1 * a.cell};
-  const float ys[2] = {a.g.lo[1] + (float)cy0 * a.cell, a.g.lo[1] + (float)cy1 * a.cell};
-  const float zs[2] = {a.g.lo[2], a.g.hi[2]};
-#pragma unroll
-  for (int c = 0; c < 8; c++) {
-    const float px = xs[c & 1] - a.g.cam[9], py = ys[(c >> 1) & 1] - a.g.cam[10], pz = zs[c >> 2] - a.g.cam[11];
-    const float q0 = a.inv[0] * px + a.inv[1] * py + a.inv[2] * pz;
-    const float q1 = a.inv[3] * px + a.inv[4] * py + a.inv[5] * pz;
-    const float q2 = a.inv[6] * px + a.inv[7] * py + a.inv[8] * pz;   // the corner's depth: minus its camera-frame z
-    if (!(q2 >= 1e-3f)) whole = true;
-    const float r = 1.0f / q2;
-    const float u = q0 * r, v = q1 * r;
-    umin = fminf(umin, u); umax = fmaxf(umax, u);   // fminf / fmaxf drop a NaN
-    vmin = fminf(vmin, v); vmax = fmaxf(vmax, v);
-  }
-  float u0 = 0.f, u1 = wm, v0 = 0.f, v1 = hm;
-  if (!whole) {
-    u0 = fmaxf(floorf(umin) - 2.f, 0.f); u1 = fminf(ceilf(umax) + 2.f, wm);
-    v0 = fmaxf(floorf(vmin) - 2.f, 0.f); v1 = fminf(ceilf(vmax) + 2.f, hm);
-  }
-  Rect r = {0u, 0u, 1u, 0u};
-  if (u0 <= u1 && v0 <= v1) {   // all four are now inside the image
-    r.u0 = (uint32_t)u0; r.v0 = (uint32_t)v0;
-    r.rw = (uint32_t)u1 - r.u0 + 1u;
-    r.count = r.rw * ((uint32_t)v1 - r.v0 + 1u);   // <= h * w < 2^31
-  }
-  return r;
-}
 
 __global__ void __launch_bounds__(NT) k_heightmap(HeightmapArgs a) {
   __shared__ unsigned long long keys[T * T];

@@ -55,4 +55,13 @@ MRE_HM_HD inline HmPoint hm_point(const HmGrid& g, float u, float v, float d) {
 MRE_HM_HD inline unsigned long long hm_key(uint32_t hz_bits, uint32_t index) {
   return ((unsigned long long)hz_bits << 32) | (unsigned long long)(0xFFFFFFFFu - index);
 }
+
+// The key of a pixel of one of several views (csrc/mre_heightmap_views.hip): the view (< 16) above the
+// index (< 2^28) in the low word, so that among equal heights the smallest view wins and inside it the smallest index.
+// View 0 gives hm_key; no pixel has key 0.
+MRE_HM_HD inline unsigned long long hm_key_view(uint32_t hz_bits, uint32_t view, uint32_t index) {
+  return hm_key(hz_bits, (view << 28) | index);
+}
+MRE_HM_HD inline uint32_t hm_key_which(unsigned long long key) { return (0xFFFFFFFFu - (uint32_t)key) >> 28; }
+MRE_HM_HD inline uint32_t hm_key_index(unsigned long long key) { return (0xFFFFFFFFu - (uint32_t)key) & 0x0FFFFFFFu; }
 #endif

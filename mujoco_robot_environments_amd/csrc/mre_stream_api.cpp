@@ -191,6 +191,25 @@ extern "C" int mre_seg_labels(void* stream, const uint8_t* seg, const float* dep
 }
 
 // ---- orthographic heightmaps on the device (csrc/mre_heightmap.hip): height, colour, label and source pixel per cell
+// the inverse of A (cam[0 .. 9), formed in float64) bounds the pixels a tile can take (the source rectangle); false when
+// there is no usable one, and every tile then scans the whole image
+static bool heightmap_inverse(const float* cam, float* inv) {
+  const double m[9] = {cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7], cam[8]};
+  const double co[9] = {m[4] * m[8] - m[5] * m[7], m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
+                        m[5] * m[6] - m[3] * m[8], m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
+                        m[3] * m[7] - m[4] * m[6], m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]};
+  const double det = m[0] * co[0] + m[1] * co[3] + m[2] * co[6];
+  double big = 0.0;
+  for (int k = 0; k < 9; k++) big = std::max(big, std::fabs(m[k]));
+  bool usable = std::isfinite(det) && std::fabs(det) > 1e-12 * big * big * big && std::isfinite(cam[9]) &&
+                std::isfinite(cam[10]) && std::isfinite(cam[11]);
+  for (int k = 0; k < 9; k++) {
+    inv[k] = (float)(co[k] / det);
+    usable = usable && std::isfinite(inv[k]);
+  }
+  return usable;
+}
+
 extern "C" int mre_heightmap(void* stream, const float* depth, const uint8_t* rgb, const uint8_t* seg, int n, int height,
                              int width, const float* cam, const float* bounds, float inv_cell, float max_depth, int out_h,
                              int out_w, float* hmap, uint8_t* cmap, uint8_t* smap, int32_t* src) {
@@ -221,25 +240,68 @@ extern "C" int mre_heightmap(void* stream, const float* depth, const uint8_t* rg
   for (int k = 0; k < 3; k++) { a.g.lo[k] = bounds[k]; a.g.hi[k] = bounds[3 + k]; }
   a.g.inv_cell = inv_cell; a.g.max_depth = max_depth; a.g.out_w = (float)out_w; a.g.out_h = (float)out_h;
   a.cell = (float)(1.0 / (double)inv_cell);
-  // the inverse of A bounds the pixels a tile can take (the source rectangle); without one every tile scans the image
-  const double m[9] = {cam[0], cam[1], cam[2], cam[3], cam[4], cam[5], cam[6], cam[7], cam[8]};
-  const double co[9] = {m[4] * m[8] - m[5] * m[7], m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
-                        m[5] * m[6] - m[3] * m[8], m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
-                        m[3] * m[7] - m[4] * m[6], m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]};
-  const double det = m[0] * co[0] + m[1] * co[3] + m[2] * co[6];
-  double big = 0.0;
-  for (int k = 0; k < 9; k++) big = std::max(big, std::fabs(m[k]));
-  bool usable = std::isfinite(det) && std::fabs(det) > 1e-12 * big * big * big && std::isfinite(cam[9]) &&
-                std::isfinite(cam[10]) && std::isfinite(cam[11]);
-  for (int k = 0; k < 9; k++) {
-    a.inv[k] = (float)(co[k] / det);
-    usable = usable && std::isfinite(a.inv[k]);
-  }
-  a.whole_image = usable ? 0u : 1u;
+  a.whole_image = heightmap_inverse(cam, a.inv) ? 0u : 1u;
   a.out_h = (uint32_t)out_h; a.out_w = (uint32_t)out_w;
   a.tiles_x = (a.out_w + HM_TILE - 1) / HM_TILE; a.tiles_y = (a.out_h + HM_TILE - 1) / HM_TILE;
   a.hmap = hmap; a.cmap = cmap; a.smap = smap; a.src = src;
   mre_launch_heightmap(&a, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
+// ---- the same maps from several views at once (csrc/mre_heightmap_views.hip): the views' pixels compete for the cells
+extern "C" int mre_heightmap_views(void* stream, int views, const float* const* depth, const uint8_t* const* rgb,
+                                   const uint8_t* const* seg, int n, const int32_t* height, const int32_t* width,
+                                   const float* cam, const float* bounds, float inv_cell, float max_depth, int out_h,
+                                   int out_w, float* hmap, uint8_t* cmap, uint8_t* smap, int32_t* src, uint8_t* view) {
+  static_assert(HM_MAX_VIEWS == MRE_HM_MAX_VIEWS, "the kernel's argument array holds the header's view count");
+  const std::string w("mre_heightmap_views");
+  if (views < 1 || views > MRE_HM_MAX_VIEWS) return fail(MRE_ERR_ARG, w + ": 1 <= views <= 8");
+  if (n < 0 || !height || !width) return fail(MRE_ERR_ARG, w + ": n >= 0, height and width non-null");
+  for (int i = 0; i < views; i++)
+    if (height[i] < 1 || width[i] < 1 || (long long)height[i] * width[i] >= (long long)HM_VIEW_PIXELS)
+      return fail(MRE_ERR_ARG, w + ": height and width >= 1, height * width < 2^28 in every view");
+  if (out_h < 1 || out_w < 1 || out_h > (int)HM_MAX_OUT || out_w > (int)HM_MAX_OUT)
+    return fail(MRE_ERR_ARG, w + ": 1 <= out_h, out_w <= 4096");
+  if (!(inv_cell > 0.f) || !(max_depth > 0.f) || !std::isfinite(inv_cell) || !std::isfinite(max_depth))
+    return fail(MRE_ERR_ARG, w + ": inv_cell and max_depth must be positive and finite");
+  if (!cam || !bounds) return fail(MRE_ERR_ARG, w + ": null cam or bounds");
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(bounds[k]) || !std::isfinite(bounds[3 + k]) || !(bounds[k] <= bounds[3 + k]))
+      return fail(MRE_ERR_ARG, w + ": bounds must be finite with lo <= hi");
+  if (!depth || !hmap) return fail(MRE_ERR_ARG, w + ": null depth or hmap");
+  if ((rgb == nullptr) != (cmap == nullptr)) return fail(MRE_ERR_ARG, w + ": rgb and cmap go together");
+  if ((seg == nullptr) != (smap == nullptr)) return fail(MRE_ERR_ARG, w + ": seg and smap go together");
+  for (int i = 0; i < views; i++) {
+    if (!depth[i] || (rgb && !rgb[i]) || (seg && !seg[i]))
+      return fail(MRE_ERR_ARG, w + ": depth, and rgb and seg when given, must be non-null in every view");
+    if ((uintptr_t)depth[i] & 3) return fail(MRE_ERR_ARG, w + ": depth, hmap and src must be 4-byte aligned");
+  }
+  if (((uintptr_t)hmap & 3) || ((uintptr_t)src & 3)) return fail(MRE_ERR_ARG, w + ": depth, hmap and src must be 4-byte aligned");
+  if (n == 0) return MRE_OK;
+  bool on_device = is_device_ptr(hmap) && (!cmap || is_device_ptr(cmap)) && (!smap || is_device_ptr(smap)) &&
+                   (!src || is_device_ptr(src)) && (!view || is_device_ptr(view));
+  for (int i = 0; i < views && on_device; i++)
+    on_device = is_device_ptr(depth[i]) && (!rgb || is_device_ptr(rgb[i])) && (!seg || is_device_ptr(seg[i]));
+  if (!on_device)
+    return fail(MRE_ERR_ARG, w + ": depth, rgb, seg, hmap, cmap, smap, src and view must be device pointers");
+  HeightmapViewsArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int i = 0; i < views; i++) {
+    HeightmapView& v = a.v[i];
+    v.depth = depth[i]; v.rgb = rgb ? rgb[i] : nullptr; v.seg = seg ? seg[i] : nullptr;
+    v.h = (uint32_t)height[i]; v.w = (uint32_t)width[i]; v.hw = v.h * v.w;
+    memcpy(v.cam, cam + 12 * i, sizeof(v.cam));
+    v.whole_image = heightmap_inverse(v.cam, v.inv) ? 0u : 1u;
+  }
+  a.views = (uint32_t)views; a.n = (uint32_t)n;
+  for (int k = 0; k < 3; k++) { a.g.lo[k] = bounds[k]; a.g.hi[k] = bounds[3 + k]; }
+  a.g.inv_cell = inv_cell; a.g.max_depth = max_depth; a.g.out_w = (float)out_w; a.g.out_h = (float)out_h;
+  a.cell = (float)(1.0 / (double)inv_cell);
+  a.out_h = (uint32_t)out_h; a.out_w = (uint32_t)out_w;
+  a.tiles_x = (a.out_w + HM_TILE - 1) / HM_TILE; a.tiles_y = (a.out_h + HM_TILE - 1) / HM_TILE;
+  a.hmap = hmap; a.cmap = cmap; a.smap = smap; a.src = src; a.view = view;
+  mre_launch_heightmap_views(&a, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
 }

@@ -35,6 +35,7 @@ UNITS = [("kernels", STEP_SOURCE, []), ("kernels_large", STEP_SOURCE, ["-DMRE_LA
          ("kernels_large_newton", STEP_SOURCE, ["-DMRE_LARGE_CAPS", "-DMRE_NEWTON"]),
          ("render", "mre_render.hip", []), ("records", "mre_records.hip", []),
          ("labels", "mre_labels.hip", []), ("heightmap", "mre_heightmap.hip", []),
+         ("heightmap_views", "mre_heightmap_views.hip", []),
          ("warp", "mre_warp.hip", []), ("warp_inputs", "mre_warp_inputs.hip", []),
          ("correlate", "mre_correlate.hip", []), ("correlate_grad", "mre_correlate_grad.hip", []),
          ("attend", "mre_attend.hip", []), ("api", "mre_api.cpp", []), ("stream_api", "mre_stream_api.cpp", []),
@@ -79,6 +80,7 @@ _SIGNATURES = {
     "mre_varint_unpack_rows": [vp, fp, sz, fp, fp, fp, fp, ci, sz, fp, sz, fp, fp, sz],
     "mre_get_arm_dynamics": [vp, ci, fp], "mre_seg_labels": [vp, fp, fp, ci, ci, ci, ci, ci, fp, fp],
     "mre_heightmap": [vp, fp, fp, fp, ci, ci, ci, fp, fp, C.c_float, C.c_float, ci, ci, fp, fp, fp, fp],
+    "mre_heightmap_views": [vp, ci, fp, fp, fp, ci, fp, fp, fp, fp, C.c_float, C.c_float, ci, ci, fp, fp, fp, fp, fp],
     "mre_warp_maps": [vp, fp, fp, fp, ci, ci, ci, fp, fp, ci, ci, ci, fp, fp, fp, fp],
     "mre_warp_inputs": [vp, fp, fp, ci, ci, ci, fp, fp, ci, ci, ci, ci, fp, fp, fp, ci, fp],
     "mre_correlate_workspace": [ci, ci, ci, ci, C.POINTER(sz)],

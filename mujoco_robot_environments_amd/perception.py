@@ -12,6 +12,10 @@ of their coordinates (the centroid) and the smallest depth among them.  ``Batche
 depth / rgb / seg frames of every env (``BatchedRearrangementEnv.heightmap``); ``world_2_cell`` puts pick and place
 points into the same map.
 
+``heightmap_views``: the same maps from several cameras in one launch of ``mre_heightmap_views``
+(csrc/mre_heightmap_views.hip) -- every view's pixels compete for the cells, so that what one camera cannot see another
+fills in; a ``FusedHeightMap`` also says which view every cell came from (``BatchedRearrangementEnv.heightmap_views``).
+
 ``warp_maps``: a nearest-neighbour affine gather of those maps, and on it what a Transporter learner does to every
 sample: a random SE(2) perturbation of the map with its pick and place cells (``sample_perturbation``) and the rotated
 crops around the pick cell (``crop_matrices``), together ``transporter_sample``
@@ -282,6 +286,115 @@ def heightmap(depth: torch.Tensor, rgb: Optional[torch.Tensor] = None, seg: Opti
                                                 b.ctypes.data, float(inv_cell), float(np.float32(max_depth)), out_h, out_w,
                                                 height.data_ptr(), ptr(colour), ptr(smap), src.data_ptr()), "mre_heightmap")
     return HeightMap(height, colour, smap, src)
+
+
+# ------------------------------------------------------------------------------------------ several views, one set of maps
+# HeightMap's four fields, so that whatever indexes maps[0 .. 3] takes it as it is, then view uint8 [N, out_h, out_w]: the
+# view whose pixel the cell holds, 255 where the cell is empty.  src is the pixel's index inside THAT view's image.
+FusedHeightMap = collections.namedtuple("FusedHeightMap", ["height", "colour", "seg", "src", "view"])
+MAX_VIEWS = 8              # MRE_HM_MAX_VIEWS
+MAX_VIEW_PIXELS = 2 ** 28  # pixels of one view's image, exclusive
+
+
+def _views_args(views, bounds, cell, max_depth):
+    """The argument checks of ``heightmap_views``: [(depth, rgb, seg, cam float32 [12])] with every view of ``heightmap``'s
+    shapes, the same number of frames, and rgb / seg in every view or in none."""
+    views = [tuple(v) for v in views]
+    if not 1 <= len(views) <= MAX_VIEWS:
+        raise ValueError(f"1 to {MAX_VIEWS} views")
+    _grid(bounds, cell)
+    out_h, out_w = heightmap_shape(bounds, cell)
+    if not (np.isfinite(max_depth) and max_depth > 0):
+        raise ValueError("max_depth must be positive and finite")
+    if out_h > MAX_MAP or out_w > MAX_MAP:
+        raise ValueError(f"a map has at most {MAX_MAP} rows and columns")
+    res = []
+    for v in views:
+        if len(v) != 4:
+            raise ValueError("a view is (depth, rgb, seg, cam)")
+        depth, rgb, seg, cam = v
+        if depth.dim() != 3:
+            raise ValueError("depth must be [N, H, W]")
+        if rgb is not None and tuple(rgb.shape) != tuple(depth.shape) + (3,):
+            raise ValueError("rgb must be [N, H, W, 3]")
+        if seg is not None and tuple(seg.shape) != tuple(depth.shape):
+            raise ValueError("seg must have depth's shape")
+        h, w = int(depth.shape[1]), int(depth.shape[2])
+        if h < 1 or w < 1 or h * w >= MAX_VIEW_PIXELS:
+            raise ValueError("a view's images must have at least one pixel and fewer than 2^28")
+        res.append((depth, rgb, seg, np.ascontiguousarray(np.asarray(cam, np.float32).reshape(12))))
+    if len({int(v[0].shape[0]) for v in res}) != 1:
+        raise ValueError("every view holds the same number of frames")
+    for k, what in ((1, "rgb"), (2, "seg")):
+        if len({v[k] is None for v in res}) != 1:
+            raise ValueError(f"{what} is given for every view or for none")
+    return res
+
+
+def heightmap_views_reference(views, *, bounds, cell: float, max_depth: float = 99.0) -> FusedHeightMap:
+    """The statement of ``heightmap_views`` (include/mre.h, mre_heightmap_views) as the composition it replaces:
+    ``heightmap`` of every view of ``views`` = [(depth, rgb, seg, cam)], then the merge in plain torch on the first view's
+    device -- a cell takes the view with the largest height among those that filled it, the lowest view among equal
+    heights.  Bit for bit the statement on any device; the fallback of ``heightmap_views``."""
+    views = _views_args(views, bounds, cell, max_depth)
+    dev = views[0][0].device
+    out = None
+    for i, (depth, rgb, seg, cam) in enumerate(views):
+        m = heightmap(depth, rgb, seg, cam=cam, bounds=bounds, cell=cell, max_depth=max_depth)
+        m = HeightMap(*(None if x is None else x.to(dev) for x in m))
+        filled = m.src >= 0
+        which = torch.where(filled, i, 255).to(torch.uint8)
+        if out is None:
+            out = FusedHeightMap(m.height, m.colour, m.seg, m.src, which)
+            continue
+        # hz >= +0 orders like its bits; strictly higher only, so that the lower view keeps a tie
+        take = filled & ((out.src < 0) | (m.height.view(torch.int32) > out.height.view(torch.int32)))
+        out = FusedHeightMap(torch.where(take, m.height, out.height),
+                             None if m.colour is None else torch.where(take[..., None], m.colour, out.colour),
+                             None if m.seg is None else torch.where(take, m.seg, out.seg),
+                             torch.where(take, m.src, out.src), torch.where(take, which, out.view))
+    return out
+
+
+def heightmap_views(views, *, bounds, cell: float, max_depth: float = 99.0) -> FusedHeightMap:
+    """One set of top-down maps from several cameras: ``views`` is a sequence of up to 8 (depth [N, H, W], rgb
+    [N, H, W, 3] or None, seg [N, H, W] or None, cam) -- what ``heightmap`` takes for one view; the views may differ in
+    H x W, and rgb / seg are given for every view or for none.  Every view's pixels are binned as ``heightmap`` bins them
+    and compete for the cells: a cell takes the highest point any view saw in it, the lowest view among equal heights,
+    the first pixel inside that view -- the merge of the views' own ``heightmap`` outputs; see ``FusedHeightMap`` and
+    include/mre.h.  CUDA float32 depths with uint8 rgb / seg, all on one device, are one launch of
+    ``mre_heightmap_views`` (non-contiguous views are made contiguous first); anything else is computed by
+    ``heightmap_views_reference`` with the same return values.  One view gives ``heightmap``'s maps."""
+    views = _views_args(views, bounds, cell, max_depth)
+    dev = views[0][0].device
+    on_device = all(d.is_cuda and d.device == dev and d.dtype == torch.float32 and all(
+        x is None or (x.device == dev and x.dtype == torch.uint8) for x in (rgb, seg)) for d, rgb, seg, _ in views)
+    if not on_device:
+        return heightmap_views_reference(views, bounds=bounds, cell=cell, max_depth=max_depth)
+    views = [(d.contiguous(), None if rgb is None else rgb.contiguous(), None if seg is None else seg.contiguous(), cam)
+             for d, rgb, seg, cam in views]
+    lo, hi, inv_cell = _grid(bounds, cell)
+    out_h, out_w = heightmap_shape(bounds, cell)
+    n, nv = int(views[0][0].shape[0]), len(views)
+    has_rgb, has_seg = views[0][1] is not None, views[0][2] is not None
+    height = torch.empty((n, out_h, out_w), dtype=torch.float32, device=dev)
+    colour = torch.empty((n, out_h, out_w, 3), dtype=torch.uint8, device=dev) if has_rgb else None
+    smap = torch.empty((n, out_h, out_w), dtype=torch.uint8, device=dev) if has_seg else None
+    src = torch.empty((n, out_h, out_w), dtype=torch.int32, device=dev)
+    which = torch.empty((n, out_h, out_w), dtype=torch.uint8, device=dev)
+    if n:
+        ptr = lambda t: None if t is None else t.data_ptr()
+        pointers = lambda k: (C.c_void_p * nv)(*[v[k].data_ptr() for v in views])
+        sizes = np.ascontiguousarray([[v[0].shape[1], v[0].shape[2]] for v in views], np.int32).T.copy()
+        cams = np.ascontiguousarray(np.stack([v[3] for v in views]), np.float32)
+        b = np.ascontiguousarray(np.concatenate([lo, hi]), np.float32)
+        with _stream_on(dev) as stream:
+            _lib.check(_lib.lib().mre_heightmap_views(
+                stream, nv, pointers(0), pointers(1) if has_rgb else None, pointers(2) if has_seg else None, n,
+                sizes[0].ctypes.data, sizes[1].ctypes.data, cams.ctypes.data, b.ctypes.data, float(inv_cell),
+                float(np.float32(max_depth)), out_h, out_w, height.data_ptr(), ptr(colour), ptr(smap), src.data_ptr(),
+                which.data_ptr()), "mre_heightmap_views")
+    return FusedHeightMap(height, colour, smap, src, which)
 
 
 def world_2_cell(points, bounds, cell: float):

@@ -167,7 +167,8 @@ class BatchedRearrangementEnv:
             q = np.asarray(cam.quat, np.float64)
             q = q / np.linalg.norm(q)
             self._cameras[f"{cam.name}/{cam.name}"] = dict(pos=np.asarray(cam.pos, np.float64),
-                                                           mat=_compile.q2m(q), fovy=float(cam.fovy))
+                                                           mat=_compile.q2m(q), fovy=float(cam.fovy),
+                                                           height=int(cam.height), width=int(cam.width))
             if cam.name == "overhead_camera":
                 self.overhead_camera_height, self.overhead_camera_width = int(cam.height), int(cam.width)
         # ---- overhead camera images (mre_render): cube albedo = colour + noise (props.py:288-291),
@@ -233,6 +234,32 @@ class BatchedRearrangementEnv:
         return self._physics.render(cam["pos"], cam["mat"], cam["fovy"], self.overhead_camera_height,
                                     self.overhead_camera_width, rgb=rgb, depth=depth, seg=seg)
 
+    def add_camera(self, name: str, pos, quat, fovy: float, height: int, width: int) -> str:
+        """Register a further fixed camera, as the reference's ``add_camera`` does at build time (environment/cameras.py):
+        ``pos`` and ``quat`` (w, x, y, z) in the world, ``fovy`` degrees, ``height`` x ``width`` pixels.  Returns the key
+        ``"name/name"`` that ``render``, ``render_views``, ``heightmap`` and ``heightmap_views`` take.  The overhead set-up
+        can so carry the two obliques of config/arena/cameras/rearrangement.yaml beside its own camera."""
+        key = f"{name}/{name}"
+        if key in self._cameras:
+            raise ValueError(f"camera {key} exists")
+        if int(height) < 1 or int(width) < 1:
+            raise ValueError("height and width must be at least 1")
+        q = np.asarray(quat, np.float64).reshape(4)
+        self._cameras[key] = dict(pos=np.asarray(pos, np.float64).reshape(3), mat=_compile.q2m(q / np.linalg.norm(q)),
+                                  fovy=float(fovy), height=int(height), width=int(width))
+        return key
+
+    def render_views(self, cameras, rgb: bool = True, depth: bool = True, seg: bool = True):
+        """``render`` through each of the named ``cameras`` at that camera's own configured size: a list of
+        (rgb, depth, seg), one per camera in the order given.  (``render`` itself renders every camera at the overhead
+        camera's size.)"""
+        out = []
+        for name in cameras:
+            cam = self._cameras[name]
+            out.append(self._physics.render(cam["pos"], cam["mat"], cam["fovy"], cam["height"], cam["width"], rgb=rgb,
+                                            depth=depth, seg=seg))
+        return out
+
     def prop_bboxes(self, seg=None) -> np.ndarray:
         """PASCAL-VOC boxes [N, 4 cubes, (xmin, ymin, xmax, ymax)] of the VISIBLE pixels of every cube
         in the segmentation image (get_bbox, tasks/rearrangement.py:254-268); -1 where a cube is not
@@ -279,15 +306,39 @@ class BatchedRearrangementEnv:
                                     None if seg is None else torch.as_tensor(seg).to(depth.device), cam=cam12,
                                     bounds=HEIGHTMAP_BOUNDS if bounds is None else bounds, cell=cell)
 
+    def heightmap_views(self, cameras, frames=None, bounds=None, cell: float = 0.0025):
+        """``heightmap`` from several cameras at once, a ``perception.FusedHeightMap``: every cell takes the highest point
+        any of the named ``cameras`` saw in it (the first camera among equal heights), so that what the overhead camera
+        cannot see -- side faces, what the arm or a tall prop hides -- is filled from the others; ``view`` says which
+        camera a cell came from.  ``frames`` is a list of (rgb, depth, seg) per camera as ``render_views`` returns it
+        (rgb / seg may be None, in every camera or in none), or None for one ``render_views`` of the current state;
+        ``self`` is not touched when it is given.  One launch of ``mre_heightmap_views`` for CUDA frames."""
+        import torch
+        cameras = list(cameras)
+        if frames is None:
+            frames = self.render_views(cameras)
+        if len(frames) != len(cameras):
+            raise ValueError("one (rgb, depth, seg) per camera")
+        views = []
+        for name, (rgb, depth, seg) in zip(cameras, frames):
+            depth = torch.as_tensor(depth)
+            cam = self._cameras[name]
+            cam12 = perception.heightmap_camera(cam["pos"], cam["mat"], cam["fovy"], int(depth.shape[1]), int(depth.shape[2]))
+            views.append((depth, None if rgb is None else torch.as_tensor(rgb).to(depth.device),
+                          None if seg is None else torch.as_tensor(seg).to(depth.device), cam12))
+        return perception.heightmap_views(views, bounds=HEIGHTMAP_BOUNDS if bounds is None else bounds, cell=cell)
+
     def transporter_sample(self, seed: int, draw: int = 0, depth=None, rgb=None, seg=None, cell: float = 0.0025,
-                           n_rotations: int = 36, crop: int = 64, camera: str = OVERHEAD):
+                           n_rotations: int = 36, crop: int = 64, camera: str = OVERHEAD, maps=None):
         """One Transporter training sample per env on the device, a ``perception.TransporterSample``: the maps of
         ``heightmap(depth, rgb, seg, cell=cell)`` under a random rigid motion keyed by (``seed``, global env id, ``draw``),
         the pick and place cells of ``sort_colours(peek=True)`` moved with them, and ``n_rotations`` rotated crops of
         ``crop`` x ``crop`` cells around the moved pick cell.  An env with nothing left to move has its home pose as
         both cells; ``tries`` is -1 (and the maps unperturbed) where no motion kept both cells inside the map.  No state
-        of the env changes: no place draw is consumed."""
-        maps = self.heightmap(depth, rgb, seg, camera=camera, cell=cell)
+        of the env changes: no place draw is consumed.  ``maps`` (a ``HeightMap`` or ``FusedHeightMap`` at ``cell``, such
+        as ``heightmap_views`` returns) takes the place of the ``heightmap`` call."""
+        if maps is None:
+            maps = self.heightmap(depth, rgb, seg, camera=camera, cell=cell)
         _, pick, place = self.sort_colours(peek=True)
         return perception.transporter_sample(
             maps, perception.world_2_cell(pick[:, :3], HEIGHTMAP_BOUNDS, cell),
@@ -296,14 +347,15 @@ class BatchedRearrangementEnv:
 
     def transporter_batch(self, seed: int, draw: int = 0, depth=None, rgb=None, seg=None, cell: float = 0.0025,
                           n_rotations: int = 36, crop: int = 64, channels=perception.CHANNELS_RGBH,
-                          dtype=torch.bfloat16, camera: str = OVERHEAD):
+                          dtype=torch.bfloat16, camera: str = OVERHEAD, maps=None):
         """One Transporter training batch on the device as the tensors a network takes, a
         ``perception.TransporterBatch``: ``scene`` [N, C, rows, columns] and ``crops`` [N, n_rotations, C, crop, crop],
         channels-first, normalised by ``channels`` (a ``perception.Channels``) and in ``dtype``, with the
         moved pick and place cells and their flat indices.  The steps of ``transporter_sample`` up to the cells -- the same
         maps, the same motion for the same (``seed``, global env id, ``draw``) -- then ``perception.transporter_batch``.  No
-        state of the env changes."""
-        maps = self.heightmap(depth, rgb, seg, camera=camera, cell=cell)
+        state of the env changes.  ``maps``, when given, takes the place of the ``heightmap`` call."""
+        if maps is None:
+            maps = self.heightmap(depth, rgb, seg, camera=camera, cell=cell)
         _, pick, place = self.sort_colours(peek=True)
         return perception.transporter_batch(
             maps, perception.world_2_cell(pick[:, :3], HEIGHTMAP_BOUNDS, cell),
@@ -359,7 +411,7 @@ class BatchedRearrangementEnv:
         return perception.pick_loss(logits, torch.from_numpy(target).to(logits.device), weight)
 
     def transporter_act(self, attention, query, key, *, channels, dtype, n_rotations: int = 36, crop: int = 64,
-                        cell: float = 0.0025, depth=None, rgb=None, seg=None):
+                        cell: float = 0.0025, depth=None, rgb=None, seg=None, maps=None):
         """One decision of a Transporter policy for every env, from the observation to the two poses ``step()`` takes:
         (pick_pose [N, 7], place_pose [N, 7], ``PickDecision``, ``PlaceDecision``).  ``attention``, ``query`` and ``key`` are
         the caller's networks: ``attention(scene)`` -> pick logits [N, K, rows, columns], ``key(scene)`` -> [N, D, rows,
@@ -371,8 +423,10 @@ class BatchedRearrangementEnv:
         and ``query(crops)``; ``transporter_poses``.  Everything up to the poses stays on the device and nothing waits for
         it; the poses are numpy because ``step()`` takes numpy.  The pick quaternion is ``home_quat()``, the place
         quaternion that turned about world z by the place decision (``transporter_poses`` has the sign).  No state of the env
-        changes: the caller passes the poses to ``step()``."""
-        maps = self.heightmap(depth, rgb, seg, cell=cell)
+        changes: the caller passes the poses to ``step()``.  ``maps``, when given (``heightmap_views``' for a policy that
+        looks through several cameras), takes the place of the ``heightmap`` call."""
+        if maps is None:
+            maps = self.heightmap(depth, rgb, seg, cell=cell)
         height, colour = maps[0], maps[1]
         n, dev = int(height.shape[0]), height.device
         kw = dict(channels=channels, dtype=dtype)
