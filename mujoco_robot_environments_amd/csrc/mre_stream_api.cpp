@@ -210,12 +210,12 @@ static bool heightmap_inverse(const float* cam, float* inv) {
   return usable;
 }
 
-extern "C" int mre_heightmap(void* stream, const float* depth, const uint8_t* rgb, const uint8_t* seg, int n, int height,
-                             int width, const float* cam, const float* bounds, float inv_cell, float max_depth, int out_h,
-                             int out_w, float* hmap, uint8_t* cmap, uint8_t* smap, int32_t* src) {
-  const std::string w("mre_heightmap");
-  if (n < 0 || height < 1 || width < 1 || (long long)height * width >= (1ll << 31))
-    return fail(MRE_ERR_ARG, w + ": n >= 0, height and width >= 1, height * width < 2^31");
+// what mre_heightmap and mre_heightmap_views say of the maps, in the name `w` of the entry point: the checks from the
+// map's size to the pairing of the images (depth, rgb, seg: an image, or a list of them) with their outputs, and the
+// grid, its tiling and the outputs as the kernels read them (all of *m but m->g.cam)
+static int heightmap_maps(const std::string& w, const void* depth, const void* rgb, const void* seg, const float* cam,
+                          const float* bounds, float inv_cell, float max_depth, int out_h, int out_w, float* hmap,
+                          uint8_t* cmap, uint8_t* smap, int32_t* src, HmMaps* m) {
   if (out_h < 1 || out_w < 1 || out_h > (int)HM_MAX_OUT || out_w > (int)HM_MAX_OUT)
     return fail(MRE_ERR_ARG, w + ": 1 <= out_h, out_w <= 4096");
   if (!(inv_cell > 0.f) || !(max_depth > 0.f) || !std::isfinite(inv_cell) || !std::isfinite(max_depth))
@@ -227,23 +227,35 @@ extern "C" int mre_heightmap(void* stream, const float* depth, const uint8_t* rg
   if (!depth || !hmap) return fail(MRE_ERR_ARG, w + ": null depth or hmap");
   if ((rgb == nullptr) != (cmap == nullptr)) return fail(MRE_ERR_ARG, w + ": rgb and cmap go together");
   if ((seg == nullptr) != (smap == nullptr)) return fail(MRE_ERR_ARG, w + ": seg and smap go together");
+  for (int k = 0; k < 3; k++) { m->g.lo[k] = bounds[k]; m->g.hi[k] = bounds[3 + k]; }
+  m->g.inv_cell = inv_cell; m->g.max_depth = max_depth; m->g.out_w = (float)out_w; m->g.out_h = (float)out_h;
+  m->cell = (float)(1.0 / (double)inv_cell);
+  m->out_h = (uint32_t)out_h; m->out_w = (uint32_t)out_w;
+  m->tiles_x = (m->out_w + HM_TILE - 1) / HM_TILE; m->tiles_y = (m->out_h + HM_TILE - 1) / HM_TILE;
+  m->hmap = hmap; m->cmap = cmap; m->smap = smap; m->src = src;
+  return MRE_OK;
+}
+
+extern "C" int mre_heightmap(void* stream, const float* depth, const uint8_t* rgb, const uint8_t* seg, int n, int height,
+                             int width, const float* cam, const float* bounds, float inv_cell, float max_depth, int out_h,
+                             int out_w, float* hmap, uint8_t* cmap, uint8_t* smap, int32_t* src) {
+  const std::string w("mre_heightmap");
+  HeightmapArgs a;
+  memset(&a, 0, sizeof(a));
+  if (n < 0 || height < 1 || width < 1 || (long long)height * width >= (1ll << 31))
+    return fail(MRE_ERR_ARG, w + ": n >= 0, height and width >= 1, height * width < 2^31");
+  if (const int rc = heightmap_maps(w, depth, rgb, seg, cam, bounds, inv_cell, max_depth, out_h, out_w, hmap, cmap, smap,
+                                    src, &a.m))
+    return rc;
   if (((uintptr_t)depth & 3) || ((uintptr_t)hmap & 3) || ((uintptr_t)src & 3))
     return fail(MRE_ERR_ARG, w + ": depth, hmap and src must be 4-byte aligned");
   if (n == 0) return MRE_OK;
   if (!is_device_ptr(depth) || !is_device_ptr(hmap) || (rgb && (!is_device_ptr(rgb) || !is_device_ptr(cmap))) ||
       (seg && (!is_device_ptr(seg) || !is_device_ptr(smap))) || (src && !is_device_ptr(src)))
     return fail(MRE_ERR_ARG, w + ": depth, rgb, seg, hmap, cmap, smap and src must be device pointers");
-  HeightmapArgs a;
-  memset(&a, 0, sizeof(a));
   a.depth = depth; a.rgb = rgb; a.seg = seg; a.n = (uint32_t)n; a.h = (uint32_t)height; a.w = (uint32_t)width;
-  memcpy(a.g.cam, cam, sizeof(a.g.cam));
-  for (int k = 0; k < 3; k++) { a.g.lo[k] = bounds[k]; a.g.hi[k] = bounds[3 + k]; }
-  a.g.inv_cell = inv_cell; a.g.max_depth = max_depth; a.g.out_w = (float)out_w; a.g.out_h = (float)out_h;
-  a.cell = (float)(1.0 / (double)inv_cell);
+  memcpy(a.m.g.cam, cam, sizeof(a.m.g.cam));
   a.whole_image = heightmap_inverse(cam, a.inv) ? 0u : 1u;
-  a.out_h = (uint32_t)out_h; a.out_w = (uint32_t)out_w;
-  a.tiles_x = (a.out_w + HM_TILE - 1) / HM_TILE; a.tiles_y = (a.out_h + HM_TILE - 1) / HM_TILE;
-  a.hmap = hmap; a.cmap = cmap; a.smap = smap; a.src = src;
   mre_launch_heightmap(&a, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
@@ -256,22 +268,16 @@ extern "C" int mre_heightmap_views(void* stream, int views, const float* const* 
                                    int out_w, float* hmap, uint8_t* cmap, uint8_t* smap, int32_t* src, uint8_t* view) {
   static_assert(HM_MAX_VIEWS == MRE_HM_MAX_VIEWS, "the kernel's argument array holds the header's view count");
   const std::string w("mre_heightmap_views");
+  HeightmapViewsArgs a;
+  memset(&a, 0, sizeof(a));
   if (views < 1 || views > MRE_HM_MAX_VIEWS) return fail(MRE_ERR_ARG, w + ": 1 <= views <= 8");
   if (n < 0 || !height || !width) return fail(MRE_ERR_ARG, w + ": n >= 0, height and width non-null");
   for (int i = 0; i < views; i++)
     if (height[i] < 1 || width[i] < 1 || (long long)height[i] * width[i] >= (long long)HM_VIEW_PIXELS)
       return fail(MRE_ERR_ARG, w + ": height and width >= 1, height * width < 2^28 in every view");
-  if (out_h < 1 || out_w < 1 || out_h > (int)HM_MAX_OUT || out_w > (int)HM_MAX_OUT)
-    return fail(MRE_ERR_ARG, w + ": 1 <= out_h, out_w <= 4096");
-  if (!(inv_cell > 0.f) || !(max_depth > 0.f) || !std::isfinite(inv_cell) || !std::isfinite(max_depth))
-    return fail(MRE_ERR_ARG, w + ": inv_cell and max_depth must be positive and finite");
-  if (!cam || !bounds) return fail(MRE_ERR_ARG, w + ": null cam or bounds");
-  for (int k = 0; k < 3; k++)
-    if (!std::isfinite(bounds[k]) || !std::isfinite(bounds[3 + k]) || !(bounds[k] <= bounds[3 + k]))
-      return fail(MRE_ERR_ARG, w + ": bounds must be finite with lo <= hi");
-  if (!depth || !hmap) return fail(MRE_ERR_ARG, w + ": null depth or hmap");
-  if ((rgb == nullptr) != (cmap == nullptr)) return fail(MRE_ERR_ARG, w + ": rgb and cmap go together");
-  if ((seg == nullptr) != (smap == nullptr)) return fail(MRE_ERR_ARG, w + ": seg and smap go together");
+  if (const int rc = heightmap_maps(w, depth, rgb, seg, cam, bounds, inv_cell, max_depth, out_h, out_w, hmap, cmap, smap,
+                                    src, &a.m))
+    return rc;
   for (int i = 0; i < views; i++) {
     if (!depth[i] || (rgb && !rgb[i]) || (seg && !seg[i]))
       return fail(MRE_ERR_ARG, w + ": depth, and rgb and seg when given, must be non-null in every view");
@@ -285,8 +291,6 @@ extern "C" int mre_heightmap_views(void* stream, int views, const float* const* 
     on_device = is_device_ptr(depth[i]) && (!rgb || is_device_ptr(rgb[i])) && (!seg || is_device_ptr(seg[i]));
   if (!on_device)
     return fail(MRE_ERR_ARG, w + ": depth, rgb, seg, hmap, cmap, smap, src and view must be device pointers");
-  HeightmapViewsArgs a;
-  memset(&a, 0, sizeof(a));
   for (int i = 0; i < views; i++) {
     HeightmapView& v = a.v[i];
     v.depth = depth[i]; v.rgb = rgb ? rgb[i] : nullptr; v.seg = seg ? seg[i] : nullptr;
@@ -294,13 +298,7 @@ extern "C" int mre_heightmap_views(void* stream, int views, const float* const* 
     memcpy(v.cam, cam + 12 * i, sizeof(v.cam));
     v.whole_image = heightmap_inverse(v.cam, v.inv) ? 0u : 1u;
   }
-  a.views = (uint32_t)views; a.n = (uint32_t)n;
-  for (int k = 0; k < 3; k++) { a.g.lo[k] = bounds[k]; a.g.hi[k] = bounds[3 + k]; }
-  a.g.inv_cell = inv_cell; a.g.max_depth = max_depth; a.g.out_w = (float)out_w; a.g.out_h = (float)out_h;
-  a.cell = (float)(1.0 / (double)inv_cell);
-  a.out_h = (uint32_t)out_h; a.out_w = (uint32_t)out_w;
-  a.tiles_x = (a.out_w + HM_TILE - 1) / HM_TILE; a.tiles_y = (a.out_h + HM_TILE - 1) / HM_TILE;
-  a.hmap = hmap; a.cmap = cmap; a.smap = smap; a.src = src; a.view = view;
+  a.views = (uint32_t)views; a.n = (uint32_t)n; a.view = view;
   mre_launch_heightmap_views(&a, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
@@ -428,16 +426,35 @@ extern "C" int mre_correlate_workspace(int n, int rotations, int h, int w, size_
   return MRE_OK;
 }
 
+// the ranges mre_correlate shares with the five training entries below; an empty string when they hold
+static std::string correlate_ranges(int n, int rotations, int depth, int h, int w, int crop) {
+  if (n < 0) return ": n >= 0";
+  if (rotations < 1 || rotations > CR_MAX_ROT) return ": 1 <= rotations <= 64";
+  if (depth < 1 || depth > CR_MAX_DEPTH) return ": 1 <= depth <= 16";
+  if (crop < 2 || crop > CR_MAX_CROP || (crop & 1)) return ": crop must be even, 2 <= crop <= 64";
+  if (h < 1 || w < 1 || h > CR_MAX_DIM || w > CR_MAX_DIM) return ": 1 <= h, w <= 4096";
+  if (!correlate_shape_ok(n, rotations, h, w)) return ": rotations * h * w must be below 2^31";
+  return "";
+}
+
+// what every launch of the forward reads: the operands, the shape, the tiling
+static void correlate_forward_args(CorrelateArgs& a, const uint16_t* scene, const uint16_t* kern, int n, int rotations,
+                                   int depth, int h, int w, int crop, void* workspace) {
+  memset(&a, 0, sizeof(a));
+  a.scene = scene; a.kern = kern; a.workspace = workspace;
+  a.n = (uint32_t)n; a.rot = (uint32_t)rotations; a.depth = (uint32_t)depth; a.h = (uint32_t)h; a.w = (uint32_t)w;
+  a.crop = (uint32_t)crop; a.pivot = (uint32_t)crop / 2;
+  a.tiles_x = cr_tiles(a.w, CR_TILE_W); a.tiles_y = cr_tiles(a.h, CR_TILE_H);
+  // the wide access: a lane's 8 taps of a kernel row (every row then starts at a multiple of 8 elements)
+  a.vec_kern = (crop % 8 == 0 && !((uintptr_t)kern & 15)) ? 1u : 0u;
+}
+
 extern "C" int mre_correlate(void* stream, const uint16_t* scene, const uint16_t* kern, int n, int rotations, int depth,
                              int h, int w, int crop, int dtype, void* logits, int64_t* best_index, float* best_value,
                              void* workspace, size_t workspace_bytes) {
   const std::string wh("mre_correlate");
-  if (n < 0) return fail(MRE_ERR_ARG, wh + ": n >= 0");
-  if (rotations < 1 || rotations > CR_MAX_ROT) return fail(MRE_ERR_ARG, wh + ": 1 <= rotations <= 64");
-  if (depth < 1 || depth > CR_MAX_DEPTH) return fail(MRE_ERR_ARG, wh + ": 1 <= depth <= 16");
-  if (crop < 2 || crop > CR_MAX_CROP || (crop & 1)) return fail(MRE_ERR_ARG, wh + ": crop must be even, 2 <= crop <= 64");
-  if (h < 1 || w < 1 || h > CR_MAX_DIM || w > CR_MAX_DIM) return fail(MRE_ERR_ARG, wh + ": 1 <= h, w <= 4096");
-  if (!correlate_shape_ok(n, rotations, h, w)) return fail(MRE_ERR_ARG, wh + ": rotations * h * w must be below 2^31");
+  const std::string bad = correlate_ranges(n, rotations, depth, h, w, crop);
+  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
   if (!scene || !kern) return fail(MRE_ERR_ARG, wh + ": null scene or kern");
   if (((uintptr_t)scene & 1) || ((uintptr_t)kern & 1)) return fail(MRE_ERR_ARG, wh + ": scene and kern must be 2-byte aligned");
   if (dtype != MRE_F32 && dtype != MRE_BF16) return fail(MRE_ERR_ARG, wh + ": dtype must be MRE_F32 or MRE_BF16");
@@ -461,44 +478,16 @@ extern "C" int mre_correlate(void* stream, const uint16_t* scene, const uint16_t
       (best_index && (!is_device_ptr(best_index) || !is_device_ptr(best_value))))
     return fail(MRE_ERR_ARG, wh + ": scene, kern, the outputs and the workspace must be device pointers");
   CorrelateArgs a;
-  memset(&a, 0, sizeof(a));
-  a.scene = scene; a.kern = kern; a.logits = logits; a.best_index = best_index; a.best_value = best_value;
-  a.workspace = workspace;
-  a.n = (uint32_t)n; a.rot = (uint32_t)rotations; a.depth = (uint32_t)depth; a.h = (uint32_t)h; a.w = (uint32_t)w;
-  a.crop = (uint32_t)crop; a.pivot = (uint32_t)crop / 2;
-  a.tiles_x = cr_tiles(a.w, CR_TILE_W); a.tiles_y = cr_tiles(a.h, CR_TILE_H);
+  correlate_forward_args(a, scene, kern, n, rotations, depth, h, w, crop, workspace);
+  a.logits = logits; a.best_index = best_index; a.best_value = best_value;
   a.bf16 = dtype == MRE_BF16 ? 1u : 0u;
-  // the wide accesses: a lane's 8 taps of a kernel row (every row then starts at a multiple of 8 elements), and its 8
-  // logits of a pixel row
-  a.vec_kern = (crop % 8 == 0 && !((uintptr_t)kern & 15)) ? 1u : 0u;
-  a.vec_out = (logits && w % 8 == 0 && !((uintptr_t)logits & 15)) ? 1u : 0u;
+  a.vec_out = (logits && w % 8 == 0 && !((uintptr_t)logits & 15)) ? 1u : 0u;   // wide too: a lane's 8 logits of a pixel row
   mre_launch_correlate(&a, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
 }
 
 // ---- training the place head (csrc/mre_correlate_grad.hip): the loss, its gradient g, and the gradients of any g
-// the ranges the five entries share with mre_correlate; an empty string when they hold
-static std::string correlate_ranges(int n, int rotations, int depth, int h, int w, int crop) {
-  if (n < 0) return ": n >= 0";
-  if (rotations < 1 || rotations > CR_MAX_ROT) return ": 1 <= rotations <= 64";
-  if (depth < 1 || depth > CR_MAX_DEPTH) return ": 1 <= depth <= 16";
-  if (crop < 2 || crop > CR_MAX_CROP || (crop & 1)) return ": crop must be even, 2 <= crop <= 64";
-  if (h < 1 || w < 1 || h > CR_MAX_DIM || w > CR_MAX_DIM) return ": 1 <= h, w <= 4096";
-  if (!correlate_shape_ok(n, rotations, h, w)) return ": rotations * h * w must be below 2^31";
-  return "";
-}
-
-static void correlate_forward_args(CorrelateArgs& a, const uint16_t* scene, const uint16_t* kern, int n, int rotations,
-                                   int depth, int h, int w, int crop, void* workspace) {
-  memset(&a, 0, sizeof(a));
-  a.scene = scene; a.kern = kern; a.workspace = workspace;
-  a.n = (uint32_t)n; a.rot = (uint32_t)rotations; a.depth = (uint32_t)depth; a.h = (uint32_t)h; a.w = (uint32_t)w;
-  a.crop = (uint32_t)crop; a.pivot = (uint32_t)crop / 2;
-  a.tiles_x = cr_tiles(a.w, CR_TILE_W); a.tiles_y = cr_tiles(a.h, CR_TILE_H);
-  a.vec_kern = (crop % 8 == 0 && !((uintptr_t)kern & 15)) ? 1u : 0u;
-}
-
 extern "C" int mre_correlate_loss(void* stream, const uint16_t* scene, const uint16_t* kern, int n, int rotations, int depth,
                                   int h, int w, int crop, const int64_t* target, float* lse, float* target_logit,
                                   float* loss, void* workspace, size_t workspace_bytes) {

@@ -72,6 +72,19 @@ def _stream_on(dev):
         yield C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+def _ptr(t):
+    """A tensor, or None, as the C ABI takes a pointer."""
+    return None if t is None else t.data_ptr()
+
+
+def _workspace(entry: str, dev, *shape):
+    """The workspace of a call: a ``torch.empty`` of as many bytes on ``dev`` as the library's ``entry`` (an
+    ``mre_*_workspace``) asks for ``shape``, and that number."""
+    nbytes = C.c_size_t(0)
+    _lib.check(getattr(_lib.lib(), entry)(*shape, C.byref(nbytes)), entry)
+    return torch.empty((nbytes.value,), dtype=torch.uint8, device=dev), nbytes.value
+
+
 def _maps_on_device(height, *companions) -> bool:
     """What the warp kernels read in place: a contiguous CUDA float32 ``height`` with contiguous uint8 companions (or None)
     on its device."""
@@ -185,6 +198,36 @@ def _grid(bounds, cell):
     return b[0], b[1], np.float32(1.0 / float(cell))
 
 
+def _map_grid(bounds, cell, max_depth):
+    """The checks of a map every entry makes: ``_grid``, then ``max_depth`` and the map's size.  lo[3], hi[3], inv_cell,
+    rows, columns."""
+    lo, hi, inv_cell = _grid(bounds, cell)
+    out_h, out_w = heightmap_shape(bounds, cell)
+    if not (np.isfinite(max_depth) and max_depth > 0):
+        raise ValueError("max_depth must be positive and finite")
+    if out_h > MAX_MAP or out_w > MAX_MAP:
+        raise ValueError(f"a map has at most {MAX_MAP} rows and columns")
+    return lo, hi, inv_cell, out_h, out_w
+
+
+def _check_frames(depth, rgb, seg) -> None:
+    """The shapes of one view's frames.  (The pixel limit is each entry's own, in its own place among the checks.)"""
+    if depth.dim() != 3:
+        raise ValueError("depth must be [N, H, W]")
+    if rgb is not None and tuple(rgb.shape) != tuple(depth.shape) + (3,):
+        raise ValueError("rgb must be [N, H, W, 3]")
+    if seg is not None and tuple(seg.shape) != tuple(depth.shape):
+        raise ValueError("seg must have depth's shape")
+
+
+def _empty_maps(n, out_h, out_w, dev, colour: bool, seg: bool):
+    """The four outputs of a launch, uninitialised: height, colour or None, seg or None, src."""
+    return (torch.empty((n, out_h, out_w), dtype=torch.float32, device=dev),
+            torch.empty((n, out_h, out_w, 3), dtype=torch.uint8, device=dev) if colour else None,
+            torch.empty((n, out_h, out_w), dtype=torch.uint8, device=dev) if seg else None,
+            torch.empty((n, out_h, out_w), dtype=torch.int32, device=dev))
+
+
 def _cells(P0, P1, lo, inv_cell):
     """(column, row) of world x / y as float tensors: floor((P - lo) * inv_cell), every operation rounded on its own."""
     return torch.floor((P0 - float(lo[0])) * float(inv_cell)), torch.floor((P1 - float(lo[1])) * float(inv_cell))
@@ -250,19 +293,9 @@ def heightmap(depth: torch.Tensor, rgb: Optional[torch.Tensor] = None, seg: Opti
     statement.  The camera's "nothing hit" depth of 100 is cut by ``max_depth``.  CUDA float32 depth with uint8 rgb /
     seg is one launch of ``mre_heightmap`` (non-contiguous views are made contiguous first); anything else is
     computed by ``heightmap_reference`` with the same return values."""
-    if depth.dim() != 3:
-        raise ValueError("depth must be [N, H, W]")
-    if rgb is not None and tuple(rgb.shape) != tuple(depth.shape) + (3,):
-        raise ValueError("rgb must be [N, H, W, 3]")
-    if seg is not None and tuple(seg.shape) != tuple(depth.shape):
-        raise ValueError("seg must have depth's shape")
+    _check_frames(depth, rgb, seg)
     cam = np.ascontiguousarray(np.asarray(cam, np.float32).reshape(12))
-    lo, hi, inv_cell = _grid(bounds, cell)
-    out_h, out_w = heightmap_shape(bounds, cell)
-    if not (np.isfinite(max_depth) and max_depth > 0):
-        raise ValueError("max_depth must be positive and finite")
-    if out_h > MAX_MAP or out_w > MAX_MAP:
-        raise ValueError(f"a map has at most {MAX_MAP} rows and columns")
+    lo, hi, inv_cell, out_h, out_w = _map_grid(bounds, cell, max_depth)
     n, h, w = (int(x) for x in depth.shape)
     if h < 1 or w < 1 or h * w >= 2 ** 31:
         raise ValueError("images must have at least one pixel and fewer than 2^31")
@@ -274,17 +307,13 @@ def heightmap(depth: torch.Tensor, rgb: Optional[torch.Tensor] = None, seg: Opti
     depth = depth.contiguous()
     rgb = None if rgb is None else rgb.contiguous()
     seg = None if seg is None else seg.contiguous()
-    height = torch.empty((n, out_h, out_w), dtype=torch.float32, device=dev)
-    colour = None if rgb is None else torch.empty((n, out_h, out_w, 3), dtype=torch.uint8, device=dev)
-    smap = None if seg is None else torch.empty((n, out_h, out_w), dtype=torch.uint8, device=dev)
-    src = torch.empty((n, out_h, out_w), dtype=torch.int32, device=dev)
+    height, colour, smap, src = _empty_maps(n, out_h, out_w, dev, rgb is not None, seg is not None)
     if n:
-        ptr = lambda t: None if t is None else t.data_ptr()
         b = np.ascontiguousarray(np.concatenate([lo, hi]), np.float32)
         with _stream_on(dev) as stream:
-            _lib.check(_lib.lib().mre_heightmap(stream, depth.data_ptr(), ptr(rgb), ptr(seg), n, h, w, cam.ctypes.data,
+            _lib.check(_lib.lib().mre_heightmap(stream, depth.data_ptr(), _ptr(rgb), _ptr(seg), n, h, w, cam.ctypes.data,
                                                 b.ctypes.data, float(inv_cell), float(np.float32(max_depth)), out_h, out_w,
-                                                height.data_ptr(), ptr(colour), ptr(smap), src.data_ptr()), "mre_heightmap")
+                                                height.data_ptr(), _ptr(colour), _ptr(smap), src.data_ptr()), "mre_heightmap")
     return HeightMap(height, colour, smap, src)
 
 
@@ -302,23 +331,13 @@ def _views_args(views, bounds, cell, max_depth):
     views = [tuple(v) for v in views]
     if not 1 <= len(views) <= MAX_VIEWS:
         raise ValueError(f"1 to {MAX_VIEWS} views")
-    _grid(bounds, cell)
-    out_h, out_w = heightmap_shape(bounds, cell)
-    if not (np.isfinite(max_depth) and max_depth > 0):
-        raise ValueError("max_depth must be positive and finite")
-    if out_h > MAX_MAP or out_w > MAX_MAP:
-        raise ValueError(f"a map has at most {MAX_MAP} rows and columns")
+    _map_grid(bounds, cell, max_depth)
     res = []
     for v in views:
         if len(v) != 4:
             raise ValueError("a view is (depth, rgb, seg, cam)")
         depth, rgb, seg, cam = v
-        if depth.dim() != 3:
-            raise ValueError("depth must be [N, H, W]")
-        if rgb is not None and tuple(rgb.shape) != tuple(depth.shape) + (3,):
-            raise ValueError("rgb must be [N, H, W, 3]")
-        if seg is not None and tuple(seg.shape) != tuple(depth.shape):
-            raise ValueError("seg must have depth's shape")
+        _check_frames(depth, rgb, seg)
         h, w = int(depth.shape[1]), int(depth.shape[2])
         if h < 1 or w < 1 or h * w >= MAX_VIEW_PIXELS:
             raise ValueError("a view's images must have at least one pixel and fewer than 2^28")
@@ -373,17 +392,12 @@ def heightmap_views(views, *, bounds, cell: float, max_depth: float = 99.0) -> F
         return heightmap_views_reference(views, bounds=bounds, cell=cell, max_depth=max_depth)
     views = [(d.contiguous(), None if rgb is None else rgb.contiguous(), None if seg is None else seg.contiguous(), cam)
              for d, rgb, seg, cam in views]
-    lo, hi, inv_cell = _grid(bounds, cell)
-    out_h, out_w = heightmap_shape(bounds, cell)
+    lo, hi, inv_cell, out_h, out_w = _map_grid(bounds, cell, max_depth)
     n, nv = int(views[0][0].shape[0]), len(views)
     has_rgb, has_seg = views[0][1] is not None, views[0][2] is not None
-    height = torch.empty((n, out_h, out_w), dtype=torch.float32, device=dev)
-    colour = torch.empty((n, out_h, out_w, 3), dtype=torch.uint8, device=dev) if has_rgb else None
-    smap = torch.empty((n, out_h, out_w), dtype=torch.uint8, device=dev) if has_seg else None
-    src = torch.empty((n, out_h, out_w), dtype=torch.int32, device=dev)
+    height, colour, smap, src = _empty_maps(n, out_h, out_w, dev, has_rgb, has_seg)
     which = torch.empty((n, out_h, out_w), dtype=torch.uint8, device=dev)
     if n:
-        ptr = lambda t: None if t is None else t.data_ptr()
         pointers = lambda k: (C.c_void_p * nv)(*[v[k].data_ptr() for v in views])
         sizes = np.ascontiguousarray([[v[0].shape[1], v[0].shape[2]] for v in views], np.int32).T.copy()
         cams = np.ascontiguousarray(np.stack([v[3] for v in views]), np.float32)
@@ -392,7 +406,7 @@ def heightmap_views(views, *, bounds, cell: float, max_depth: float = 99.0) -> F
             _lib.check(_lib.lib().mre_heightmap_views(
                 stream, nv, pointers(0), pointers(1) if has_rgb else None, pointers(2) if has_seg else None, n,
                 sizes[0].ctypes.data, sizes[1].ctypes.data, cams.ctypes.data, b.ctypes.data, float(inv_cell),
-                float(np.float32(max_depth)), out_h, out_w, height.data_ptr(), ptr(colour), ptr(smap), src.data_ptr(),
+                float(np.float32(max_depth)), out_h, out_w, height.data_ptr(), _ptr(colour), _ptr(smap), src.data_ptr(),
                 which.data_ptr()), "mre_heightmap_views")
     return FusedHeightMap(height, colour, smap, src, which)
 
@@ -614,11 +628,10 @@ def warp_maps(height: torch.Tensor, colour: Optional[torch.Tensor] = None, seg: 
     out_s = None if seg is None else torch.empty((samples, out_h, out_w), dtype=torch.uint8, device=dev)
     source = torch.empty((samples, out_h, out_w), dtype=torch.int32, device=dev) if with_source else None
     if n and samples:
-        ptr = lambda t: None if t is None else t.data_ptr()
         with _stream_on(dev) as stream:
-            _lib.check(_lib.lib().mre_warp_maps(stream, height.data_ptr(), ptr(colour), ptr(seg), n, in_h, in_w, ptr(index),
-                                                mats.data_ptr(), samples, out_h, out_w, out_hz.data_ptr(), ptr(out_c),
-                                                ptr(out_s), ptr(source)), "mre_warp_maps")
+            _lib.check(_lib.lib().mre_warp_maps(stream, height.data_ptr(), _ptr(colour), _ptr(seg), n, in_h, in_w, _ptr(index),
+                                                mats.data_ptr(), samples, out_h, out_w, out_hz.data_ptr(), _ptr(out_c),
+                                                _ptr(out_s), _ptr(source)), "mre_warp_maps")
     return WarpedMaps(out_hz, out_c, out_s, source)
 
 
@@ -653,6 +666,15 @@ def sample_perturbation(seed: int, env_ids, draw: int, cells, shape, max_theta: 
     return Perturbation(F, affine_mats(invert_affine(F)), moved, tries)
 
 
+def _label_cells(pick_cells, place_cells, n: int) -> np.ndarray:
+    """The pick and place cells of ``n`` envs (tensors or arrays [N, 2]) as ``sample_perturbation`` takes them: int64 [N, 2, 2]."""
+    to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    cells = np.stack([to_np(pick_cells), to_np(place_cells)], axis=1).astype(np.int64)
+    if cells.shape != (n, 2, 2):
+        raise ValueError("pick_cells and place_cells must be [N, 2]")
+    return cells
+
+
 def transporter_sample(maps, pick_cells, place_cells, *, seed: int, env_ids, draw: int, n_rotations: int = 36,
                        crop: int = 64) -> TransporterSample:
     """One Transporter training sample per env from its ``maps`` (a ``HeightMap`` / ``WarpedMaps``, or (height, colour,
@@ -661,12 +683,9 @@ def transporter_sample(maps, pick_cells, place_cells, *, seed: int, env_ids, dra
     the moved pick cell, crop k turned by 2 pi k / n_rotations (``crop_matrices``): see ``TransporterSample``.  Two
     launches of ``mre_warp_maps`` for CUDA maps."""
     height, colour, seg = maps[0], maps[1], maps[2]
-    to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    cells = np.stack([to_np(pick_cells), to_np(place_cells)], axis=1).astype(np.int64)
     n = int(height.shape[0])
-    if cells.shape != (n, 2, 2):
-        raise ValueError("pick_cells and place_cells must be [N, 2]")
-    pert = sample_perturbation(seed, env_ids, draw, cells, tuple(height.shape[1:3]))
+    cells = _label_cells(pick_cells, place_cells, n)
+    pert =sample_perturbation(seed, env_ids, draw, cells, tuple(height.shape[1:3]))
     warped = warp_maps(height, colour, seg, mats=pert.M)
     mats, index = crop_matrices(pert.cells[:, 0], n_rotations, crop)
     flat = warp_maps(warped.height, warped.colour, warped.seg, mats=mats, index=index, out_shape=(crop, crop))
@@ -805,11 +824,8 @@ def transporter_batch(maps, pick_cells, place_cells, *, seed: int, env_ids, draw
     rotation bin a Transporter's place head is trained on is bin 0."""
     height, colour = maps[0], maps[1]
     channels = _input_args(colour, channels, dtype)
-    to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-    cells = np.stack([to_np(pick_cells), to_np(place_cells)], axis=1).astype(np.int64)
     n = int(height.shape[0])
-    if cells.shape != (n, 2, 2):
-        raise ValueError("pick_cells and place_cells must be [N, 2]")
+    cells = _label_cells(pick_cells, place_cells, n)
     cols = int(height.shape[2])
     pert = sample_perturbation(seed, env_ids, draw, cells, tuple(height.shape[1:3]))
     kw = dict(channels=channels, dtype=dtype)
@@ -850,6 +866,20 @@ def _correlate_args(scene, kernels, logits, best):
     return n, rot, depth, h, w, crop
 
 
+def _logits_f32(scene, kernels, n, rot, depth, h, w, crop):
+    """The conv2d line of ``correlate_reference``, differentiable: float32 [n, rot, h, w]"""
+    x = scene.to(torch.float32).reshape(1, n * depth, h, w)
+    k = kernels.to(torch.float32).reshape(n * rot, depth, crop, crop)
+    if n == 0:   # (conv2d takes no empty group; the sums keep the empty result in the graph)
+        return (x.sum() + k.sum()) * torch.zeros((0, rot, h, w), dtype=torch.float32, device=scene.device)
+    return torch.nn.functional.conv2d(x, k, padding=crop // 2, groups=n)[..., :h, :w].reshape(n, rot, h, w)
+
+
+def _on_device(*tensors) -> bool:
+    """What the place head's kernels read in place: contiguous CUDA bfloat16"""
+    return all(t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() for t in tensors)
+
+
 def correlate_reference(scene: torch.Tensor, kernels: torch.Tensor, *, logits=None, best: bool = True) -> Correlation:
     """The statement of ``correlate`` (include/mre.h, mre_correlate) in plain torch, on whatever device and for any
     strides and dtype: the grouped ``conv2d`` of the zero-padded scene with every env's own kernels in float32 from the
@@ -857,12 +887,7 @@ def correlate_reference(scene: torch.Tensor, kernels: torch.Tensor, *, logits=No
     counts as -inf).  The fallback of ``correlate``.  The order of its float32 additions is the library's, not the
     kernel's: integer-valued inputs (every partial sum below 2^24) make both exact."""
     n, rot, depth, h, w, crop = _correlate_args(scene, kernels, logits, best)
-    x = scene.to(torch.float32).reshape(1, n * depth, h, w)
-    k = kernels.to(torch.float32).reshape(n * rot, depth, crop, crop)
-    if n == 0:
-        out = torch.zeros((0, rot, h, w), dtype=torch.float32, device=scene.device)
-    else:
-        out = torch.nn.functional.conv2d(x, k, padding=crop // 2, groups=n)[..., :h, :w].reshape(n, rot, h, w)
+    out = _logits_f32(scene, kernels, n, rot, depth, h, w, crop)
     index = value = None
     if best:
         flat = out.reshape(n, rot * h * w)
@@ -884,24 +909,19 @@ def correlate(scene: torch.Tensor, kernels: torch.Tensor, *, logits=None, best: 
     accumulation) on torch's current stream with a ``torch.empty`` workspace, without a synchronise; anything else is
     computed by ``correlate_reference``.  No autograd: ``place_loss`` and ``correlate_backward`` are the training path."""
     n, rot, depth, h, w, crop = _correlate_args(scene, kernels, logits, best)
-    on_device = all(t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() for t in (scene, kernels))
-    if not on_device:
+    if not _on_device(scene, kernels):
         return correlate_reference(scene, kernels, logits=logits, best=best)
     dev = scene.device
     out = None if logits is None else torch.empty((n, rot, h, w), dtype=logits, device=dev)
     index = torch.empty((n,), dtype=torch.int64, device=dev) if best else None
     value = torch.empty((n,), dtype=torch.float32, device=dev) if best else None
     if n:
-        L = _lib.lib()
-        nbytes = C.c_size_t(0)
-        _lib.check(L.mre_correlate_workspace(n, rot, h, w, C.byref(nbytes)), "mre_correlate_workspace")
-        work = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+        work, nbytes = _workspace("mre_correlate_workspace", dev, n, rot, h, w)
         with _stream_on(dev) as stream:
-            _lib.check(L.mre_correlate(
+            _lib.check(_lib.lib().mre_correlate(
                 stream, scene.detach().data_ptr(), kernels.detach().data_ptr(), n, rot, depth, h, w, crop,
-                _DTYPES[logits if logits is not None else torch.float32], None if out is None else out.data_ptr(),
-                index.data_ptr() if best else None, value.data_ptr() if best else None, work.data_ptr(), nbytes.value),
-                "mre_correlate")
+                _DTYPES[logits if logits is not None else torch.float32], _ptr(out), _ptr(index), _ptr(value),
+                work.data_ptr(), nbytes), "mre_correlate")
     return Correlation(out, index, value)
 
 
@@ -961,15 +981,6 @@ def _as_weight(weight, n, dev):
     return w
 
 
-def _logits_f32(scene, kernels, n, rot, depth, h, w, crop):
-    """The conv2d line of ``correlate_reference``, differentiable: float32 [n, rot, h, w]"""
-    x = scene.to(torch.float32).reshape(1, n * depth, h, w)
-    k = kernels.to(torch.float32).reshape(n * rot, depth, crop, crop)
-    if n == 0:   # (conv2d takes no empty group; the sums keep the empty result in the graph)
-        return (x.sum() + k.sum()) * torch.zeros((0, rot, h, w), dtype=torch.float32, device=scene.device)
-    return torch.nn.functional.conv2d(x, k, padding=crop // 2, groups=n)[..., :h, :w].reshape(n, rot, h, w)
-
-
 def place_loss_reference(scene: torch.Tensor, kernels: torch.Tensor, target, weight=None) -> torch.Tensor:
     """The statement of ``place_loss`` (include/mre.h, mre_correlate_loss) in plain float32 torch, on any device and for
     any dtype and strides, differentiable by torch itself: weight * (logsumexp of the env's R * rows * columns logits
@@ -1005,10 +1016,6 @@ def correlate_backward_reference(scene: torch.Tensor, kernels: torch.Tensor, dlo
     return gs, gk
 
 
-def _on_device(*tensors) -> bool:
-    return all(t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() for t in tensors)
-
-
 def correlate_backward(scene: torch.Tensor, kernels: torch.Tensor, dlogits: torch.Tensor):
     """The gradients of sum(dlogits * logits) of ``correlate`` with respect to ``scene`` and ``kernels``, for any
     ``dlogits`` [N, R, rows, columns]: (grad_scene float32 [N, D, rows, columns], grad_kernels float32 [N, R, D, crop,
@@ -1028,13 +1035,10 @@ def correlate_backward(scene: torch.Tensor, kernels: torch.Tensor, dlogits: torc
 def _grad_call(name, g, other, out, shape):
     n, rot, depth, h, w, crop = shape
     if n:
-        L = _lib.lib()
-        nbytes = C.c_size_t(0)
-        _lib.check(L.mre_correlate_grad_workspace(n, rot, depth, h, w, crop, C.byref(nbytes)), "mre_correlate_grad_workspace")
-        work = torch.empty((nbytes.value,), dtype=torch.uint8, device=g.device)
+        work, nbytes = _workspace("mre_correlate_grad_workspace", g.device, n, rot, depth, h, w, crop)
         with _stream_on(g.device) as stream:
-            _lib.check(getattr(L, name)(stream, g.data_ptr(), other.data_ptr(), n, rot, depth, h, w, crop, out.data_ptr(),
-                                        work.data_ptr(), nbytes.value), name)
+            _lib.check(getattr(_lib.lib(), name)(stream, g.data_ptr(), other.data_ptr(), n, rot, depth, h, w, crop,
+                                                 out.data_ptr(), work.data_ptr(), nbytes), name)
     return out
 
 
@@ -1061,14 +1065,11 @@ def place_loss_forward(scene, kernels, target) -> PlaceLoss:
     dev = scene.device
     out = torch.empty((3, n), dtype=torch.float32, device=dev)
     if n:
-        L = _lib.lib()
-        nbytes = C.c_size_t(0)
-        _lib.check(L.mre_correlate_workspace(n, rot, h, w, C.byref(nbytes)), "mre_correlate_workspace")
-        work = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+        work, nbytes = _workspace("mre_correlate_workspace", dev, n, rot, h, w)
         with _stream_on(dev) as stream:
-            _lib.check(L.mre_correlate_loss(stream, scene.detach().data_ptr(), kernels.detach().data_ptr(), n, rot, depth, h, w,
-                                            crop, target.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                                            work.data_ptr(), nbytes.value), "mre_correlate_loss")
+            _lib.check(_lib.lib().mre_correlate_loss(
+                stream, scene.detach().data_ptr(), kernels.detach().data_ptr(), n, rot, depth, h, w, crop, target.data_ptr(),
+                out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), work.data_ptr(), nbytes), "mre_correlate_loss")
     return PlaceLoss(out[0], out[1], out[2])
 
 

@@ -296,15 +296,20 @@ class BatchedRearrangementEnv:
         position to its cell).  The frames are the caller's (``depth`` [N, H, W] with optional ``rgb`` / ``seg``, as
         ``render`` returns them, seen from ``camera``) or one ``render`` of the current state when ``depth`` is not
         given; ``self`` is not touched when it is."""
-        import torch
         if depth is None:
             rgb, depth, seg = self.render(camera=camera)
+        depth, rgb, seg, cam12 = self._view(camera, rgb, depth, seg)
+        return perception.heightmap(depth, rgb, seg, cam=cam12, bounds=HEIGHTMAP_BOUNDS if bounds is None else bounds,
+                                    cell=cell)
+
+    def _view(self, camera: str, rgb, depth, seg):
+        """The frames of ``camera`` as a view of ``perception.heightmap_views``: (depth, rgb, seg, cam12), tensors on the
+        device of ``depth``."""
         depth = torch.as_tensor(depth)
         cam = self._cameras[camera]
         cam12 = perception.heightmap_camera(cam["pos"], cam["mat"], cam["fovy"], int(depth.shape[1]), int(depth.shape[2]))
-        return perception.heightmap(depth, None if rgb is None else torch.as_tensor(rgb).to(depth.device),
-                                    None if seg is None else torch.as_tensor(seg).to(depth.device), cam=cam12,
-                                    bounds=HEIGHTMAP_BOUNDS if bounds is None else bounds, cell=cell)
+        return (depth, None if rgb is None else torch.as_tensor(rgb).to(depth.device),
+                None if seg is None else torch.as_tensor(seg).to(depth.device), cam12)
 
     def heightmap_views(self, cameras, frames=None, bounds=None, cell: float = 0.0025):
         """``heightmap`` from several cameras at once, a ``perception.FusedHeightMap``: every cell takes the highest point
@@ -313,19 +318,12 @@ class BatchedRearrangementEnv:
         camera a cell came from.  ``frames`` is a list of (rgb, depth, seg) per camera as ``render_views`` returns it
         (rgb / seg may be None, in every camera or in none), or None for one ``render_views`` of the current state;
         ``self`` is not touched when it is given.  One launch of ``mre_heightmap_views`` for CUDA frames."""
-        import torch
         cameras = list(cameras)
         if frames is None:
             frames = self.render_views(cameras)
         if len(frames) != len(cameras):
             raise ValueError("one (rgb, depth, seg) per camera")
-        views = []
-        for name, (rgb, depth, seg) in zip(cameras, frames):
-            depth = torch.as_tensor(depth)
-            cam = self._cameras[name]
-            cam12 = perception.heightmap_camera(cam["pos"], cam["mat"], cam["fovy"], int(depth.shape[1]), int(depth.shape[2]))
-            views.append((depth, None if rgb is None else torch.as_tensor(rgb).to(depth.device),
-                          None if seg is None else torch.as_tensor(seg).to(depth.device), cam12))
+        views = [self._view(name, rgb, depth, seg) for name, (rgb, depth, seg) in zip(cameras, frames)]
         return perception.heightmap_views(views, bounds=HEIGHTMAP_BOUNDS if bounds is None else bounds, cell=cell)
 
     def transporter_sample(self, seed: int, draw: int = 0, depth=None, rgb=None, seg=None, cell: float = 0.0025,
@@ -337,13 +335,17 @@ class BatchedRearrangementEnv:
         both cells; ``tries`` is -1 (and the maps unperturbed) where no motion kept both cells inside the map.  No state
         of the env changes: no place draw is consumed.  ``maps`` (a ``HeightMap`` or ``FusedHeightMap`` at ``cell``, such
         as ``heightmap_views`` returns) takes the place of the ``heightmap`` call."""
+        return perception.transporter_sample(*self._labelled_maps(maps, depth, rgb, seg, camera, cell), seed=seed,
+                                             env_ids=self.env_ids, draw=draw, n_rotations=n_rotations, crop=crop)
+
+    def _labelled_maps(self, maps, depth, rgb, seg, camera, cell):
+        """What the ``transporter_*`` producers start from: (maps, pick cells, place cells) -- ``maps`` or, without them,
+        ``heightmap(depth, rgb, seg, camera, cell)``, and the cells of ``sort_colours(peek=True)`` in them."""
         if maps is None:
             maps = self.heightmap(depth, rgb, seg, camera=camera, cell=cell)
         _, pick, place = self.sort_colours(peek=True)
-        return perception.transporter_sample(
-            maps, perception.world_2_cell(pick[:, :3], HEIGHTMAP_BOUNDS, cell),
-            perception.world_2_cell(place[:, :3], HEIGHTMAP_BOUNDS, cell), seed=seed, env_ids=self.env_ids, draw=draw,
-            n_rotations=n_rotations, crop=crop)
+        return (maps, perception.world_2_cell(pick[:, :3], HEIGHTMAP_BOUNDS, cell),
+                perception.world_2_cell(place[:, :3], HEIGHTMAP_BOUNDS, cell))
 
     def transporter_batch(self, seed: int, draw: int = 0, depth=None, rgb=None, seg=None, cell: float = 0.0025,
                           n_rotations: int = 36, crop: int = 64, channels=perception.CHANNELS_RGBH,
@@ -354,13 +356,9 @@ class BatchedRearrangementEnv:
         moved pick and place cells and their flat indices.  The steps of ``transporter_sample`` up to the cells -- the same
         maps, the same motion for the same (``seed``, global env id, ``draw``) -- then ``perception.transporter_batch``.  No
         state of the env changes.  ``maps``, when given, takes the place of the ``heightmap`` call."""
-        if maps is None:
-            maps = self.heightmap(depth, rgb, seg, camera=camera, cell=cell)
-        _, pick, place = self.sort_colours(peek=True)
-        return perception.transporter_batch(
-            maps, perception.world_2_cell(pick[:, :3], HEIGHTMAP_BOUNDS, cell),
-            perception.world_2_cell(place[:, :3], HEIGHTMAP_BOUNDS, cell), seed=seed, env_ids=self.env_ids, draw=draw,
-            n_rotations=n_rotations, crop=crop, channels=channels, dtype=dtype)
+        return perception.transporter_batch(*self._labelled_maps(maps, depth, rgb, seg, camera, cell), seed=seed,
+                                            env_ids=self.env_ids, draw=draw, n_rotations=n_rotations, crop=crop,
+                                            channels=channels, dtype=dtype)
 
     def transporter_place(self, scene_features, crop_features, cell: float = 0.0025):
         """The place decision of a Transporter's place head for every env, on the device: ``scene_features`` [N, D, rows,

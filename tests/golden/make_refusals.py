@@ -1,0 +1,24 @@
+"""Generates tests/golden/refusals.json: the return code and the mre_last_error() text of every bad call of
+tests/refusal_cases.py, the record tests/test_refusals.py holds the library to.
+
+The record states what the checks answered BEFORE a change to them, so it is made with the library of the commit the
+change starts from, never with the changed one: build that commit's sources
+(lib.compile_and_link(so, objdir, csrc=<its csrc>)) and name the result in MRE_LIB.  Run from the repo root, no GPU needed:
+    MRE_LIB=/path/to/libmre_of_the_parent.so python tests/golden/make_refusals.py
+"""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+from mujoco_robot_environments_amd import lib  # noqa: E402
+from tests import refusal_cases  # noqa: E402
+
+if __name__ == "__main__":
+    out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "refusals.json")
+    rows = refusal_cases.answers(lib.lib())
+    with open(out, "w") as fh:
+        fh.write("[\n" + ",\n".join(json.dumps(r) for r in rows) + "\n]\n")
+    print(f"{out}: {len(rows)} calls, {sum(1 for r in rows if r[1])} refused")
