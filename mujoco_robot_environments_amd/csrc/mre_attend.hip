@@ -20,64 +20,52 @@
 //
 // S depends on the number of cells alone, every workgroup serves one env and a lane's cells do not depend on an address: an
 // env's bytes depend neither on n nor on its place in the batch nor on its alignment.  No atomics; every output element and
-// every slot is written exactly once.  `better` is mre_correlate's total order (greater value, then lower index).
+// every slot is written exactly once.  `better` is the total order of csrc/mre_head.h (greater value, then lower index).
 //
 // -inf is a valid logit (a masked cell).  The running max of a lane that has met nothing finite is -inf, and -inf - -inf
 // would be a NaN: every rescale subtracts `ms`, the max with -inf replaced by 0, so that an all -inf prefix contributes
 // exp2(-inf) = 0 and nothing else.
 #include "mre_attend.h"
-
-#include "mre_warp_input_point.h"
+#include "mre_head.h"
 
 namespace {
 
-constexpr float L2E = 1.44269504088896340736f;
-constexpr int NO_INDEX = 0x7FFFFFFF;
-constexpr uint32_t MAX_GRID_Y = 65535, MAX_GRID = 1u << 20;
 constexpr uint32_t NINF_F32 = 0xFF800000u, NINF_BF16 = 0xFF80u;
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float as_f32(uint32_t u) { return __builtin_bit_cast(float, u); }
 __device__ __forceinline__ uint32_t as_u32(float f) { return __builtin_bit_cast(uint32_t, f); }
 
-struct Acc {   // what a lane, a wave, a workgroup and a slot hold: ((-inf, 0), (-inf, NO_INDEX)) is the empty set
-  float m, s, bv;
-  int bi;
+struct Acc {   // what a lane, a wave, a workgroup and a 16-byte slot hold: ((-inf, 0), (-inf, NO_INDEX)) is the empty set
+  Soft s;
+  Best b;
 };
+constexpr Acc ACC_EMPTY = {{-__builtin_inff(), 0.f}, {-__builtin_inff(), NO_INDEX}};
 
-__device__ __forceinline__ bool better(float v2, int i2, float v1, int i1) { return v2 > v1 || (v2 == v1 && i2 < i1); }
-
-// BEST / SOFT: which half is live; the other keeps the empty set and costs nothing
+// BEST / SOFT: which half is live; the other keeps the empty set and costs nothing.
+// The SOFT half is NOT the place head's soft_merge (csrc/mre_correlate_grad.hip): the sum is ONE expression, a multiply and a
+// fused multiply-add under -ffp-contract=on, where soft_merge rounds both products; and a -inf max is replaced by 0, not
+// returned early.  One shared merge would change the last bit of one head's lse.
 template <bool BEST, bool SOFT>
 __device__ __forceinline__ Acc acc_merge(Acc a, Acc b) {
   Acc r = a;
   if (SOFT) {
-    const float m = fmaxf(a.m, b.m);
+    const float m = fmaxf(a.s.m, b.s.m);
     const float ms = m == -__builtin_inff() ? 0.f : m;
-    r.m = m;
-    r.s = a.s * ex2((a.m - ms) * L2E) + b.s * ex2((b.m - ms) * L2E);
+    r.s.m = m;
+    r.s.s = a.s.s * ex2((a.s.m - ms) * L2E) + b.s.s * ex2((b.s.m - ms) * L2E);
   }
-  if (BEST) {
-    const bool take = better(b.bv, b.bi, a.bv, a.bi);
-    r.bv = take ? b.bv : a.bv;
-    r.bi = take ? b.bi : a.bi;
-  }
+  if (BEST) r.b = best_merge(a.b, b.b);
   return r;
 }
+
+template <bool XOR, typename T>
+__device__ __forceinline__ T from_lane(T v, int from) { return XOR ? __shfl_xor(v, from, 64) : __shfl(v, from, 64); }
 
 template <bool BEST, bool SOFT, bool XOR>
 __device__ __forceinline__ Acc acc_lane(Acc v, int from) {
   Acc o = v;
-  if (SOFT) {
-    o.m = XOR ? __shfl_xor(v.m, from, 64) : __shfl(v.m, from, 64);
-    o.s = XOR ? __shfl_xor(v.s, from, 64) : __shfl(v.s, from, 64);
-  }
-  if (BEST) {
-    o.bv = XOR ? __shfl_xor(v.bv, from, 64) : __shfl(v.bv, from, 64);
-    o.bi = XOR ? __shfl_xor(v.bi, from, 64) : __shfl(v.bi, from, 64);
-  }
+  if (SOFT) o.s = Soft{from_lane<XOR>(v.s.m, from), from_lane<XOR>(v.s.s, from)};
+  if (BEST) o.b = Best{from_lane<XOR>(v.b.v, from), from_lane<XOR>(v.b.i, from)};
   return o;
 }
 
@@ -125,42 +113,41 @@ __device__ __forceinline__ uint32_t at_cell(uint32_t c, uint32_t j, uint32_t t) 
   return c * AT_CHUNK + (j * AT_NT + t) * (BF16 ? 8 : 4);
 }
 
+// online, per vector (the place head makes two passes over its registers)
 template <int VEC, bool BEST, bool SOFT>
 __device__ __forceinline__ void at_update(Acc& a, const float (&v)[VEC], uint32_t i0) {
   float vm = v[0];
 #pragma unroll
   for (int p = 1; p < VEC; p++) vm = fmaxf(vm, v[p]);
-  if (BEST && vm > a.bv) {   // rare after a lane's first vectors; the cells in rising order, so strictly greater is enough
+  if (BEST && vm > a.b.v) {   // rare after a lane's first vectors; the cells in rising order, so strictly greater is enough
 #pragma unroll
     for (int p = 0; p < VEC; p++)
-      if (v[p] > a.bv) { a.bv = v[p]; a.bi = (int)(i0 + p); }
+      if (v[p] > a.b.v) { a.b.v = v[p]; a.b.i = (int)(i0 + p); }
   }
   if (SOFT) {
-    const float m = fmaxf(a.m, vm);
+    const float m = fmaxf(a.s.m, vm);
     const float ms = m == -__builtin_inff() ? 0.f : m;
-    float s = a.s * ex2((a.m - ms) * L2E);
+    float s = a.s.s * ex2((a.s.m - ms) * L2E);
 #pragma unroll
     for (int p = 0; p < VEC; p++) s += ex2((v[p] - ms) * L2E);
-    a.m = m;
-    a.s = s;
+    a.s.m = m;
+    a.s.s = s;
   }
 }
 
 constexpr uint32_t AT_AHEAD = 3;   // chunks whose loads a lane issues before it uses the first: a whole split of the workload
 
-__device__ __forceinline__ uint32_t at_env(void) { return blockIdx.z * gridDim.y + blockIdx.y; }
-
 template <bool BF16, bool BEST, bool SOFT>
 __global__ void __launch_bounds__(AT_NT) k_attend(AttendArgs a) {
   constexpr int VEC = BF16 ? 8 : 4, VPL = AT_LANE / VEC;
   __shared__ Acc red[AT_NT / 64];
-  const uint32_t t = threadIdx.x, e = at_env(), sp = blockIdx.x;
+  const uint32_t t = threadIdx.x, e = env_index(), sp = blockIdx.x;
   if (e >= a.n) return;
   const uint32_t cells = a.cells, chunks = at_chunks(cells), S = at_split(cells);
   const uint32_t c0 = at_first(chunks, S, sp), c1 = at_first(chunks, S, sp + 1);
   const char* base = reinterpret_cast<const char*>(a.logits) + (size_t)e * cells * (BF16 ? 2 : 4);
   const bool aligned = ((uintptr_t)base & 15) == 0;
-  Acc acc = {-__builtin_inff(), 0.f, -__builtin_inff(), NO_INDEX};
+  Acc acc = ACC_EMPTY;
   for (uint32_t c = c0; c < c1; c += AT_AHEAD) {
     u32x4 raw[AT_AHEAD][VPL];
 #pragma unroll
@@ -201,28 +188,28 @@ __device__ __forceinline__ float at_elem(const void* logits, bool bf16, size_t i
 template <bool BEST, bool SOFT>
 __global__ void __launch_bounds__(64) k_attend_merge(AttendArgs a) {
   const uint32_t S = at_split(a.cells);
-  const Acc empty = {-__builtin_inff(), 0.f, -__builtin_inff(), NO_INDEX};
   for (uint32_t e = blockIdx.x; e < a.n; e += gridDim.x) {
     const Acc* slots = reinterpret_cast<const Acc*>(a.workspace) + (size_t)e * S;
-    const Acc mine = threadIdx.x < S ? slots[threadIdx.x] : empty;
-    Acc b = empty;
+    const Acc mine = threadIdx.x < S ? slots[threadIdx.x] : ACC_EMPTY;
+    Acc b = ACC_EMPTY;
+    // in the order 0 .. S - 1, each slot broadcast from its lane (the place head takes strided partials, then a butterfly)
     for (uint32_t k = 0; k < S; k++) b = acc_merge<BEST, SOFT>(b, acc_lane<BEST, SOFT, false>(mine, (int)k));
     if (threadIdx.x == 0) {
       const size_t first = (size_t)e * a.cells;
       if (BEST) {
-        // no cell was better than the start only if none is above -inf: the first cell stands, as the statement has it
-        const bool none = b.bi == NO_INDEX;
-        a.best_index[e] = none ? 0 : (int64_t)b.bi;
-        a.best_value[e] = none ? at_elem(a.logits, a.bf16, first) : b.bv;
+        // no cell was better than the start only if none is above -inf: the first cell stands, as the statement has it, with
+        // its own logit as the value (the place head returns NaN there)
+        const bool none = b.b.i == NO_INDEX;
+        a.best_index[e] = none ? 0 : (int64_t)b.b.i;
+        a.best_value[e] = none ? at_elem(a.logits, a.bf16, first) : b.b.v;
       }
       if (SOFT) {
         const int64_t tgt = a.target[e];
-        const bool inside = tgt >= 0 && tgt < (int64_t)a.cells;
-        const float lse = b.m + logf(b.s);
-        const float tl = inside ? at_elem(a.logits, a.bf16, first + (size_t)(inside ? tgt : 0)) : __builtin_nanf("");
-        a.lse[e] = lse;
-        a.target_logit[e] = tl;
-        a.loss[e] = lse - tl;
+        const size_t at = soft_inside(tgt, a.cells) ? (size_t)tgt : 0;   // (a target outside reads the first cell, on purpose and unused)
+        const SoftEnd f = soft_finish(b.s, tgt, a.cells, at_elem(a.logits, a.bf16, first + at));
+        a.lse[e] = f.lse;
+        a.target_logit[e] = f.target_logit;
+        a.loss[e] = f.loss;
       }
     }
   }
@@ -231,7 +218,7 @@ __global__ void __launch_bounds__(64) k_attend_merge(AttendArgs a) {
 template <bool BF16>
 __global__ void __launch_bounds__(AT_NT) k_attend_dlogits(AttendGradArgs a) {
   constexpr int VEC = BF16 ? 8 : 4, VPL = AT_LANE / VEC, ESIZE = BF16 ? 2 : 4;
-  const uint32_t t = threadIdx.x, e = at_env(), sp = blockIdx.x;
+  const uint32_t t = threadIdx.x, e = env_index(), sp = blockIdx.x;
   if (e >= a.n) return;
   const uint32_t cells = a.cells, chunks = at_chunks(cells), S = at_split(cells);
   const uint32_t c0 = at_first(chunks, S, sp), c1 = at_first(chunks, S, sp + 1);
@@ -261,7 +248,7 @@ __global__ void __launch_bounds__(AT_NT) k_attend_dlogits(AttendGradArgs a) {
         at_values<BF16>(v, raw[k][j]);
 #pragma unroll
         for (int p = 0; p < VEC; p++) {
-          const float pr = dead ? 0.f : ex2((v[p] - lse) * L2E);
+          const float pr = dead ? 0.f : ex2((v[p] - lse) * L2E);   // (`dead` is this head's alone: -inf is no sum of the place head)
           const float hit = !dead && i0 + p == hit_cell ? 1.f : 0.f;
           v[p] = wgt * (pr - hit);
         }
@@ -288,11 +275,6 @@ __global__ void __launch_bounds__(AT_NT) k_attend_dlogits(AttendGradArgs a) {
   }
 }
 
-dim3 env_grid(uint32_t x, uint32_t n) {
-  const uint32_t gy = n < MAX_GRID_Y ? n : MAX_GRID_Y;
-  return dim3(x, gy, (n + gy - 1) / gy);
-}
-
 }  // namespace
 
 extern "C" void mre_launch_attend(const AttendArgs* a, hipStream_t stream) {
@@ -303,7 +285,7 @@ extern "C" void mre_launch_attend(const AttendArgs* a, hipStream_t stream) {
   const int which = !a->target ? 0 : (!a->best_index ? 1 : 2);
   hipLaunchKernelGGL(table[a->bf16 ? 1 : 0][which], env_grid(at_split(a->cells), a->n), dim3(AT_NT), 0, stream, *a);
   static const Kernel merge[3] = {k_attend_merge<true, false>, k_attend_merge<false, true>, k_attend_merge<true, true>};
-  hipLaunchKernelGGL(merge[which], dim3(a->n < MAX_GRID ? a->n : MAX_GRID), dim3(64), 0, stream, *a);
+  hipLaunchKernelGGL(merge[which], wave_per_env_grid(a->n), dim3(64), 0, stream, *a);
 }
 
 extern "C" void mre_launch_attend_dlogits(const AttendGradArgs* a, hipStream_t stream) {

@@ -28,46 +28,24 @@
 //                      and the workgroup's best (value, flat index) to its own slot of the workspace.
 //   k_correlate_best   one wave per env reduces that env's slots.
 //
-// `Better` is a total order on (value, index) -- greater value, then lower index -- so the reductions give the first
-// occurrence of the maximum in whatever order they combine; a NaN is never better than anything.  No atomics; every
-// output element and every slot is written exactly once.  Offsets into logits and kern are formed in 64 bits.
+// The reductions go by `better` (csrc/mre_head.h).  No atomics; every output element and every slot is written exactly once.
+// Offsets into logits and kern are formed in 64 bits.
 #include "mre_correlate_core.h"
 
-#include "mre_warp_input_point.h"
-
 namespace {
-
-constexpr int NO_INDEX = 0x7FFFFFFF;
-
-struct Best {
-  float v;
-  int i;
-};
-
-__device__ __forceinline__ bool better(float v2, int i2, float v1, int i1) { return v2 > v1 || (v2 == v1 && i2 < i1); }
-
-__device__ __forceinline__ Best wave_best(Best b) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const float v = __shfl_xor(b.v, m, 64);
-    const int i = __shfl_xor(b.i, m, 64);
-    if (better(v, i, b.v, b.i)) { b.v = v; b.i = i; }
-  }
-  return b;
-}
 
 template <int RT, bool VK>
 __global__ void __launch_bounds__(NT, 2) k_correlate(CorrelateArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t patch[PROWS * PITCH];
   __shared__ Best red[NT / 64];
-  const uint32_t t = threadIdx.x, lane = t & 63;
-  const int wv = __builtin_amdgcn_readfirstlane((int)(t >> 6));   // the same in every lane of a wave: scalar
-  const uint32_t lr = lane & 15, g = lane >> 4;
+  const CrLane l = cr_lane();
+  const uint32_t t = l.t, lane = l.lane, lr = l.lr, g = l.g;
+  const int wv = l.wv;
   const int R = (int)a.rot, H = (int)a.h, W = (int)a.w;
   const uint32_t tiles = a.tiles_x * a.tiles_y;
   // one workgroup per (tile, env): blockIdx.x the tile, y and z the env (no loop over items: what it would keep alive
   // across the body does not fit the scalar registers)
-  const uint32_t e = blockIdx.z * gridDim.y + blockIdx.y, tile = blockIdx.x;
+  const uint32_t e = env_index(), tile = blockIdx.x;
   if (e >= a.n) return;
   {
     const int y0 = (int)(tile / a.tiles_x) * CR_TILE_H, x0 = (int)(tile % a.tiles_x) * CR_TILE_W;
@@ -133,18 +111,17 @@ __global__ void __launch_bounds__(NT, 2) k_correlate(CorrelateArgs a) {
   }
 }
 
+// the slots of an env in strided partials per lane, then the butterfly
 __global__ void __launch_bounds__(64) k_correlate_best(CorrelateArgs a) {
   const uint32_t tiles = a.tiles_x * a.tiles_y;
   for (uint32_t e = blockIdx.x; e < a.n; e += gridDim.x) {
     const Best* slots = reinterpret_cast<const Best*>(a.workspace) + (size_t)e * tiles;
     Best b = {-__builtin_inff(), NO_INDEX};
-    for (uint32_t s = threadIdx.x; s < tiles; s += 64) {
-      const Best o = slots[s];
-      if (better(o.v, o.i, b.v, b.i)) b = o;
-    }
+    for (uint32_t s = threadIdx.x; s < tiles; s += 64) b = best_merge(b, slots[s]);
     b = wave_best(b);
     if (threadIdx.x == 0) {
-      // no cell was better than the start only if every sum is a NaN: the first cell stands, as the statement has it
+      // no cell was better than the start only if every sum is a NaN: the first cell stands, as the statement has it, with
+      // NaN as its value (the pick head returns the first logit there: -inf is a valid logit for it)
       const bool none = b.i == NO_INDEX;
       a.best_index[e] = none ? 0 : (int64_t)b.i;
       a.best_value[e] = none ? __builtin_nanf("") : b.v;
@@ -155,13 +132,8 @@ __global__ void __launch_bounds__(64) k_correlate_best(CorrelateArgs a) {
 }  // namespace
 
 extern "C" void mre_launch_correlate(const CorrelateArgs* a, hipStream_t stream) {
-  const uint32_t gy = a->n < MAX_GRID_Y ? a->n : MAX_GRID_Y;
-  const dim3 grid(a->tiles_x * a->tiles_y, gy, (a->n + gy - 1) / gy);   // at most 32 768 tiles; n < 2^31 envs
-  typedef void (*Kernel)(CorrelateArgs);
-  static const Kernel table[8] = {k_correlate<1, false>, k_correlate<1, true>, k_correlate<2, false>, k_correlate<2, true>,
-                                  k_correlate<3, false>, k_correlate<3, true>, k_correlate<4, false>, k_correlate<4, true>};
-  const int rt = ((int)a->rot + 15) / 16;
-  hipLaunchKernelGGL(table[2 * (rt - 1) + (a->vec_kern ? 1 : 0)], grid, dim3(NT), 0, stream, *a);
-  if (a->best_index)
-    hipLaunchKernelGGL(k_correlate_best, dim3(a->n < MAX_GRID ? a->n : MAX_GRID), dim3(64), 0, stream, *a);
+#define CR_FORWARD(RT, VK) k_correlate<RT, VK>
+  static void (*const table[8])(CorrelateArgs) = CR_TABLE(CR_FORWARD);
+  hipLaunchKernelGGL(table[cr_which(a->rot, a->vec_kern)], env_grid(a->tiles_x * a->tiles_y, a->n), dim3(NT), 0, stream, *a);   // at most 32 768 tiles
+  if (a->best_index) hipLaunchKernelGGL(k_correlate_best, wave_per_env_grid(a->n), dim3(64), 0, stream, *a);
 }

@@ -11,6 +11,7 @@
 #ifndef MRE_CORRELATE_CORE_H
 #define MRE_CORRELATE_CORE_H
 #include "mre_correlate.h"
+#include "mre_head.h"
 
 namespace {
 
@@ -18,10 +19,8 @@ constexpr int NT = 256;
 constexpr int PITCH = 112;                              // bf16 elements of a patch row: 14 slots of 16 bytes
 constexpr int PCOLS = 96;                               // staged columns: 24 (wave) + 32 (j0) + 24 (g) + 15 (window) + 1
 constexpr int PROWS = CR_TILE_H + CR_MAX_CROP - 1;      // 79
-constexpr uint32_t MAX_GRID_Y = 65535, MAX_GRID = 1u << 20;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ bf16x8 frag(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
@@ -151,6 +150,23 @@ __device__ __forceinline__ void cr_forward(f32x4 (&acc)[RT][8], uint16_t* patch,
     cr_slice<RT, VK, true>(acc, patch, scene_e + (size_t)d * H * W, H, W, y0 - half, x0 - half, kern_e + (size_t)d * c * c,
                            rot_off, c, c, c, i_lo, i_hi, t, wv, lr, g);
 }
+
+// Where a lane stands in its workgroup of 4 waves: lane (lr, g) of wave wv holds rows 16 rt + 4 g + q of the A operand at
+// output row lr and the wave's 8 output columns.
+struct CrLane {
+  uint32_t t, lane, lr, g;
+  int wv;   // the same in every lane of a wave: scalar
+};
+
+__device__ __forceinline__ CrLane cr_lane(void) {
+  const uint32_t t = threadIdx.x, lane = t & 63, g = lane >> 4, lr = lane & 15;
+  return CrLane{t, lane, lr, g, __builtin_amdgcn_readfirstlane((int)(t >> 6))};
+}
+
+// The eight instantiations K(RT, VK) of a kernel template (K a macro that names one, as CR_SOFT of csrc/mre_correlate_grad.hip
+// does), and which of them serves `rot` rows of A (RT tiles of 16) with the wide access or without
+#define CR_TABLE(K) {K(1, false), K(1, true), K(2, false), K(2, true), K(3, false), K(3, true), K(4, false), K(4, true)}
+inline int cr_which(uint32_t rot, uint32_t vk) { return 2 * (((int)rot + 15) / 16 - 1) + (vk ? 1 : 0); }
 
 }  // namespace
 #endif

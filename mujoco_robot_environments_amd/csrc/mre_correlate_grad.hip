@@ -29,18 +29,12 @@
 
 #include "mre_correlate_core.h"
 
-#include "mre_warp_input_point.h"
-
 namespace {
 
-constexpr float L2E = 1.44269504088896340736f;
-
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-struct Soft {   // max and sum of exp(l - max); (-inf, 0) is the empty set
-  float m, s;
-};
-
+// NOT the pick head's merge (acc_merge of csrc/mre_attend.hip).  sa and sb are formed in statements of their own and then
+// added: two multiplies and an add under -ffp-contract=on, where the pick head's single expression is a multiply and a fused
+// multiply-add; one shared merge would change the last bit of one head's lse.  An empty pair returns (m, 0) early; non-finite
+// sums are left unspecified here (the pick head substitutes 0 for a -inf max, -inf being a valid logit there).
 __device__ __forceinline__ Soft soft_merge(Soft a, Soft b) {
   const float m = fmaxf(a.m, b.m);
   if (m == -__builtin_inff()) return Soft{m, 0.f};
@@ -50,10 +44,7 @@ __device__ __forceinline__ Soft soft_merge(Soft a, Soft b) {
 
 __device__ __forceinline__ Soft wave_soft(Soft v) {
 #pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const Soft o = {__shfl_xor(v.m, m, 64), __shfl_xor(v.s, m, 64)};
-    v = soft_merge(v, o);
-  }
+  for (int m = 32; m >= 1; m >>= 1) v = soft_merge(v, Soft{__shfl_xor(v.m, m, 64), __shfl_xor(v.s, m, 64)});
   return v;
 }
 
@@ -62,12 +53,12 @@ __global__ void __launch_bounds__(NT, 2) k_correlate_soft(CorrelateLossArgs s) {
   __shared__ __attribute__((aligned(16))) uint16_t patch[PROWS * PITCH];
   __shared__ Soft red[NT / 64];
   const CorrelateArgs& a = s.fwd;
-  const uint32_t t = threadIdx.x, lane = t & 63;
-  const int wv = __builtin_amdgcn_readfirstlane((int)(t >> 6));
-  const uint32_t lr = lane & 15, g = lane >> 4;
+  const CrLane l = cr_lane();
+  const uint32_t t = l.t, lane = l.lane, lr = l.lr, g = l.g;
+  const int wv = l.wv;
   const int R = (int)a.rot, H = (int)a.h, W = (int)a.w;
   const uint32_t tiles = a.tiles_x * a.tiles_y;
-  const uint32_t e = blockIdx.z * gridDim.y + blockIdx.y, tile = blockIdx.x;
+  const uint32_t e = env_index(), tile = blockIdx.x;
   if (e >= a.n) return;
   const int y0 = (int)(tile / a.tiles_x) * CR_TILE_H, x0 = (int)(tile % a.tiles_x) * CR_TILE_W;
   const int xw = x0 + 8 * wv;
@@ -140,6 +131,7 @@ __global__ void __launch_bounds__(NT, 2) k_correlate_soft(CorrelateLossArgs s) {
   }
 }
 
+// the slots of an env in strided partials per lane, then the butterfly (the pick head's k_attend_merge goes 0 .. S - 1)
 __global__ void __launch_bounds__(64) k_correlate_lse(CorrelateLossArgs s) {
   const CorrelateArgs& a = s.fwd;
   const uint32_t tiles = a.tiles_x * a.tiles_y;
@@ -150,14 +142,12 @@ __global__ void __launch_bounds__(64) k_correlate_lse(CorrelateLossArgs s) {
     for (uint32_t k = threadIdx.x; k < tiles; k += 64) b = soft_merge(b, slots[k]);
     b = wave_soft(b);
     if (threadIdx.x == 0) {
-      const int64_t tgt = s.target[e];
-      const bool inside = tgt >= 0 && tgt < cells;
-      const float lse = b.m + logf(b.s);
-      // the lane that held the target cell has written its logit; nobody has for a target outside
-      const float tl = inside ? s.target_logit[e] : __builtin_nanf("");
-      if (!inside) s.target_logit[e] = tl;
-      s.lse[e] = lse;
-      s.loss[e] = lse - tl;
+      // the lane that held the target cell has written its logit; nobody has for a target outside: what is read then is
+      // never used (soft_finish answers NaN), and the NaN is stored over it
+      const SoftEnd f = soft_finish(b, s.target[e], cells, s.target_logit[e]);
+      s.lse[e] = f.lse;
+      s.target_logit[e] = f.target_logit;
+      s.loss[e] = f.loss;
     }
   }
 }
@@ -173,11 +163,11 @@ __global__ void __launch_bounds__(256) k_correlate_flip(CorrelateGradArgs a, uin
 template <int RT, bool VK>
 __global__ void __launch_bounds__(NT, 2) k_correlate_grad_kern(CorrelateGradArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t patch[PROWS * PITCH];
-  const uint32_t t = threadIdx.x, lane = t & 63;
+  const uint32_t t = threadIdx.x, lane = t & 63;   // (not cr_lane: its order of lr and g renames this kernel's registers)
   const int wv = __builtin_amdgcn_readfirstlane((int)(t >> 6));
   const uint32_t lr = lane & 15, g = lane >> 4;
   const int R = (int)a.rot, D = (int)a.depth, H = (int)a.h, W = (int)a.w, c = (int)a.crop, half = c / 2;
-  const uint32_t e = blockIdx.z * gridDim.y + blockIdx.y;
+  const uint32_t e = env_index();
   if (e >= a.n) return;
   const uint32_t tj = cr_tiles(a.crop, CR_TILE_W), ntile = tj * cr_tiles(a.crop, CR_TILE_H), split = cr_split(a.h);
   const uint32_t tile = blockIdx.x % ntile;
@@ -230,11 +220,6 @@ __global__ void __launch_bounds__(256) k_correlate_sum(CorrelateGradArgs a) {
   }
 }
 
-dim3 env_grid(uint32_t x, uint32_t n) {
-  const uint32_t gy = n < MAX_GRID_Y ? n : MAX_GRID_Y;
-  return dim3(x, gy, (n + gy - 1) / gy);
-}
-
 uint32_t flat_grid(size_t total) {
   const size_t b = (total + 255) / 256;
   return (uint32_t)(b < MAX_GRID ? b : MAX_GRID);
@@ -242,20 +227,17 @@ uint32_t flat_grid(size_t total) {
 
 template <bool G>
 void launch_soft(const CorrelateLossArgs* s, hipStream_t stream) {
-  typedef void (*Kernel)(CorrelateLossArgs);
-  static const Kernel table[8] = {k_correlate_soft<1, false, G>, k_correlate_soft<1, true, G>, k_correlate_soft<2, false, G>,
-                                  k_correlate_soft<2, true, G>,  k_correlate_soft<3, false, G>, k_correlate_soft<3, true, G>,
-                                  k_correlate_soft<4, false, G>, k_correlate_soft<4, true, G>};
   const CorrelateArgs& a = s->fwd;
-  const int rt = ((int)a.rot + 15) / 16;
-  hipLaunchKernelGGL(table[2 * (rt - 1) + (a.vec_kern ? 1 : 0)], env_grid(a.tiles_x * a.tiles_y, a.n), dim3(NT), 0, stream, *s);
+#define CR_SOFT(RT, VK) k_correlate_soft<RT, VK, G>
+  static void (*const table[8])(CorrelateLossArgs) = CR_TABLE(CR_SOFT);
+  hipLaunchKernelGGL(table[cr_which(a.rot, a.vec_kern)], env_grid(a.tiles_x * a.tiles_y, a.n), dim3(NT), 0, stream, *s);
 }
 
 }  // namespace
 
 extern "C" void mre_launch_correlate_loss(const CorrelateLossArgs* s, hipStream_t stream) {
   launch_soft<false>(s, stream);
-  hipLaunchKernelGGL(k_correlate_lse, dim3(s->fwd.n < MAX_GRID ? s->fwd.n : MAX_GRID), dim3(64), 0, stream, *s);
+  hipLaunchKernelGGL(k_correlate_lse, wave_per_env_grid(s->fwd.n), dim3(64), 0, stream, *s);
 }
 
 extern "C" void mre_launch_correlate_dlogits(const CorrelateLossArgs* s, hipStream_t stream) { launch_soft<true>(s, stream); }
@@ -276,14 +258,11 @@ extern "C" void mre_launch_correlate_grad_scene(const CorrelateGradArgs* a, hipS
 }
 
 extern "C" void mre_launch_correlate_grad_kern(const CorrelateGradArgs* a, hipStream_t stream) {
-  typedef void (*Kernel)(CorrelateGradArgs);
-  static const Kernel table[8] = {k_correlate_grad_kern<1, false>, k_correlate_grad_kern<1, true>, k_correlate_grad_kern<2, false>,
-                                  k_correlate_grad_kern<2, true>,  k_correlate_grad_kern<3, false>, k_correlate_grad_kern<3, true>,
-                                  k_correlate_grad_kern<4, false>, k_correlate_grad_kern<4, true>};
-  const int rt = ((int)a->rot + 15) / 16;
+#define CR_GRAD_KERN(RT, VK) k_correlate_grad_kern<RT, VK>
+  static void (*const table[8])(CorrelateGradArgs) = CR_TABLE(CR_GRAD_KERN);
   const uint32_t split = cr_split(a->h);
   const uint32_t x = cr_tiles(a->crop, CR_TILE_W) * cr_tiles(a->crop, CR_TILE_H) * a->depth * split;
-  hipLaunchKernelGGL(table[2 * (rt - 1) + (a->vec_g ? 1 : 0)], env_grid(x, a->n), dim3(NT), 0, stream, *a);
+  hipLaunchKernelGGL(table[cr_which(a->rot, a->vec_g)], env_grid(x, a->n), dim3(NT), 0, stream, *a);
   if (split > 1)
     hipLaunchKernelGGL(k_correlate_sum, dim3(flat_grid((size_t)a->n * a->rot * a->depth * a->crop * a->crop)), dim3(256), 0,
                        stream, *a);

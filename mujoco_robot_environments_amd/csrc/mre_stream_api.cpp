@@ -405,6 +405,38 @@ extern "C" int mre_warp_inputs(void* stream, const float* hmap, const uint8_t* c
   return MRE_OK;
 }
 
+// ---- what the entries of the two Transporter heads check alike; `wh` is the entry's name
+static size_t element_size(int dtype) { return dtype == MRE_BF16 ? 2 : 4; }
+
+static int workspace_ok(const std::string& wh, const void* workspace, size_t workspace_bytes, size_t need, const char* sizer) {
+  if (workspace && !((uintptr_t)workspace & 15) && workspace_bytes >= need) return MRE_OK;
+  return fail(MRE_ERR_ARG, wh + ": workspace must be non-NULL, 16-byte aligned and as large as " + sizer + " says");
+}
+
+static int best_pair_ok(const std::string& wh, const int64_t* best_index, const float* best_value) {
+  if (!best_index != !best_value) return fail(MRE_ERR_ARG, wh + ": best_index and best_value are NULL together or not at all");
+  if (((uintptr_t)best_index & 7) || ((uintptr_t)best_value & 3))
+    return fail(MRE_ERR_ARG, wh + ": best_index must be 8-byte and best_value 4-byte aligned");
+  return MRE_OK;
+}
+
+static int target_ok(const std::string& wh, const int64_t* target) {
+  return ((uintptr_t)target & 7) ? fail(MRE_ERR_ARG, wh + ": target must be 8-byte aligned") : MRE_OK;
+}
+
+// `required`: none of the three may be NULL (else the entry has its own rule for that)
+static int loss_outputs_ok(const std::string& wh, const float* lse, const float* target_logit, const float* loss, bool required) {
+  if (required && (!lse || !target_logit || !loss)) return fail(MRE_ERR_ARG, wh + ": null lse, target_logit or loss");
+  if (((uintptr_t)lse & 3) || ((uintptr_t)target_logit & 3) || ((uintptr_t)loss & 3))
+    return fail(MRE_ERR_ARG, wh + ": lse, target_logit and loss must be 4-byte aligned");
+  return MRE_OK;
+}
+
+static int launched(void) {
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
 // ---- the Transporter place head on the device (csrc/mre_correlate.hip): correlate the crops with the scene, best cell
 static bool correlate_shape_ok(int n, int rotations, int h, int w) {
   return n >= 0 && rotations >= 1 && rotations <= CR_MAX_ROT && h >= 1 && w >= 1 && h <= CR_MAX_DIM && w <= CR_MAX_DIM &&
@@ -426,15 +458,15 @@ extern "C" int mre_correlate_workspace(int n, int rotations, int h, int w, size_
   return MRE_OK;
 }
 
-// the ranges mre_correlate shares with the five training entries below; an empty string when they hold
-static std::string correlate_ranges(int n, int rotations, int depth, int h, int w, int crop) {
-  if (n < 0) return ": n >= 0";
-  if (rotations < 1 || rotations > CR_MAX_ROT) return ": 1 <= rotations <= 64";
-  if (depth < 1 || depth > CR_MAX_DEPTH) return ": 1 <= depth <= 16";
-  if (crop < 2 || crop > CR_MAX_CROP || (crop & 1)) return ": crop must be even, 2 <= crop <= 64";
-  if (h < 1 || w < 1 || h > CR_MAX_DIM || w > CR_MAX_DIM) return ": 1 <= h, w <= 4096";
-  if (!correlate_shape_ok(n, rotations, h, w)) return ": rotations * h * w must be below 2^31";
-  return "";
+// the ranges mre_correlate shares with the five training entries below
+static int correlate_ranges(const std::string& wh, int n, int rotations, int depth, int h, int w, int crop) {
+  if (n < 0) return fail(MRE_ERR_ARG, wh + ": n >= 0");
+  if (rotations < 1 || rotations > CR_MAX_ROT) return fail(MRE_ERR_ARG, wh + ": 1 <= rotations <= 64");
+  if (depth < 1 || depth > CR_MAX_DEPTH) return fail(MRE_ERR_ARG, wh + ": 1 <= depth <= 16");
+  if (crop < 2 || crop > CR_MAX_CROP || (crop & 1)) return fail(MRE_ERR_ARG, wh + ": crop must be even, 2 <= crop <= 64");
+  if (h < 1 || w < 1 || h > CR_MAX_DIM || w > CR_MAX_DIM) return fail(MRE_ERR_ARG, wh + ": 1 <= h, w <= 4096");
+  if (!correlate_shape_ok(n, rotations, h, w)) return fail(MRE_ERR_ARG, wh + ": rotations * h * w must be below 2^31");
+  return MRE_OK;
 }
 
 // what every launch of the forward reads: the operands, the shape, the tiling
@@ -453,20 +485,16 @@ extern "C" int mre_correlate(void* stream, const uint16_t* scene, const uint16_t
                              int h, int w, int crop, int dtype, void* logits, int64_t* best_index, float* best_value,
                              void* workspace, size_t workspace_bytes) {
   const std::string wh("mre_correlate");
-  const std::string bad = correlate_ranges(n, rotations, depth, h, w, crop);
-  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  if (int rc = correlate_ranges(wh, n, rotations, depth, h, w, crop)) return rc;
   if (!scene || !kern) return fail(MRE_ERR_ARG, wh + ": null scene or kern");
   if (((uintptr_t)scene & 1) || ((uintptr_t)kern & 1)) return fail(MRE_ERR_ARG, wh + ": scene and kern must be 2-byte aligned");
   if (dtype != MRE_F32 && dtype != MRE_BF16) return fail(MRE_ERR_ARG, wh + ": dtype must be MRE_F32 or MRE_BF16");
-  const size_t esize = dtype == MRE_BF16 ? 2 : 4;
+  const size_t esize = element_size(dtype);
   if ((uintptr_t)logits & (esize - 1)) return fail(MRE_ERR_ARG, wh + ": logits must be aligned to its element size");
-  if (!best_index != !best_value) return fail(MRE_ERR_ARG, wh + ": best_index and best_value are NULL together or not at all");
-  if (((uintptr_t)best_index & 7) || ((uintptr_t)best_value & 3))
-    return fail(MRE_ERR_ARG, wh + ": best_index must be 8-byte and best_value 4-byte aligned");
+  if (int rc = best_pair_ok(wh, best_index, best_value)) return rc;
   if (!logits && !best_index) return fail(MRE_ERR_ARG, wh + ": nothing to write: logits and best_* are all NULL");
   const size_t need = correlate_workspace(n, h, w);
-  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need)
-    return fail(MRE_ERR_ARG, wh + ": workspace must be non-NULL, 16-byte aligned and as large as mre_correlate_workspace says");
+  if (int rc = workspace_ok(wh, workspace, workspace_bytes, need, "mre_correlate_workspace")) return rc;
   // no output or workspace byte range may overlap an input (n < 2^31, 64 x 16 x 64 x 64 x 2 B per env: below 2^54)
   const size_t cells = (size_t)h * w;
   const ByteRange ins[2] = {{scene, 2 * (size_t)n * depth * cells}, {kern, 2 * (size_t)n * rotations * depth * crop * crop}};
@@ -483,8 +511,7 @@ extern "C" int mre_correlate(void* stream, const uint16_t* scene, const uint16_t
   a.bf16 = dtype == MRE_BF16 ? 1u : 0u;
   a.vec_out = (logits && w % 8 == 0 && !((uintptr_t)logits & 15)) ? 1u : 0u;   // wide too: a lane's 8 logits of a pixel row
   mre_launch_correlate(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
+  return launched();
 }
 
 // ---- training the place head (csrc/mre_correlate_grad.hip): the loss, its gradient g, and the gradients of any g
@@ -492,17 +519,13 @@ extern "C" int mre_correlate_loss(void* stream, const uint16_t* scene, const uin
                                   int h, int w, int crop, const int64_t* target, float* lse, float* target_logit,
                                   float* loss, void* workspace, size_t workspace_bytes) {
   const std::string wh("mre_correlate_loss");
-  const std::string bad = correlate_ranges(n, rotations, depth, h, w, crop);
-  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  if (int rc = correlate_ranges(wh, n, rotations, depth, h, w, crop)) return rc;
   if (!scene || !kern || !target) return fail(MRE_ERR_ARG, wh + ": null scene, kern or target");
   if (((uintptr_t)scene & 1) || ((uintptr_t)kern & 1)) return fail(MRE_ERR_ARG, wh + ": scene and kern must be 2-byte aligned");
-  if ((uintptr_t)target & 7) return fail(MRE_ERR_ARG, wh + ": target must be 8-byte aligned");
-  if (!lse || !target_logit || !loss) return fail(MRE_ERR_ARG, wh + ": null lse, target_logit or loss");
-  if (((uintptr_t)lse & 3) || ((uintptr_t)target_logit & 3) || ((uintptr_t)loss & 3))
-    return fail(MRE_ERR_ARG, wh + ": lse, target_logit and loss must be 4-byte aligned");
+  if (int rc = target_ok(wh, target)) return rc;
+  if (int rc = loss_outputs_ok(wh, lse, target_logit, loss, true)) return rc;
   const size_t need = correlate_workspace(n, h, w);
-  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need)
-    return fail(MRE_ERR_ARG, wh + ": workspace must be non-NULL, 16-byte aligned and as large as mre_correlate_workspace says");
+  if (int rc = workspace_ok(wh, workspace, workspace_bytes, need, "mre_correlate_workspace")) return rc;
   // (lengths below 2^54, as in mre_correlate)
   const size_t cells = (size_t)h * w;
   const ByteRange ins[3] = {{scene, 2 * (size_t)n * depth * cells}, {kern, 2 * (size_t)n * rotations * depth * crop * crop},
@@ -518,19 +541,17 @@ extern "C" int mre_correlate_loss(void* stream, const uint16_t* scene, const uin
   correlate_forward_args(a.fwd, scene, kern, n, rotations, depth, h, w, crop, workspace);
   a.target = target; a.lse = lse; a.target_logit = target_logit; a.loss = loss;
   mre_launch_correlate_loss(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
+  return launched();
 }
 
 extern "C" int mre_correlate_dlogits(void* stream, const uint16_t* scene, const uint16_t* kern, int n, int rotations,
                                      int depth, int h, int w, int crop, const int64_t* target, const float* lse,
                                      const float* weight, uint16_t* g) {
   const std::string wh("mre_correlate_dlogits");
-  const std::string bad = correlate_ranges(n, rotations, depth, h, w, crop);
-  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  if (int rc = correlate_ranges(wh, n, rotations, depth, h, w, crop)) return rc;
   if (!scene || !kern || !target || !lse) return fail(MRE_ERR_ARG, wh + ": null scene, kern, target or lse");
   if (((uintptr_t)scene & 1) || ((uintptr_t)kern & 1)) return fail(MRE_ERR_ARG, wh + ": scene and kern must be 2-byte aligned");
-  if ((uintptr_t)target & 7) return fail(MRE_ERR_ARG, wh + ": target must be 8-byte aligned");
+  if (int rc = target_ok(wh, target)) return rc;
   if (((uintptr_t)lse & 3) || ((uintptr_t)weight & 3)) return fail(MRE_ERR_ARG, wh + ": lse and weight must be 4-byte aligned");
   if (!g || ((uintptr_t)g & 1)) return fail(MRE_ERR_ARG, wh + ": g must be non-NULL and 2-byte aligned");
   const size_t cells = (size_t)h * w;
@@ -548,8 +569,7 @@ extern "C" int mre_correlate_dlogits(void* stream, const uint16_t* scene, const 
   a.target = target; a.lse_in = lse; a.weight = weight; a.g = g;
   a.vec_g = (w % 8 == 0 && !((uintptr_t)g & 15)) ? 1u : 0u;
   mre_launch_correlate_dlogits(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
+  return launched();
 }
 
 // grad_scene keeps the flipped kernels (bfloat16) there, grad_kern the partial tiles of its cr_split(h) workgroups (float32)
@@ -562,8 +582,7 @@ static size_t correlate_grad_workspace(int n, int rotations, int depth, int h, i
 extern "C" int mre_correlate_grad_workspace(int n, int rotations, int depth, int h, int w, int crop, size_t* bytes) {
   const std::string wh("mre_correlate_grad_workspace");
   if (!bytes) return fail(MRE_ERR_ARG, wh + ": null bytes");
-  const std::string bad = correlate_ranges(n, rotations, depth, h, w, crop);
-  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  if (int rc = correlate_ranges(wh, n, rotations, depth, h, w, crop)) return rc;
   *bytes = correlate_grad_workspace(n, rotations, depth, h, crop);
   return MRE_OK;
 }
@@ -572,14 +591,12 @@ extern "C" int mre_correlate_grad_workspace(int n, int rotations, int depth, int
 static int correlate_grad_check(const std::string& wh, const char* other_name, const uint16_t* g, const uint16_t* other,
                                 size_t other_bytes, int n, int rotations, int depth, int h, int w, int crop, float* out,
                                 size_t out_bytes, void* workspace, size_t workspace_bytes) {
-  const std::string bad = correlate_ranges(n, rotations, depth, h, w, crop);
-  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  if (int rc = correlate_ranges(wh, n, rotations, depth, h, w, crop)) return rc;
   if (!g || !other) return fail(MRE_ERR_ARG, wh + ": null g or " + other_name);
   if (((uintptr_t)g & 1) || ((uintptr_t)other & 1)) return fail(MRE_ERR_ARG, wh + ": g and " + other_name + " must be 2-byte aligned");
   if (!out || ((uintptr_t)out & 3)) return fail(MRE_ERR_ARG, wh + ": the output must be non-NULL and 4-byte aligned");
   const size_t need = correlate_grad_workspace(n, rotations, depth, h, crop);
-  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need)
-    return fail(MRE_ERR_ARG, wh + ": workspace must be non-NULL, 16-byte aligned and as large as mre_correlate_grad_workspace says");
+  if (int rc = workspace_ok(wh, workspace, workspace_bytes, need, "mre_correlate_grad_workspace")) return rc;
   // (n < 2^31 envs of at most 4 x 4 x 64 x 16 x 64 x 64 B of workspace: below 2^60)
   const ByteRange ins[2] = {{g, 2 * (size_t)n * rotations * h * w}, {other, other_bytes}};
   const ByteRange outs[2] = {{out, out_bytes}, {workspace, need}};
@@ -609,8 +626,7 @@ extern "C" int mre_correlate_grad_scene(void* stream, const uint16_t* g, const u
   a.kern = kern;
   a.vec_out = (w % 8 == 0 && !((uintptr_t)grad_scene & 15)) ? 1u : 0u;
   mre_launch_correlate_grad_scene(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
+  return launched();
 }
 
 extern "C" int mre_correlate_grad_kern(void* stream, const uint16_t* g, const uint16_t* scene, int n, int rotations, int depth,
@@ -624,18 +640,17 @@ extern "C" int mre_correlate_grad_kern(void* stream, const uint16_t* g, const ui
   a.scene = scene;
   a.vec_g = (w % 8 == 0 && !((uintptr_t)g & 15)) ? 1u : 0u;
   mre_launch_correlate_grad_kern(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
+  return launched();
 }
 
 // ---- the Transporter pick head on the device (csrc/mre_attend.hip): best cell, loss and gradient from stored logits
-static std::string attend_ranges(int n, int rotations, int h, int w, int dtype) {
-  if (n < 0) return ": n >= 0";
-  if (rotations < 1 || rotations > AT_MAX_ROT) return ": 1 <= rotations <= 64";
-  if (h < 1 || w < 1 || h > AT_MAX_DIM || w > AT_MAX_DIM) return ": 1 <= h, w <= 4096";
-  if ((long long)rotations * h * w >= (1ll << 31)) return ": rotations * h * w must be below 2^31";
-  if (dtype != MRE_F32 && dtype != MRE_BF16) return ": dtype must be MRE_F32 or MRE_BF16";
-  return "";
+static int attend_ranges(const std::string& wh, int n, int rotations, int h, int w, int dtype) {
+  if (n < 0) return fail(MRE_ERR_ARG, wh + ": n >= 0");
+  if (rotations < 1 || rotations > AT_MAX_ROT) return fail(MRE_ERR_ARG, wh + ": 1 <= rotations <= 64");
+  if (h < 1 || w < 1 || h > AT_MAX_DIM || w > AT_MAX_DIM) return fail(MRE_ERR_ARG, wh + ": 1 <= h, w <= 4096");
+  if ((long long)rotations * h * w >= (1ll << 31)) return fail(MRE_ERR_ARG, wh + ": rotations * h * w must be below 2^31");
+  if (dtype != MRE_F32 && dtype != MRE_BF16) return fail(MRE_ERR_ARG, wh + ": dtype must be MRE_F32 or MRE_BF16");
+  return MRE_OK;
 }
 
 static size_t attend_workspace(int n, int rotations, int h, int w) {
@@ -646,8 +661,7 @@ static size_t attend_workspace(int n, int rotations, int h, int w) {
 extern "C" int mre_attend_workspace(int n, int rotations, int h, int w, size_t* bytes) {
   const std::string wh("mre_attend_workspace");
   if (!bytes) return fail(MRE_ERR_ARG, wh + ": null bytes");
-  const std::string bad = attend_ranges(n, rotations, h, w, MRE_F32);
-  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
+  if (int rc = attend_ranges(wh, n, rotations, h, w, MRE_F32)) return rc;
   *bytes = attend_workspace(n, rotations, h, w);
   return MRE_OK;
 }
@@ -656,23 +670,18 @@ extern "C" int mre_attend(void* stream, const void* logits, int n, int rotations
                           const int64_t* target, int64_t* best_index, float* best_value, float* lse, float* target_logit,
                           float* loss, void* workspace, size_t workspace_bytes) {
   const std::string wh("mre_attend");
-  const std::string bad = attend_ranges(n, rotations, h, w, dtype);
-  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
-  const size_t esize = dtype == MRE_BF16 ? 2 : 4;
+  if (int rc = attend_ranges(wh, n, rotations, h, w, dtype)) return rc;
+  const size_t esize = element_size(dtype);
   if (!logits || ((uintptr_t)logits & (esize - 1)))
     return fail(MRE_ERR_ARG, wh + ": logits must be non-NULL and aligned to its element size");
-  if (!best_index != !best_value) return fail(MRE_ERR_ARG, wh + ": best_index and best_value are NULL together or not at all");
-  if (((uintptr_t)best_index & 7) || ((uintptr_t)best_value & 3))
-    return fail(MRE_ERR_ARG, wh + ": best_index must be 8-byte and best_value 4-byte aligned");
+  if (int rc = best_pair_ok(wh, best_index, best_value)) return rc;
   if (!target != !lse || !target != !target_logit || !target != !loss)
     return fail(MRE_ERR_ARG, wh + ": target, lse, target_logit and loss are NULL together or not at all");
-  if ((uintptr_t)target & 7) return fail(MRE_ERR_ARG, wh + ": target must be 8-byte aligned");
-  if (((uintptr_t)lse & 3) || ((uintptr_t)target_logit & 3) || ((uintptr_t)loss & 3))
-    return fail(MRE_ERR_ARG, wh + ": lse, target_logit and loss must be 4-byte aligned");
+  if (int rc = target_ok(wh, target)) return rc;
+  if (int rc = loss_outputs_ok(wh, lse, target_logit, loss, false)) return rc;
   if (!target && !best_index) return fail(MRE_ERR_ARG, wh + ": nothing to write: target and best_* are all NULL");
   const size_t need = attend_workspace(n, rotations, h, w);
-  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < need)
-    return fail(MRE_ERR_ARG, wh + ": workspace must be non-NULL, 16-byte aligned and as large as mre_attend_workspace says");
+  if (int rc = workspace_ok(wh, workspace, workspace_bytes, need, "mre_attend_workspace")) return rc;
   // no output or workspace byte range may overlap an input (n < 2^31 envs of fewer than 2^31 cells of 4 B: below 2^64)
   const size_t cells = (size_t)rotations * h * w;
   const ByteRange ins[2] = {{logits, esize * (size_t)n * cells}, {target, 8 * (size_t)n}};
@@ -690,19 +699,17 @@ extern "C" int mre_attend(void* stream, const void* logits, int n, int rotations
   a.lse = lse; a.target_logit = target_logit; a.loss = loss; a.workspace = workspace;
   a.n = (uint32_t)n; a.cells = (uint32_t)cells; a.bf16 = dtype == MRE_BF16 ? 1u : 0u;
   mre_launch_attend(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
+  return launched();
 }
 
 extern "C" int mre_attend_dlogits(void* stream, const void* logits, int n, int rotations, int h, int w, int dtype,
                                   const int64_t* target, const float* lse, const float* weight, void* g) {
   const std::string wh("mre_attend_dlogits");
-  const std::string bad = attend_ranges(n, rotations, h, w, dtype);
-  if (!bad.empty()) return fail(MRE_ERR_ARG, wh + bad);
-  const size_t esize = dtype == MRE_BF16 ? 2 : 4;
+  if (int rc = attend_ranges(wh, n, rotations, h, w, dtype)) return rc;
+  const size_t esize = element_size(dtype);
   if (!logits || !target || !lse) return fail(MRE_ERR_ARG, wh + ": null logits, target or lse");
   if ((uintptr_t)logits & (esize - 1)) return fail(MRE_ERR_ARG, wh + ": logits must be aligned to its element size");
-  if ((uintptr_t)target & 7) return fail(MRE_ERR_ARG, wh + ": target must be 8-byte aligned");
+  if (int rc = target_ok(wh, target)) return rc;
   if (((uintptr_t)lse & 3) || ((uintptr_t)weight & 3)) return fail(MRE_ERR_ARG, wh + ": lse and weight must be 4-byte aligned");
   if (!g || ((uintptr_t)g & (esize - 1))) return fail(MRE_ERR_ARG, wh + ": g must be non-NULL and aligned to its element size");
   // (lengths below 2^64, as in mre_attend)
@@ -720,6 +727,5 @@ extern "C" int mre_attend_dlogits(void* stream, const void* logits, int n, int r
   a.logits = logits; a.target = target; a.lse = lse; a.weight = weight; a.g = g;
   a.n = (uint32_t)n; a.cells = (uint32_t)cells; a.bf16 = dtype == MRE_BF16 ? 1u : 0u;
   mre_launch_attend_dlogits(&a, (hipStream_t)stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
+  return launched();
 }

@@ -77,19 +77,33 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _workspace(entry: str, dev, *shape):
-    """The workspace of a call: a ``torch.empty`` of as many bytes on ``dev`` as the library's ``entry`` (an
-    ``mre_*_workspace``) asks for ``shape``, and that number."""
+@functools.lru_cache(maxsize=64)
+def _workspace_bytes(entry: str, *shape) -> int:   # what the library's ``entry`` (an ``mre_*_workspace``) asks for ``shape``
     nbytes = C.c_size_t(0)
     _lib.check(getattr(_lib.lib(), entry)(*shape, C.byref(nbytes)), entry)
-    return torch.empty((nbytes.value,), dtype=torch.uint8, device=dev), nbytes.value
+    return int(nbytes.value)
+
+
+def _workspace(entry: str, dev, *shape):
+    """The workspace of a call: a ``torch.empty`` of ``_workspace_bytes(entry, *shape)`` bytes on ``dev``, and that number."""
+    nbytes = _workspace_bytes(entry, *shape)
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
+
+
+def _empty_if(on: bool, shape, dtype, dev):   # an output that is asked for, or None
+    return torch.empty(shape, dtype=dtype, device=dev) if on else None
+
+
+def _in_place(dtypes, *tensors) -> bool:   # what a kernel reads in place: contiguous CUDA tensors of one of ``dtypes``
+    return all(t.is_cuda and t.dtype in dtypes and t.is_contiguous() for t in tensors)
 
 
 def _maps_on_device(height, *companions) -> bool:
     """What the warp kernels read in place: a contiguous CUDA float32 ``height`` with contiguous uint8 companions (or None)
     on its device."""
-    return height.is_cuda and height.dtype == torch.float32 and height.is_contiguous() and all(
-        x is None or (x.device == height.device and x.dtype == torch.uint8 and x.is_contiguous()) for x in companions)
+    given = [x for x in companions if x is not None]
+    return _in_place((torch.float32,), height) and _in_place((torch.uint8,), *given) and all(
+        x.device == height.device for x in given)
 
 
 def seg_labels_reference(seg: torch.Tensor, depth: Optional[torch.Tensor] = None, id0: int = PROP_GEOM_ID0,
@@ -148,9 +162,9 @@ def seg_labels(seg: torch.Tensor, depth: Optional[torch.Tensor] = None, id0: int
     zmin = None if depth is None else torch.empty((n, nid), dtype=torch.float32, device=dev)
     if n:
         with _stream_on(dev) as stream:
-            _lib.check(_lib.lib().mre_seg_labels(stream, seg.data_ptr(), None if depth is None else depth.data_ptr(),
+            _lib.check(_lib.lib().mre_seg_labels(stream, seg.data_ptr(), _ptr(depth),
                                                  n, h, w, int(id0), int(nid), stats.data_ptr(),
-                                                 None if zmin is None else zmin.data_ptr()), "mre_seg_labels")
+                                                 _ptr(zmin)), "mre_seg_labels")
     return SegLabels(stats[..., 0:4], stats[..., 4], stats[..., 5:7], zmin)
 
 
@@ -803,7 +817,7 @@ def warp_inputs(height: torch.Tensor, colour: Optional[torch.Tensor] = None, *, 
         with _stream_on(dev) as stream:
             _lib.check(_lib.lib().mre_warp_inputs(
                 stream, height.data_ptr(), colour.data_ptr() if channels.uses_colour else None, n, in_h, in_w,
-                None if index is None else index.data_ptr(), mats.data_ptr(), samples, out_h, out_w, nc,
+                _ptr(index), mats.data_ptr(), samples, out_h, out_w, nc,
                 C.addressof(src), C.addressof(scale), C.addressof(bias), _DTYPES[dtype], out.data_ptr()), "mre_warp_inputs")
     return out
 
@@ -846,6 +860,10 @@ MAX_ROTATIONS, MAX_DEPTH, MAX_CROP = 64, 16, 64   # the limits of mre_correlate
 Correlation = collections.namedtuple("Correlation", ["logits", "index", "value"])
 
 
+def _cells_in_range(rot, h, w) -> bool:   # the ranges of rotations, rows and columns that both heads take
+    return 1 <= rot <= MAX_ROTATIONS and 1 <= h <= MAX_MAP and 1 <= w <= MAX_MAP and rot * h * w < 2 ** 31
+
+
 def _correlate_args(scene, kernels, logits, best):
     if scene.dim() != 4 or kernels.dim() != 5:
         raise ValueError("scene must be [N, D, rows, columns] and kernels [N, R, D, crop, crop]")
@@ -855,7 +873,7 @@ def _correlate_args(scene, kernels, logits, best):
         raise ValueError("kernels must be [N, R, D, crop, crop] with the N and D of scene")
     if not (1 <= rot <= MAX_ROTATIONS and 1 <= depth <= MAX_DEPTH and 2 <= crop <= MAX_CROP and crop % 2 == 0):
         raise ValueError("1 <= R <= 64, 1 <= D <= 16 and an even crop of 2 .. 64")
-    if not (1 <= h <= MAX_MAP and 1 <= w <= MAX_MAP and rot * h * w < 2 ** 31):
+    if not _cells_in_range(rot, h, w):
         raise ValueError("1 <= rows, columns <= 4096 and R * rows * columns < 2^31")
     if logits not in (None, torch.float32, torch.bfloat16):
         raise ValueError("logits must be None, torch.float32 or torch.bfloat16")
@@ -875,9 +893,7 @@ def _logits_f32(scene, kernels, n, rot, depth, h, w, crop):
     return torch.nn.functional.conv2d(x, k, padding=crop // 2, groups=n)[..., :h, :w].reshape(n, rot, h, w)
 
 
-def _on_device(*tensors) -> bool:
-    """What the place head's kernels read in place: contiguous CUDA bfloat16"""
-    return all(t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous() for t in tensors)
+_on_device = functools.partial(_in_place, (torch.bfloat16,))   # what the place head's kernels read in place
 
 
 def correlate_reference(scene: torch.Tensor, kernels: torch.Tensor, *, logits=None, best: bool = True) -> Correlation:
@@ -912,9 +928,8 @@ def correlate(scene: torch.Tensor, kernels: torch.Tensor, *, logits=None, best: 
     if not _on_device(scene, kernels):
         return correlate_reference(scene, kernels, logits=logits, best=best)
     dev = scene.device
-    out = None if logits is None else torch.empty((n, rot, h, w), dtype=logits, device=dev)
-    index = torch.empty((n,), dtype=torch.int64, device=dev) if best else None
-    value = torch.empty((n,), dtype=torch.float32, device=dev) if best else None
+    out = _empty_if(logits is not None, (n, rot, h, w), logits, dev)
+    index, value = _empty_if(best, (n,), torch.int64, dev), _empty_if(best, (n,), torch.float32, dev)
     if n:
         work, nbytes = _workspace("mre_correlate_workspace", dev, n, rot, h, w)
         with _stream_on(dev) as stream:
@@ -993,7 +1008,7 @@ def place_loss_reference(scene: torch.Tensor, kernels: torch.Tensor, target, wei
     inside = (t >= 0) & (t < rot * h * w)
     at = flat.gather(1, torch.where(inside, t, torch.zeros_like(t))[:, None])[:, 0]
     loss = torch.logsumexp(flat, dim=1) - torch.where(inside, at, torch.full_like(at, float("nan")))
-    return loss if wgt is None else wgt * loss
+    return _weighted(loss, wgt)
 
 
 def _backward_args(scene, kernels, dlogits):
@@ -1082,8 +1097,13 @@ def place_dlogits(scene, kernels, target, lse, weight=None) -> torch.Tensor:
         with _stream_on(scene.device) as stream:
             _lib.check(_lib.lib().mre_correlate_dlogits(
                 stream, scene.detach().data_ptr(), kernels.detach().data_ptr(), n, rot, depth, h, w, crop, target.data_ptr(),
-                lse.data_ptr(), None if weight is None else weight.data_ptr(), g.data_ptr()), "mre_correlate_dlogits")
+                lse.data_ptr(), _ptr(weight), g.data_ptr()), "mre_correlate_dlogits")
     return g
+
+
+def _weighted(x, weight):
+    """``x`` times ``weight`` (None: 1): a head's loss, and in backward, of the incoming gradient, its dlogits' weight"""
+    return x if weight is None else weight * x
 
 
 class _PlaceLoss(torch.autograd.Function):
@@ -1092,13 +1112,12 @@ class _PlaceLoss(torch.autograd.Function):
         out = place_loss_forward(scene, kernels, target)
         ctx.save_for_backward(scene, kernels, target, out.lse)
         ctx.weight = weight
-        return out.loss if weight is None else weight * out.loss
+        return _weighted(out.loss, weight)
 
     @staticmethod
     def backward(ctx, grad):
         scene, kernels, target, lse = ctx.saved_tensors
-        wgt = grad.to(torch.float32) if ctx.weight is None else grad.to(torch.float32) * ctx.weight
-        g = place_dlogits(scene, kernels, target, lse, wgt.contiguous())
+        g = place_dlogits(scene, kernels, target, lse, _weighted(grad.to(torch.float32), ctx.weight).contiguous())
         gs = _grad_scene(scene, kernels, g) if ctx.needs_input_grad[0] else None
         gk = _grad_kernels(scene, kernels, g) if ctx.needs_input_grad[1] else None
         return gs, gk, None, None
@@ -1145,14 +1164,12 @@ def _attend_args(logits):
     if logits.dim() != 4:
         raise ValueError("logits must be [N, K, rows, columns]")
     n, rot, h, w = (int(x) for x in logits.shape)
-    if not (1 <= rot <= MAX_ROTATIONS and 1 <= h <= MAX_MAP and 1 <= w <= MAX_MAP and rot * h * w < 2 ** 31):
+    if not _cells_in_range(rot, h, w):
         raise ValueError("1 <= K <= 64, 1 <= rows, columns <= 4096 and K * rows * columns < 2^31")
     return n, rot, h, w
 
 
-def _logits_on_device(*tensors) -> bool:
-    """What the pick head's kernels read in place: contiguous CUDA float32 or bfloat16"""
-    return all(t.is_cuda and t.dtype in _DTYPES and t.is_contiguous() for t in tensors)
+_logits_on_device = functools.partial(_in_place, tuple(_DTYPES))   # what the pick head's kernels read in place
 
 
 def attend_reference(logits: torch.Tensor, target=None, best: bool = True) -> Attention:
@@ -1182,13 +1199,6 @@ def attend_reference(logits: torch.Tensor, target=None, best: bool = True) -> At
     return Attention(index, value, lse, at, loss)
 
 
-@functools.lru_cache(maxsize=64)
-def _attend_workspace(n, rot, h, w) -> int:
-    nbytes = C.c_size_t(0)
-    _lib.check(_lib.lib().mre_attend_workspace(n, rot, h, w, C.byref(nbytes)), "mre_attend_workspace")
-    return int(nbytes.value)
-
-
 def attend(logits: torch.Tensor, target=None, best: bool = True) -> Attention:
     """A Transporter's pick head: from the ``logits`` [N, K, rows, columns] of an attention network (K pick rotations, 1
     for a classic Transporter), per env the largest logit with its flat index (k * rows + y) * columns + x (``best``), and
@@ -1206,20 +1216,16 @@ def attend(logits: torch.Tensor, target=None, best: bool = True) -> Attention:
         return attend_reference(logits, target, best)
     dev = logits.device
     t = None if target is None else _as_target(target, n, dev)
-    index = torch.empty((n,), dtype=torch.int64, device=dev) if best else None
+    index = _empty_if(best, (n,), torch.int64, dev)
     # the four float32 rows and, behind them, the workspace (a multiple of 16 bytes per env, 16 n bytes in): one allocation
-    nbytes = _attend_workspace(n, rot, h, w) if n else 0
+    nbytes = _workspace_bytes("mre_attend_workspace", n, rot, h, w) if n else 0
     out = torch.empty((4 + nbytes // (4 * n) if n else 4, n), dtype=torch.float32, device=dev)
+    rows = [out[k] if on else None for k, on in enumerate((best, t is not None, t is not None, t is not None))]
     if n:
-        first = out.data_ptr()
-        ptr = lambda k, on: first + 4 * n * k if on else None
         with _stream_on(dev) as stream:
-            _lib.check(_lib.lib().mre_attend(stream, logits.data_ptr(), n, rot, h, w, _DTYPES[logits.dtype],
-                                             None if t is None else t.data_ptr(), index.data_ptr() if best else None,
-                                             ptr(0, best), ptr(1, t is not None), ptr(2, t is not None), ptr(3, t is not None),
-                                             first + 16 * n, nbytes), "mre_attend")
-    given = lambda k, on: out[k] if on else None
-    return Attention(index, given(0, best), given(1, t is not None), given(2, t is not None), given(3, t is not None))
+            _lib.check(_lib.lib().mre_attend(stream, logits.data_ptr(), n, rot, h, w, _DTYPES[logits.dtype], _ptr(t), _ptr(index),
+                                             *map(_ptr, rows), out.data_ptr() + 16 * n, nbytes), "mre_attend")
+    return Attention(index, *rows)
 
 
 def attend_dlogits(logits: torch.Tensor, target, lse: torch.Tensor, weight=None) -> torch.Tensor:
@@ -1239,7 +1245,7 @@ def attend_dlogits(logits: torch.Tensor, target, lse: torch.Tensor, weight=None)
         with _stream_on(dev) as stream:
             _lib.check(_lib.lib().mre_attend_dlogits(
                 stream, logits.data_ptr(), n, rot, h, w, _DTYPES[logits.dtype], target.data_ptr(), lse.data_ptr(),
-                None if weight is None else weight.data_ptr(), g.data_ptr()), "mre_attend_dlogits")
+                _ptr(weight), g.data_ptr()), "mre_attend_dlogits")
     return g
 
 
@@ -1249,13 +1255,12 @@ class _PickLoss(torch.autograd.Function):
         out = attend(logits, target, best=False)
         ctx.save_for_backward(logits, target, out.lse)
         ctx.weight = weight
-        return out.loss if weight is None else weight * out.loss
+        return _weighted(out.loss, weight)
 
     @staticmethod
     def backward(ctx, grad):
         logits, target, lse = ctx.saved_tensors
-        wgt = grad.to(torch.float32) if ctx.weight is None else grad.to(torch.float32) * ctx.weight
-        return attend_dlogits(logits, target, lse, wgt.contiguous()), None, None
+        return attend_dlogits(logits, target, lse, _weighted(grad.to(torch.float32), ctx.weight).contiguous()), None, None
 
 
 def pick_loss_reference(logits: torch.Tensor, target, weight=None) -> torch.Tensor:
@@ -1265,7 +1270,7 @@ def pick_loss_reference(logits: torch.Tensor, target, weight=None) -> torch.Tens
     n = _attend_args(logits)[0]
     loss = attend_reference(logits, target, best=False).loss
     wgt = _as_weight(weight, n, logits.device)
-    return loss if wgt is None else wgt * loss
+    return _weighted(loss, wgt)
 
 
 def pick_loss(logits: torch.Tensor, target, weight=None) -> torch.Tensor:

@@ -122,6 +122,18 @@ def transporter_poses(pick_xy, place_xy, place_angle, pick_quat=None, height: fl
     return np.concatenate([pick_xy, z, q0], axis=1), np.concatenate([place_xy, z, quat_mul(qz, q0)], axis=1)
 
 
+def _decision(best, shape, n_rotations, cell, kind):
+    """A head's ``best`` (index and value per env) over maps of ``shape`` = (rows, columns) as a ``kind`` of decision"""
+    cells, bins, angles = perception.decode_place(best.index, shape, n_rotations, check=False)
+    return kind(cells, bins, angles, perception.cell_2_world(cells, HEIGHTMAP_BOUNDS, cell), best.value)
+
+
+def _cell_target(cells, bins, features):
+    """The target a head's loss takes: ``cells`` [N, 2] at ``bins`` [N] over the maps of ``features``, on its device"""
+    target = perception.encode_place(np.asarray(cells), np.asarray(bins), tuple(features.shape[2:]))
+    return torch.from_numpy(target).to(features.device)
+
+
 class BatchedRearrangementEnv:
     """num_envs independent RearrangementEnv instances stepped in lockstep on one GPU."""
 
@@ -368,11 +380,8 @@ class BatchedRearrangementEnv:
         ``HEIGHTMAP_BOUNDS`` at ``cell`` metres per cell.  A ``PlaceDecision``: cells int64 [N, 2] (column, row), rotation
         bins int64 [N], angles float64 [N] (radians), xy float64 [N, 2] and the values float32 [N], on the features'
         device.  No logits are written and no state of the env changes."""
-        rows, cols = int(scene_features.shape[2]), int(scene_features.shape[3])
-        n_rotations = int(crop_features.shape[1])
         best = perception.correlate(scene_features, crop_features)
-        cells, bins, angles = perception.decode_place(best.index, (rows, cols), n_rotations, check=False)
-        return PlaceDecision(cells, bins, angles, perception.cell_2_world(cells, HEIGHTMAP_BOUNDS, cell), best.value)
+        return _decision(best, scene_features.shape[2:], int(crop_features.shape[1]), cell, PlaceDecision)
 
     def transporter_loss(self, scene_features, crop_features, batch, weight=None):
         """The training loss of a Transporter's place head for every env, float32 [N], on the device:
@@ -381,9 +390,8 @@ class BatchedRearrangementEnv:
         ``perception.TransporterBatch``: its moved place cell at its rotation bin (``perception.encode_place``).
         Differentiable with respect to both feature tensors; NaN for an env whose place cell lies outside the map (where
         ``batch.tries`` is 0).  No logits are written and no state of the env changes."""
-        rows, cols = int(scene_features.shape[2]), int(scene_features.shape[3])
-        target = perception.encode_place(np.asarray(batch.place), np.asarray(batch.rotation_index), (rows, cols))
-        return perception.place_loss(scene_features, crop_features, torch.from_numpy(target).to(scene_features.device), weight)
+        target = _cell_target(batch.place, batch.rotation_index, scene_features)
+        return perception.place_loss(scene_features, crop_features, target, weight)
 
     def transporter_pick(self, logits, cell: float = 0.0025):
         """The pick decision of a Transporter's attention head for every env, on the device: the best cell and rotation bin
@@ -391,10 +399,7 @@ class BatchedRearrangementEnv:
         Transporter; -inf masks a cell) by ``perception.attend`` and ``perception.decode_pick``, and that cell's centre in
         the world by ``perception.cell_2_world`` on ``HEIGHTMAP_BOUNDS`` at ``cell`` metres per cell.  A ``PickDecision`` on
         the logits' device; nothing synchronises and no state of the env changes."""
-        rot, rows, cols = (int(x) for x in logits.shape[1:])
-        best = perception.attend(logits)
-        cells, bins, angles = perception.decode_pick(best.index, (rows, cols), rot, check=False)
-        return PickDecision(cells, bins, angles, perception.cell_2_world(cells, HEIGHTMAP_BOUNDS, cell), best.value)
+        return _decision(perception.attend(logits), logits.shape[2:], int(logits.shape[1]), cell, PickDecision)
 
     def transporter_pick_loss(self, logits, batch, weight=None):
         """The training loss of a Transporter's attention head for every env, float32 [N], on the device:
@@ -403,10 +408,7 @@ class BatchedRearrangementEnv:
         (``perception.encode_pick``).  Differentiable with respect to ``logits``.  An env whose pick cell lies outside the
         map has no label: its loss is NaN and its gradient that of the logsumexp alone, so the caller gives such envs
         ``weight`` 0 (the gradient is then exactly 0) and leaves them out of the sum.  No state of the env changes."""
-        rows, cols = int(logits.shape[2]), int(logits.shape[3])
-        pick = np.asarray(batch.pick)
-        target = perception.encode_pick(pick, np.zeros(len(pick), np.int64), (rows, cols))
-        return perception.pick_loss(logits, torch.from_numpy(target).to(logits.device), weight)
+        return perception.pick_loss(logits, _cell_target(batch.pick, np.zeros(len(batch.pick), np.int64), logits), weight)
 
     def transporter_act(self, attention, query, key, *, channels, dtype, n_rotations: int = 36, crop: int = 64,
                         cell: float = 0.0025, depth=None, rgb=None, seg=None, maps=None):

@@ -1,6 +1,7 @@
 """Bad calls of the stream-only C ABI's perception entries, for tests/test_refusals.py and tests/golden/make_refusals.py:
 what every check of mre_heightmap, mre_heightmap_views, mre_correlate, mre_correlate_loss, mre_correlate_dlogits,
-mre_correlate_grad_scene, mre_correlate_grad_kern and mre_correlate_workspace answers, and in which order the checks come.
+mre_correlate_grad_scene, mre_correlate_grad_kern, mre_correlate_workspace, mre_attend, mre_attend_dlogits, mre_attend_workspace
+and mre_correlate_grad_workspace answers, and in which order the checks come.
 
 No case reaches a launch: every pointer is a HOST pointer into one arena, so a call that passes every other check is
 refused by the entry's "must be device pointers" check, and a call with n == 0 returns before it.  The shapes are tiny, so
@@ -43,6 +44,11 @@ DLOGITS = ["stream", "scene", "kern", "n", "rotations", "depth", "h", "w", "crop
 GRAD_SCENE = ["stream", "g", "kern", "n", "rotations", "depth", "h", "w", "crop", "out", "workspace", "workspace_bytes"]
 GRAD_KERN = ["stream", "g", "scene", "n", "rotations", "depth", "h", "w", "crop", "out", "workspace", "workspace_bytes"]
 WORKSPACE = ["n", "rotations", "h", "w", "bytes"]
+ATTEND = ["stream", "logits", "n", "rotations", "h", "w", "dtype", "target", "best_index", "best_value", "lse", "target_logit",
+          "loss", "workspace", "workspace_bytes"]
+ATTEND_DLOGITS = ["stream", "logits", "n", "rotations", "h", "w", "dtype", "target", "lse", "weight", "g"]
+ATTEND_WORKSPACE = ["n", "rotations", "h", "w", "bytes"]
+GRAD_WORKSPACE = ["n", "rotations", "depth", "h", "w", "crop", "bytes"]
 
 
 def cases():
@@ -194,6 +200,68 @@ def cases():
         ("good", {}), ("n == 0", dict(n=0)), ("null bytes", dict(bytes=None)), ("n < 0", dict(n=-1)),
         ("rotations 0", dict(rotations=0)), ("rotations 65", dict(rotations=65)), ("h 0", dict(h=0)), ("w 4097", dict(w=4097)),
         ("two: null bytes and n < 0", dict(bytes=None, n=-1)), ("two: rotations 65 and h 0", dict(rotations=65, h=0)),
+    ])
+    # ---- the pick head: 2 envs, 2 rotations, 8 x 8 cells
+    shape = dict(n=2, rotations=2, h=8, w=8)
+    alogits, agrad = slot(43), slot(44)
+    aranges = [("n < 0", dict(n=-1)), ("rotations 0", dict(rotations=0)), ("rotations 65", dict(rotations=65)), ("h 0", dict(h=0)),
+               ("w 4097", dict(w=4097)), ("dtype 2", dict(dtype=2)), ("two: rotations 0 and h 0", dict(rotations=0, h=0)),
+               ("two: n < 0 and w 0", dict(n=-1, w=0)), ("two: h 4097 and dtype 7", dict(h=4097, dtype=7))]
+    g = dict(stream=None, logits=alogits, **shape, dtype=0, target=target, best_index=best_index, best_value=best_value, lse=lse,
+             target_logit=target_logit, loss=loss, workspace=work, workspace_bytes=SLOT)
+    no_best, no_loss = dict(best_index=None, best_value=None), dict(target=None, lse=None, target_logit=None, loss=None)
+    table("mre_attend", ATTEND, g, [
+        ("host pointers", {}), ("host pointers, the decision alone", no_loss), ("host pointers, the loss alone", no_best),
+        ("host pointers, bf16", dict(dtype=1)), ("n == 0", dict(n=0)), *aranges,
+        ("null logits", dict(logits=None)), ("float32 logits misaligned", dict(logits=alogits + 2)),
+        ("bf16 logits misaligned", dict(dtype=1, logits=alogits + 1)), ("best_index without best_value", dict(best_value=None)),
+        ("best_value without best_index", dict(best_index=None)), ("best_index misaligned", dict(best_index=best_index + 4)),
+        ("best_value misaligned", dict(best_value=best_value + 2)), ("target without lse", dict(lse=None)),
+        ("target without target_logit", dict(target_logit=None)), ("target without loss", dict(loss=None)),
+        ("lse without target", dict(target=None)), ("loss alone", dict(target=None, lse=None, target_logit=None)),
+        ("target misaligned", dict(target=target + 4)), ("lse misaligned", dict(lse=lse + 2)),
+        ("target_logit misaligned", dict(target_logit=target_logit + 1)), ("loss misaligned", dict(loss=loss + 2)),
+        ("nothing to write", {**no_best, **no_loss}), ("null workspace", dict(workspace=None)),
+        ("workspace misaligned", dict(workspace=work + 8)), ("workspace too small", dict(workspace_bytes=31)),
+        ("lse on target", dict(lse=target)), ("best_value on logits", dict(best_value=alogits)),
+        ("workspace inside logits", dict(workspace=alogits + 16)),
+        ("two: dtype 2 and null logits", dict(dtype=2, logits=None)),
+        ("two: null logits and best_index without best_value", dict(logits=None, best_value=None)),
+        ("two: best_index misaligned and target without lse", dict(best_index=best_index + 4, lse=None)),
+        ("two: target without loss and target misaligned", dict(loss=None, target=target + 4)),
+        ("two: target misaligned and lse misaligned", dict(target=target + 4, lse=lse + 2)),
+        ("two: loss misaligned and nothing to write", {**no_best, **no_loss, "loss": loss + 2}),
+        ("two: nothing to write and null workspace", {**no_best, **no_loss, "workspace": None}),
+        ("two: workspace too small and lse on target", dict(workspace_bytes=0, lse=target)),
+        ("n == 0 and null workspace", dict(n=0, workspace=None)), ("n == 0 and lse on target", dict(n=0, lse=target)),
+        ("n == 0 and dtype 2", dict(n=0, dtype=2)),
+    ])
+
+    g = dict(stream=None, logits=alogits, **shape, dtype=0, target=target, lse=lse, weight=weight, g=agrad)
+    table("mre_attend_dlogits", ATTEND_DLOGITS, g, [
+        ("host pointers", {}), ("host pointers, no weight", dict(weight=None)), ("host pointers, bf16", dict(dtype=1)),
+        ("n == 0", dict(n=0)), *aranges,
+        ("null logits", dict(logits=None)), ("null target", dict(target=None)), ("null lse", dict(lse=None)),
+        ("float32 logits misaligned", dict(logits=alogits + 2)), ("bf16 logits misaligned", dict(dtype=1, logits=alogits + 1)),
+        ("target misaligned", dict(target=target + 2)), ("lse misaligned", dict(lse=lse + 2)),
+        ("weight misaligned", dict(weight=weight + 1)), ("null g", dict(g=None)), ("float32 g misaligned", dict(g=agrad + 2)),
+        ("bf16 g misaligned", dict(dtype=1, g=agrad + 1)), ("g on logits", dict(g=alogits)), ("g on weight", dict(g=weight)),
+        ("two: dtype 2 and null lse", dict(dtype=2, lse=None)), ("two: null target and logits misaligned", dict(target=None, logits=alogits + 2)),
+        ("two: logits misaligned and target misaligned", dict(logits=alogits + 2, target=target + 2)),
+        ("two: target misaligned and weight misaligned", dict(target=target + 2, weight=weight + 1)),
+        ("two: lse misaligned and null g", dict(lse=lse + 2, g=None)), ("two: g misaligned and g on logits", dict(g=alogits + 2)),
+        ("n == 0 and null g", dict(n=0, g=None)), ("n == 0 and g on logits", dict(n=0, g=alogits)),
+    ])
+
+    nbytes = C.cast(slot(45), C.POINTER(C.c_size_t))
+    table("mre_attend_workspace", ATTEND_WORKSPACE, dict(**shape, bytes=nbytes), [
+        ("good", {}), ("n == 0", dict(n=0)), ("null bytes", dict(bytes=None)), ("n < 0", dict(n=-1)),
+        ("rotations 0", dict(rotations=0)), ("rotations 65", dict(rotations=65)), ("h 0", dict(h=0)), ("w 4097", dict(w=4097)),
+        ("two: null bytes and n < 0", dict(bytes=None, n=-1)), ("two: rotations 65 and h 0", dict(rotations=65, h=0)),
+    ])
+    table("mre_correlate_grad_workspace", GRAD_WORKSPACE, dict(n=2, rotations=2, depth=2, h=8, w=8, crop=4, bytes=nbytes), [
+        ("good", {}), ("n == 0", dict(n=0)), ("null bytes", dict(bytes=None)), *ranges,
+        ("two: null bytes and crop odd", dict(bytes=None, crop=3)), ("n == 0 and depth 0", dict(n=0, depth=0)),
     ])
     assert len({c[0] for c in out}) == len(out)
     return out

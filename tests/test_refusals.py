@@ -10,7 +10,8 @@ from tests import refusal_cases
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refusals.json")
 ENTRIES = ["mre_heightmap", "mre_heightmap_views", "mre_correlate", "mre_correlate_loss", "mre_correlate_dlogits",
-           "mre_correlate_grad_scene", "mre_correlate_grad_kern", "mre_correlate_workspace"]
+           "mre_correlate_grad_scene", "mre_correlate_grad_kern", "mre_correlate_workspace", "mre_attend", "mre_attend_dlogits",
+           "mre_attend_workspace", "mre_correlate_grad_workspace"]
 
 
 @pytest.fixture(scope="module")
@@ -36,7 +37,7 @@ def test_the_table_covers_what_it_says():
         rows = [w for w in want if w[0].startswith(entry + ": ")]
         assert any(w[0].startswith(entry + ": two: ") for w in rows), entry        # wrong in two ways at once
         assert any("n == 0" in w[0] and w[1] == 0 for w in rows), entry            # n == 0 returns MRE_OK
-        if entry != "mre_correlate_workspace":                                     # (it takes no device pointer)
+        if not entry.endswith("_workspace"):                                       # (they take no device pointer)
             host = [w for w in rows if w[0].startswith(entry + ": host pointers")]
             assert host and all(w[1] == -1 and w[2].endswith("must be device pointers") for w in host), entry
         assert all(w[1] == 0 or w[2].startswith(entry + ": ") for w in rows), entry
