@@ -1,6 +1,6 @@
 // mre_api.cpp -- the entry points of the C ABI (include/mre.h) that work on an mre_env handle; those that take a stream
-// and no handle are mre_stream_api.cpp's.  Owns the device buffers and the HIP stream of a batch of environments,
-// uploads the fp32 DevModel that mre_model.cpp builds from the model blob, and
+// and no handle are mre_stream_api.cpp's.  Creates and destroys the handle (what it owns is recorded by mre_env.h's four
+// functions), uploads the fp32 DevModel that mre_model.cpp builds from the model blob, stages host arrays and
 // enqueues kernels; how stepping launches are issued is mre_sched.cpp's.  No torch types; plain pointers and sizes only.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +24,88 @@ int mre::fail(int code, const std::string& msg) {
   return code;
 }
 
+// The opening of every entry that works on a handle.  A NULL handle, or a NULL among the pointers the entry requires
+// (`args_ok`), is refused with the entry's text before any HIP call; then the handle's device is selected -- the HIP
+// current device is per thread, and everything an entry allocates, copies or launches below relies on it -- and, with
+// DRAIN_FIRST, what the stepping calls left pending is completed (mre::drain: the call counts as one that touches the
+// state).  The stepping calls themselves and mre_wait_stream leave it pending; mre_num_envs, mre_stream and
+// mre_get_solver read one member, make no HIP call and do not open with it.
+enum Pending { LEAVE_PENDING, DRAIN_FIRST };
+#define ENTER(e, args_ok, text, pending)                        \
+  do {                                                          \
+    if (!(e) || !(args_ok)) return fail(MRE_ERR_ARG, text);     \
+    HIPCHK(hipSetDevice((e)->device));                          \
+    if ((pending) == DRAIN_FIRST) DRAIN(e);                     \
+  } while (0)
+
+// ------------------------------------------------------------------- staging
+// The caller's array to the device, enqueued on the handle's stream: it is borrowed for the call (include/mre.h).
+static int copy_in(mre_env* e, void* dst, const void* src, size_t n) {
+  HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDefault, e->stream));
+  return MRE_OK;
+}
+static int copy_out(mre_env* e, void* dst, const void* src, size_t n) {
+  HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDefault, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return MRE_OK;
+}
+// Host staging in vectors of this file's own.  A host vector handed to an asynchronous copy must outlive it: fetch and
+// store return only when the handle's stream has run the copy, so the vector may change or die as soon as they have
+// returned, and no call site reasons about that again.  src / dst: a device array of the handle or an array of the
+// caller (host or device).
+template <class T> static int fetch(mre_env* e, const void* src, size_t count, std::vector<T>& h) {
+  h.resize(count);
+  return copy_out(e, h.data(), src, count * sizeof(T));
+}
+template <class T> static int store(mre_env* e, void* dst, const std::vector<T>& h) {
+  return copy_out(e, dst, h.data(), h.size() * sizeof(T));
+}
+// Read dev[N][row], let edit(i, row i) change the rows of the envs `pick` names, write all of it back.
+template <class T, class Pick, class Edit> static int patch_rows(mre_env* e, T* dev, size_t row, Pick pick, Edit edit) {
+  std::vector<T> h;
+  int rc = fetch(e, dev, (size_t)e->N * row, h);
+  if (rc) return rc;
+  for (size_t i = 0; i < (size_t)e->N; i++) if (pick(i)) edit(i, &h[i * row]);
+  return store(e, dev, h);
+}
+// the state rows with their low-order words: qpos [N][NQP], qvel [N][NVP], qfine [N][QFINE_ROW]
+static int read_state(mre_env* e, std::vector<float>& hq, std::vector<float>& hv, std::vector<float>& hf) {
+  const size_t N = (size_t)e->N;
+  int rc = fetch(e, e->qpos, N * NQP, hq);
+  if (!rc) rc = fetch(e, e->qvel, N * NVP, hv);
+  if (!rc) rc = fetch(e, e->qfine, N * QFINE_ROW, hf);
+  return rc;
+}
+// returns device mask pointer or nullptr
+static int stage_mask(mre_env* e, const uint8_t* mask, const uint8_t** dmask) {
+  *dmask = nullptr;
+  if (!mask) return MRE_OK;
+  int rc = copy_in(e, e->mask, mask, (size_t)e->N);
+  *dmask = e->mask;
+  return rc;
+}
+
+static void fill_args(mre_env* e, StepArgs& a) {
+  memset(&a, 0, sizeof(a));
+  a.M = e->dM; a.N = e->N; a.seq_stride = e->N;
+  a.qpos = e->qpos; a.qvel = e->qvel; a.qacc_ws = e->qacc_ws; a.ctrl = e->ctrl; a.qfine = e->qfine;
+  a.nprops = e->nprops; a.prop_size = e->prop_size;
+  a.control_steps = 1; a.mode = CTRL_HELD; a.flags = e->base_flags;
+  a.osc = e->d_osc_env ? e->d_osc_env : e->d_osc; a.osc_stride = e->d_osc_env ? 1 : 0;
+  a.osc_target = e->osc_target; a.grip_closed = e->grip_closed;
+  a.sites = e->sites; a.status = e->status; a.stats = e->stats; a.nstep = e->nstep;
+  a.env_order = e->use_order ? e->order : (e->have_auto_order ? e->auto_order : nullptr);
+  a.trace = e->trace; a.trace_nenv = e->trace_nenv; a.trace_max = e->trace_max; a.trace_base = e->trace_pos;
+}
+// A launch of the step kernel that steps nothing -- kinematics, and whatever the flags and outputs of `a` (from fill_args,
+// plus what the caller set) ask for on the current state -- on the handle's stream, outside the scheduler and untraced.
+static int zero_step(mre_env* e, StepArgs& a) {
+  a.nsteps = 0; a.trace = nullptr;
+  step_kernels(e->solver).step(&a, e->stream);
+  HIPCHK(hipGetLastError());
+  return MRE_OK;
+}
+
 // ------------------------------------------------------------------- lifecycle
 extern "C" const char* mre_last_error(void) { return g_err.c_str(); }
 
@@ -31,45 +113,44 @@ extern "C" const char* mre_last_error(void) { return g_err.c_str(); }
 static int create_buffers(mre_env* e, int num_envs, int device_id) {
   e->N = num_envs;
   e->device = device_id;
-  HIPCHK(hipSetDevice(device_id));
-  HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
   const size_t N = (size_t)num_envs;
-  HIPCHK(hipMalloc(&e->dM, sizeof(DevModel)));
+  const unsigned mapped = hipHostMallocMapped | hipHostMallocCoherent;
+  int rc = new_stream(e, &e->stream);
+  auto dev = [&](auto** p, size_t bytes) { if (!rc) rc = alloc_dev(e, p, bytes); };
+  // (the sv_* are the rows a guarded launch copies aside, StepArgs::sv_*.  The first copy on the null stream and the first
+  // memsets on the handle's stream come BEFORE stream2 and sched_create's streams exist, as they always have: with all of
+  // them moved behind sched_create the per-tick launches of bench.py ran at 21.7 instead of 23.4 M env-steps/s in three
+  // alternating runs, and at 23.4 again with them back here -- profiles/README.md, handle_late_memsets_bench_*.json)
+  dev(&e->dM, sizeof(DevModel));
+  if (rc) return rc;
   HIPCHK(hipMemcpy(e->dM, &e->hM, sizeof(DevModel), hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&e->qpos, N * NQP * 4)); HIPCHK(hipMalloc(&e->qvel, N * NVP * 4));
-  HIPCHK(hipMalloc(&e->qacc_ws, N * NVP * 4)); HIPCHK(hipMalloc(&e->ctrl, N * NU * 4));
-  HIPCHK(hipMalloc(&e->qfine, N * QFINE_ROW * 4)); HIPCHK(hipMalloc(&e->sv_qfine, N * QFINE_ROW * 4));
-  HIPCHK(hipMemsetAsync(e->qfine, 0, N * QFINE_ROW * 4, e->stream));
-  HIPCHK(hipMalloc(&e->nstep, N * 4)); HIPCHK(hipMalloc(&e->sv_nstep, N * 4));
-  HIPCHK(hipMemsetAsync(e->nstep, 0, N * 4, e->stream));
-  HIPCHK(hipMalloc(&e->nprops, N * 4)); HIPCHK(hipMalloc(&e->prop_size, N * NPROP * 3 * 4));
-  HIPCHK(hipMalloc(&e->osc_target, N * 16 * 4)); HIPCHK(hipMalloc(&e->grip_closed, N));
-  HIPCHK(hipMalloc(&e->converged, N)); HIPCHK(hipMalloc(&e->mask, N));
-  HIPCHK(hipMalloc(&e->sites, N * 16 * 4));
-  HIPCHK(hipMalloc(&e->status, N * 4)); HIPCHK(hipMalloc(&e->stats, N * 4 * 4));
-  HIPCHK(hipMalloc(&e->order, N * 4)); HIPCHK(hipMalloc(&e->auto_order, N * 4));
-  HIPCHK(hipHostMalloc((void**)&e->h_auto_order, N * 4, hipHostMallocDefault));
-  HIPCHK(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
-  HIPCHK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-  HIPCHK(hipMalloc(&e->d_large, N)); HIPCHK(hipMalloc(&e->mask_r, N));
-  HIPCHK(hipMalloc(&e->sv_qpos, N * NQP * 4)); HIPCHK(hipMalloc(&e->sv_qvel, N * NVP * 4));
-  HIPCHK(hipMalloc(&e->sv_qacc_ws, N * NVP * 4)); HIPCHK(hipMalloc(&e->sv_ctrl, N * NU * 4));
-  HIPCHK(hipMalloc(&e->sv_status, N * 4));
-  HIPCHK(hipMalloc(&e->sv_converged, N));
-  HIPCHK(hipHostMalloc((void**)&e->h_launch_info, mre_env::RING * N * 16, hipHostMallocMapped | hipHostMallocCoherent));
-  HIPCHK(hipHostGetDevicePointer((void**)&e->d_launch_info, e->h_launch_info, 0));
+  dev(&e->qpos, N * NQP * 4); dev(&e->qvel, N * NVP * 4); dev(&e->qacc_ws, N * NVP * 4); dev(&e->ctrl, N * NU * 4);
+  dev(&e->qfine, N * QFINE_ROW * 4); dev(&e->sv_qfine, N * QFINE_ROW * 4); dev(&e->nstep, N * 4); dev(&e->sv_nstep, N * 4);
+  if (rc) return rc;
+  // (device memsets are enqueued on the handle's stream: a hipMemset on the null stream is
+  // asynchronous and is NOT ordered against a non-blocking stream)
+  HIPCHK(hipMemsetAsync(e->qfine, 0, N * QFINE_ROW * 4, e->stream)); HIPCHK(hipMemsetAsync(e->nstep, 0, N * 4, e->stream));
+  dev(&e->nprops, N * 4); dev(&e->prop_size, N * NPROP * 3 * 4); dev(&e->osc_target, N * 16 * 4); dev(&e->grip_closed, N);
+  dev(&e->converged, N); dev(&e->mask, N); dev(&e->sites, N * 16 * 4); dev(&e->status, N * 4); dev(&e->stats, N * 4 * 4);
+  dev(&e->order, N * 4); dev(&e->auto_order, N * 4);
+  if (!rc) rc = alloc_host(e, &e->h_auto_order, N * 4, hipHostMallocDefault);
+  if (!rc) rc = new_stream(e, &e->stream2);
+  if (!rc) rc = new_event(e, &e->ev_fork);
+  if (!rc) rc = new_event(e, &e->ev_join);
+  dev(&e->d_large, N); dev(&e->mask_r, N);
+  dev(&e->sv_qpos, N * NQP * 4); dev(&e->sv_qvel, N * NVP * 4); dev(&e->sv_qacc_ws, N * NVP * 4); dev(&e->sv_ctrl, N * NU * 4);
+  dev(&e->sv_status, N * 4); dev(&e->sv_converged, N);
+  if (!rc) rc = alloc_host(e, &e->h_launch_info, mre_env::RING * N * 16, mapped, &e->d_launch_info);
+  if (!rc) rc = alloc_host(e, &e->h_info_last, N * 16, hipHostMallocDefault);
+  if (!rc) rc = alloc_host(e, &e->h_large_stage, mre_env::NSTAGE * N, mapped, &e->d_large_stage);
+  dev(&e->d_pending, N);
+  if (rc) return rc;
+  HIPCHK(hipMemsetAsync(e->d_pending, 0, N, e->stream)); HIPCHK(hipMemsetAsync(e->d_large, 0, N, e->stream));
   memset(e->h_launch_info, 0xFF, mre_env::RING * N * 16);
-  HIPCHK(hipHostMalloc((void**)&e->h_info_last, N * 16, hipHostMallocDefault));
   memset(e->h_info_last, 0xFF, N * 16);   // -1: no launch yet
-  HIPCHK(hipHostMalloc((void**)&e->h_large_stage, mre_env::NSTAGE * N, hipHostMallocMapped | hipHostMallocCoherent));
-  HIPCHK(hipHostGetDevicePointer((void**)&e->d_large_stage, e->h_large_stage, 0));
   memset(e->h_large_stage, 0, mre_env::NSTAGE * N);
-  HIPCHK(hipMalloc(&e->d_pending, N));
-  HIPCHK(hipMemsetAsync(e->d_pending, 0, N, e->stream));
-  HIPCHK(hipMemsetAsync(e->d_large, 0, N, e->stream));
   e->h_large.assign(N, 0); e->h_rerun.assign(N, 0);
-  { int rc = sched_create(e); if (rc) return rc; }
+  if ((rc = sched_create(e))) return rc;
   if (const char* fb = getenv("MRE_NO_FALLBACK")) e->fallback = atoi(fb) == 0;  // profiling knob only
   if (const char* ng = getenv("MRE_NARROW_GENERIC")) e->base_flags = atoi(ng) != 0 ? F_CLIP_ALWAYS : 0u;  // comparison knob only
   if (const char* ng = getenv("MRE_NEWTON_GENERIC")) e->base_flags |= atoi(ng) != 0 ? F_NW_ALL_TILES : 0u;  // likewise: every Hessian tile
@@ -90,12 +171,10 @@ static int create_buffers(mre_env* e, int num_envs, int device_id) {
   // OSC defaults (osc.yaml:5-22)
   e->osc = OscConfig{350.f, 20.f, 500.f, 100.f, 200.f, 30.f, {0.f, -0.785f, 0.f, -2.356f, 0.f, 1.571f, 0.785f},
                      5e-3f, 68e-3f, 0};
-  HIPCHK(hipMalloc(&e->d_osc, sizeof(OscConfig)));
+  if ((rc = alloc_dev(e, &e->d_osc, sizeof(OscConfig)))) return rc;
   HIPCHK(hipMemcpy(e->d_osc, &e->osc, sizeof(OscConfig), hipMemcpyHostToDevice));
-  // (device memsets above are enqueued on the handle's stream: a hipMemset on the null stream is
-  // asynchronous and is NOT ordered against a non-blocking stream)
   HIPCHK(hipStreamSynchronize(e->stream));
-  int rc = mre_reset(e, nullptr);
+  rc = mre_reset(e, nullptr);
   if (rc != MRE_OK) return rc;
   return mre_sync(e);
 }
@@ -107,7 +186,6 @@ extern "C" int mre_create(const void* blob, size_t nbytes, int num_envs, int dev
   const std::string err = build_model(blob, nbytes, e->hM, e->solver);
   if (!err.empty()) { delete e; return fail(MRE_ERR_MODEL, err); }
   if (const char* it = getenv("MRE_DEBUG_ITERS")) e->hM.opt_rec.iterations = atoi(it);  // profiling knob only
-  int rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     delete e;
@@ -117,7 +195,7 @@ extern "C" int mre_create(const void* blob, size_t nbytes, int num_envs, int dev
     delete e;
     return fail(MRE_ERR_ARG, "mre_create: device_id out of range");
   }
-  rc = create_buffers(e, num_envs, device_id);
+  const int rc = create_buffers(e, num_envs, device_id);
   if (rc != MRE_OK) {
     const std::string msg = g_err;  // mre_destroy must not clobber the reason
     mre_destroy(e);
@@ -128,6 +206,8 @@ extern "C" int mre_create(const void* blob, size_t nbytes, int num_envs, int dev
   return MRE_OK;
 }
 
+// Drain, let every stream of the handle finish, then release what the handle recorded: device memory, host memory,
+// events, streams.
 extern "C" int mre_destroy(mre_env* e) {
   if (!e) return MRE_OK;
   (void)hipSetDevice(e->device);
@@ -135,29 +215,11 @@ extern "C" int mre_destroy(mre_env* e) {
   if (getenv("MRE_DEBUG_TIMING") && e->dbg_calls > 0)
     fprintf(stderr, "mre: %ld pipelined calls, %.1f us per call in the library, of which %.1f us waiting for launch info\n",
             e->dbg_calls, 1e6 * e->dbg_call_s / e->dbg_calls, 1e6 * e->dbg_wait_s / e->dbg_calls);
-  sched_destroy(e);
-  for (float* p : e->seq_copy) if (p) (void)hipFree(p);
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
-  if (e->stream2) (void)hipStreamSynchronize(e->stream2);
-  void* ptrs[] = {e->dM, e->qpos, e->qvel, e->qacc_ws, e->ctrl, e->nprops, e->prop_size, e->osc_target,
-                  e->grip_closed, e->converged, e->mask, e->sites, e->status, e->stats, e->d_osc, e->d_osc_env, e->order,
-                  e->geoms, e->prop_rgb, e->bg_depth, e->bg_rgb, e->bg_seg,
-                  e->d_large, e->mask_r, e->qfine, e->sv_qfine, e->nstep, e->sv_nstep, e->sv_qpos, e->sv_qvel, e->sv_qacc_ws, e->sv_ctrl,
-                  e->sv_status, e->auto_order, e->sv_converged, e->contacts, e->contacts_full, e->settle_steps,
-                  e->d_env_ids, e->ps_attempts, e->ps_prop, e->ps_tick, e->ps_which, e->ps_bounds, e->ps_pose, e->ps_zones,
-                  e->ps_pick};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (e->h_launch_info) (void)hipHostFree(e->h_launch_info);
-  if (e->h_info_last) (void)hipHostFree(e->h_info_last);
-  if (e->h_large_stage) (void)hipHostFree(e->h_large_stage);
-  if (e->d_pending) (void)hipFree(e->d_pending);
-  if (e->h_auto_order) (void)hipHostFree(e->h_auto_order);
-  for (auto& pr : e->events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-  if (e->ev_order) (void)hipEventDestroy(e->ev_order);
-  if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-  if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-  if (e->stream2) (void)hipStreamDestroy(e->stream2);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
+  for (hipStream_t s : e->owned.streams) (void)hipStreamSynchronize(s);
+  for (void* p : e->owned.dev) (void)hipFree(p);
+  for (void* p : e->owned.host) (void)hipHostFree(p);
+  for (hipEvent_t ev : e->owned.events) (void)hipEventDestroy(ev);
+  for (hipStream_t s : e->owned.streams) (void)hipStreamDestroy(s);
   delete e;
   return MRE_OK;
 }
@@ -165,45 +227,20 @@ extern "C" int mre_destroy(mre_env* e) {
 extern "C" int mre_num_envs(const mre_env* e) { return e ? e->N : 0; }
 extern "C" void* mre_stream(mre_env* e) { return e ? (void*)e->stream : nullptr; }
 extern "C" int mre_sync(mre_env* e) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  HIPCHK(hipSetDevice(e->device));
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   HIPCHK(hipStreamSynchronize(e->stream));
   return MRE_OK;
-}
-
-static int copy_in(mre_env* e, void* dst, const void* src, size_t n) {
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDefault, e->stream));
-  return MRE_OK;
-}
-static int copy_out(mre_env* e, void* dst, const void* src, size_t n) {
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDefault, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return MRE_OK;
-}
-// returns device mask pointer or nullptr
-static int stage_mask(mre_env* e, const uint8_t* mask, const uint8_t** dmask) {
-  *dmask = nullptr;
-  if (!mask) return MRE_OK;
-  int rc = copy_in(e, e->mask, mask, (size_t)e->N);
-  *dmask = e->mask;
-  return rc;
 }
 
 extern "C" int mre_set_props(mre_env* e, const int32_t* nprops, const float* prop_half_size) {
-  if (!e || !nprops || !prop_half_size) return fail(MRE_ERR_ARG, "mre_set_props: null");
-  DRAIN(e);
+  ENTER(e, nprops && prop_half_size, "mre_set_props: null", DRAIN_FIRST);
   int rc = copy_in(e, e->nprops, nprops, (size_t)e->N * 4);
   if (rc) return rc;
   return copy_in(e, e->prop_size, prop_half_size, (size_t)e->N * NPROP * 3 * 4);
 }
 
 extern "C" int mre_reset(mre_env* e, const uint8_t* mask) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
-  HIPCHK(hipSetDevice(e->device));
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   const uint8_t* dmask;
   int rc = stage_mask(e, mask, &dmask);
   if (rc) return rc;
@@ -213,29 +250,19 @@ extern "C" int mre_reset(mre_env* e, const uint8_t* mask) {
   // a reset env starts on the compact kernel again (the mask may be a device pointer: read a host copy)
   bool changed = false;
   std::vector<uint8_t> hmask;
-  if (mask) {
-    hmask.resize((size_t)e->N);
-    rc = copy_out(e, hmask.data(), dmask, (size_t)e->N);
-    if (rc) return rc;
-  }
+  if (mask && (rc = fetch(e, dmask, (size_t)e->N, hmask))) return rc;
   for (int i = 0; i < e->N; i++)
     if (!e->large_only && e->h_large[i] && (!mask || hmask[i])) { e->h_large[i] = 0; e->n_large--; changed = true; }
-  if (changed) {
-    HIPCHK(hipMemcpyAsync(e->d_large, e->h_large.data(), (size_t)e->N, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-  }
-  return MRE_OK;
+  return changed ? store(e, e->d_large, e->h_large) : MRE_OK;
 }
 
 // ---- batched overhead camera (csrc/mre_render.hip)
-static void fill_args(mre_env* e, StepArgs& a);
-
 extern "C" int mre_set_render_colours(mre_env* e, const uint8_t* prop_rgb, const float* geom_rgb) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   const size_t N = (size_t)e->N;
   if (!e->prop_rgb) {
-    HIPCHK(hipMalloc(&e->prop_rgb, N * NPROP * 3));
+    int rc = alloc_dev(e, &e->prop_rgb, N * NPROP * 3);
+    if (rc) return rc;
     HIPCHK(hipMemsetAsync(e->prop_rgb, 128, N * NPROP * 3, e->stream));
     for (int g = 0; g < NG; g++) for (int k = 0; k < 3; k++) e->geom_rgb[g][k] = 0.5f;
   }
@@ -245,11 +272,7 @@ extern "C" int mre_set_render_colours(mre_env* e, const uint8_t* prop_rgb, const
   return MRE_OK;
 }
 
-extern "C" int mre_render(mre_env* e, const float* cam_pos, const float* cam_mat, float fovy_deg, int height, int width,
-                          uint8_t* rgb, float* depth, uint8_t* seg, const uint8_t* mask) {
-  if (!e || !cam_pos || !cam_mat) return fail(MRE_ERR_ARG, "mre_render: null argument");
-  DRAIN(e);
-  HIPCHK(hipSetDevice(e->device));
+static int render_check(float fovy_deg, int height, int width, const uint8_t* rgb, const float* depth, const uint8_t* seg) {
   if (height <= 0 || width <= 0 || (width & 3) != 0 || width / 4 > 320 || !(fovy_deg > 0.f && fovy_deg < 180.f))
     return fail(MRE_ERR_ARG, "mre_render: width must be a multiple of 4 (<= 1280), 0 < fovy < 180");
   if ((rgb && !is_device_ptr(rgb)) || (depth && !is_device_ptr(depth)) || (seg && !is_device_ptr(seg)))
@@ -257,24 +280,21 @@ extern "C" int mre_render(mre_env* e, const float* cam_pos, const float* cam_mat
   if (depth && ((uintptr_t)depth & 15)) return fail(MRE_ERR_ARG, "mre_render: depth must be 16-byte aligned");
   if ((rgb && ((uintptr_t)rgb & 3)) || (seg && ((uintptr_t)seg & 3)))
     return fail(MRE_ERR_ARG, "mre_render: rgb / seg must be 4-byte aligned");
-  int rc = MRE_OK;
-  if (!e->prop_rgb) { rc = mre_set_render_colours(e, nullptr, nullptr); if (rc) return rc; }
-  const size_t N = (size_t)e->N;
-  if (!e->geoms) HIPCHK(hipMalloc(&e->geoms, N * NG * 16 * 4));
-  const uint8_t* dmask;
-  rc = stage_mask(e, mask, &dmask);
-  if (rc) return rc;
-  // geometry of the current state: a zero-step launch of the step kernel (kinematics + export)
-  StepArgs a;
-  fill_args(e, a);
-  a.nsteps = 0; a.trace = nullptr; a.env_order = nullptr; a.env_mask = dmask; a.geoms = e->geoms;
-  hipEvent_t e0, e1;   // same event bracket as launch_step: tools/bench_render.py times the camera with it
-  rc = profile_events(e, &e0, &e1);
-  if (rc) return rc;
-  if (e0) HIPCHK(hipEventRecord(e0, e->stream));
-  step_kernels(e->solver).step(&a, e->stream);
-  HIPCHK(hipGetLastError());
-  RenderArgs r;
+  return MRE_OK;
+}
+// row groups per env of a render launch
+static int render_row_groups(int height, int width) {
+  const int rows_per_iter = 320 / (width / 4);
+  int row_groups = (height + rows_per_iter - 1) / rows_per_iter;
+  int cap = 8;  // 8 row groups per env: the per-workgroup geom set-up is amortised over 30 row pairs
+  if (const char* rg = getenv("MRE_RENDER_ROW_GROUPS")) cap = atoi(rg);  // tuning knob
+  if (cap < 1) cap = 1;
+  return row_groups > cap ? cap : row_groups;
+}
+
+// what of the scene does not depend on the state: image size, camera, the arena's lights, checker and clip constants
+static void render_scene(RenderArgs& r, const mre_env* e, const float* cam_pos, const float* cam_mat, float fovy_deg,
+                         int height, int width) {
   memset(&r, 0, sizeof(r));
   r.N = e->N; r.height = height; r.width = width;
   r.geoms = e->geoms; r.nprops = e->nprops; r.prop_rgb = e->prop_rgb;
@@ -290,50 +310,74 @@ extern "C" int mre_render(mre_env* e, const float* cam_pos, const float* cam_mat
   for (int k = 0; k < 3; k++) { r.checker[0][k] = c0[k]; r.checker[1][k] = c1[k]; }
   r.checker_size = 0.1f;
   r.zfar = 100.f;
+}
+
+// The static geoms (ground plane, table: geoms 0 and 1, fixed to the world) look the same in every
+// env and every frame of a camera: their image is rendered once per camera and every frame then
+// starts from it and composites the moving geoms (robot hulls, cubes) on top.
+constexpr int N_STATIC = 2;
+// Makes the cached image that of this camera and image size (r: the frame's scene, a: the frame's geometry launch).
+static int refresh_background(mre_env* e, const StepArgs& a, const RenderArgs& r, float fovy_deg, int row_groups) {
+  float key[16] = {r.cam_pos[0], r.cam_pos[1], r.cam_pos[2], r.cam_mat[0], r.cam_mat[1], r.cam_mat[2], r.cam_mat[3], r.cam_mat[4],
+                   r.cam_mat[5], r.cam_mat[6], r.cam_mat[7], r.cam_mat[8], fovy_deg, 0.f, 0.f, 0.f};
+  if (e->bg_valid && e->bg_h == r.height && e->bg_w == r.width && memcmp(key, e->bg_key, sizeof(key)) == 0) return MRE_OK;
+  if (e->bg_h != r.height || e->bg_w != r.width) {
+    e->bg_h = e->bg_w = 0; e->bg_valid = false;   // (until all three exist again: a failure leaves no size beside a null)
+    release(e, &e->bg_depth); release(e, &e->bg_rgb); release(e, &e->bg_seg);
+    const size_t px = (size_t)r.height * r.width;
+    int rc;
+    if ((rc = alloc_dev(e, &e->bg_depth, px * 4)) || (rc = alloc_dev(e, &e->bg_rgb, px * 3)) || (rc = alloc_dev(e, &e->bg_seg, px)))
+      return rc;
+    e->bg_h = r.height; e->bg_w = r.width;
+  }
+  // the static geoms' poses do not depend on the env: cast them for env 0 (exported by the frame's launch even
+  // when env 0 is masked out? no -- so export it unmasked once)
+  if (a.env_mask) {
+    StepArgs a0 = a;
+    a0.env_mask = nullptr;
+    int rc = zero_step(e, a0);
+    if (rc) return rc;
+  }
+  RenderArgs b = r;
+  b.N = 1; b.env_mask = nullptr; b.g0 = 0; b.g1 = N_STATIC;
+  b.rgb = e->bg_rgb; b.depth = e->bg_depth; b.seg = e->bg_seg;
+  mre_launch_render(&b, row_groups, e->stream);
+  HIPCHK(hipGetLastError());
+  memcpy(e->bg_key, key, sizeof(key));
+  e->bg_valid = true;
+  return MRE_OK;
+}
+
+extern "C" int mre_render(mre_env* e, const float* cam_pos, const float* cam_mat, float fovy_deg, int height, int width,
+                          uint8_t* rgb, float* depth, uint8_t* seg, const uint8_t* mask) {
+  ENTER(e, cam_pos && cam_mat, "mre_render: null argument", DRAIN_FIRST);
+  int rc = render_check(fovy_deg, height, width, rgb, depth, seg);
+  if (rc) return rc;
+  if (!e->prop_rgb) { rc = mre_set_render_colours(e, nullptr, nullptr); if (rc) return rc; }
+  if ((rc = alloc_dev(e, &e->geoms, (size_t)e->N * NG * 16 * 4))) return rc;
+  const uint8_t* dmask;
+  rc = stage_mask(e, mask, &dmask);
+  if (rc) return rc;
+  // geometry of the current state: a zero-step launch of the step kernel (kinematics + export)
+  StepArgs a;
+  fill_args(e, a);
+  a.env_order = nullptr; a.env_mask = dmask; a.geoms = e->geoms;
+  hipEvent_t e0, e1;   // same event bracket as launch_step: tools/bench_render.py times the camera with it
+  rc = profile_events(e, &e0, &e1);
+  if (rc) return rc;
+  if (e0) HIPCHK(hipEventRecord(e0, e->stream));
+  if ((rc = zero_step(e, a))) return rc;
+  RenderArgs r;
+  render_scene(r, e, cam_pos, cam_mat, fovy_deg, height, width);
   r.rgb = rgb; r.depth = depth; r.seg = seg; r.env_mask = dmask;
-  const int rows_per_iter = 320 / (width / 4);
-  int row_groups = (height + rows_per_iter - 1) / rows_per_iter;
-  int cap = 8;  // 8 row groups per env: the per-workgroup geom set-up is amortised over 30 row pairs
-  if (const char* rg = getenv("MRE_RENDER_ROW_GROUPS")) cap = atoi(rg);  // tuning knob
-  if (cap < 1) cap = 1;
-  if (row_groups > cap) row_groups = cap;
-  // The static geoms (ground plane, table: geoms 0 and 1, fixed to the world) look the same in every
-  // env and every frame of a camera: their image is rendered once per camera and every frame then
-  // starts from it and composites the moving geoms (robot hulls, cubes) on top.
-  constexpr int N_STATIC = 2;
+  const int row_groups = render_row_groups(height, width);
   bool use_bg = true;
   if (const char* nb = getenv("MRE_RENDER_NO_BACKGROUND")) use_bg = atoi(nb) == 0;  // diagnostic
+  r.g0 = 0; r.g1 = NG;
   if (use_bg) {
-    float key[16] = {cam_pos[0], cam_pos[1], cam_pos[2], cam_mat[0], cam_mat[1], cam_mat[2], cam_mat[3], cam_mat[4],
-                     cam_mat[5], cam_mat[6], cam_mat[7], cam_mat[8], fovy_deg, 0.f, 0.f, 0.f};
-    if (!e->bg_valid || e->bg_h != height || e->bg_w != width || memcmp(key, e->bg_key, sizeof(key)) != 0) {
-      if (e->bg_h != height || e->bg_w != width) {
-        for (void* p : {(void*)e->bg_depth, (void*)e->bg_rgb, (void*)e->bg_seg}) if (p) (void)hipFree(p);
-        e->bg_depth = nullptr; e->bg_rgb = nullptr; e->bg_seg = nullptr;
-        const size_t px = (size_t)height * width;
-        HIPCHK(hipMalloc(&e->bg_depth, px * 4)); HIPCHK(hipMalloc(&e->bg_rgb, px * 3)); HIPCHK(hipMalloc(&e->bg_seg, px));
-        e->bg_h = height; e->bg_w = width;
-      }
-      // the static geoms' poses do not depend on the env: cast them for env 0 (exported above even
-      // when env 0 is masked out? no -- so export it unmasked once)
-      if (dmask) {
-        StepArgs a0 = a;
-        a0.env_mask = nullptr;
-        step_kernels(e->solver).step(&a0, e->stream);
-        HIPCHK(hipGetLastError());
-      }
-      RenderArgs b = r;
-      b.N = 1; b.env_mask = nullptr; b.g0 = 0; b.g1 = N_STATIC;
-      b.rgb = e->bg_rgb; b.depth = e->bg_depth; b.seg = e->bg_seg;
-      mre_launch_render(&b, row_groups, e->stream);
-      HIPCHK(hipGetLastError());
-      memcpy(e->bg_key, key, sizeof(key));
-      e->bg_valid = true;
-    }
-    r.g0 = N_STATIC; r.g1 = NG;
+    if ((rc = refresh_background(e, a, r, fovy_deg, row_groups))) return rc;
+    r.g0 = N_STATIC;
     r.bg_depth = e->bg_depth; r.bg_rgb = e->bg_rgb; r.bg_seg = e->bg_seg;
-  } else {
-    r.g0 = 0; r.g1 = NG;
   }
   mre_launch_render(&r, row_groups, e->stream);
   HIPCHK(hipGetLastError());
@@ -342,8 +386,7 @@ extern "C" int mre_render(mre_env* e, const float* cam_pos, const float* cam_mat
 }
 
 extern "C" int mre_set_fallback(mre_env* e, int mode) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   if (mode < 0 || mode > 2) return fail(MRE_ERR_ARG, "mre_set_fallback: mode is 0 (compact only), 1 (fallback) or 2 (large only)");
   e->fallback = mode != 0;
   e->large_only = mode == 2;
@@ -357,26 +400,23 @@ extern "C" int mre_set_fallback(mre_env* e, int mode) {
 }
 
 extern "C" int mre_wait_stream(mre_env* e, void* stream) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  HIPCHK(hipSetDevice(e->device));
-  if (!e->ev_order) HIPCHK(hipEventCreateWithFlags(&e->ev_order, hipEventDisableTiming));
+  ENTER(e, true, "null handle", LEAVE_PENDING);
+  if (!e->ev_order) { int rc = new_event(e, &e->ev_order); if (rc) return rc; }
   HIPCHK(hipEventRecord(e->ev_order, (hipStream_t)stream));
   HIPCHK(hipStreamWaitEvent(e->stream, e->ev_order, 0));
   return MRE_OK;
 }
 
 extern "C" int mre_set_solver(mre_env* e, int solver) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   if (solver != MRE_SOLVER_PGS && solver != MRE_SOLVER_NEWTON)
     return fail(MRE_ERR_ARG, "mre_set_solver: solver is 0 (PGS) or 2 (Newton)");
-  HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->stream));
   e->solver = solver;   // host-side only: it picks the kernel instantiation, no kernel reads it
   return MRE_OK;
 }
 
-extern "C" int mre_get_solver(mre_env* e) {
+extern "C" int mre_get_solver(mre_env* e) {   // (no HIP call: the return value is the solver, not a status)
   if (!e) return fail(MRE_ERR_ARG, "null handle");
   return e->solver;
 }
@@ -384,27 +424,23 @@ extern "C" int mre_get_solver(mre_env* e) {
 // {queue launches so far, waves of a queue launch, control ticks per queue launch (the library's choice), enabled,
 //  envs handed over to the large kernel inside a queue launch so far}
 extern "C" int mre_get_queue_info(mre_env* e, long long* out5) {
-  if (!e || !out5) return fail(MRE_ERR_ARG, "mre_get_queue_info: null");
-  DRAIN(e);
+  ENTER(e, out5, "mre_get_queue_info: null", DRAIN_FIRST);
   out5[0] = e->n_queue_launches; out5[1] = e->queue_waves; out5[2] = e->queue_ticks; out5[3] = e->queue_ok ? 1 : 0;
   out5[4] = e->n_handovers;
   return MRE_OK;
 }
 
 extern "C" int mre_get_fallback_stats(mre_env* e, long long* out4) {
-  if (!e || !out4) return fail(MRE_ERR_ARG, "mre_get_fallback_stats: null");
-  DRAIN(e);
+  ENTER(e, out4, "mre_get_fallback_stats: null", DRAIN_FIRST);
   out4[0] = e->n_large; out4[1] = e->n_reruns; out4[2] = e->n_promotions; out4[3] = e->n_demotions;
   return MRE_OK;
 }
 
 extern "C" int mre_set_state(mre_env* e, const float* qpos, const float* qvel) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   int rc = MRE_OK;
   if (qpos) rc = copy_in(e, e->qpos, qpos, (size_t)e->N * NQP * 4);
   if (!rc && qvel) rc = copy_in(e, e->qvel, qvel, (size_t)e->N * NVP * 4);
-  // a float32 row IS the value: the low-order words of the robot's angles / velocities start from zero
   // the float32 rows ARE the state now: the low-order words of what was overwritten go to zero (robot joints, cube poses /
   // robot and cube velocities)
   if (!rc && qpos) {
@@ -418,72 +454,60 @@ extern "C" int mre_set_state(mre_env* e, const float* qpos, const float* qvel) {
   return rc;
 }
 
-// physics.data.qpos / .qvel as the reference holds them (float64): the robot's 15 joints are carried as
-// double-float pairs on the device (StepArgs::qfine), the cubes' coordinates as float32.  Host pointers.
+// physics.data.qpos / .qvel as the reference holds them (float64): every coordinate is carried as a double-float pair
+// on the device, the float32 row entry and its low-order word (StepArgs::qfine; qfine_of_q / qfine_of_v).  Host pointers.
 extern "C" int mre_get_state_f64(mre_env* e, double* qpos, double* qvel) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   const size_t N = (size_t)e->N;
-  std::vector<float> hq(N * NQP), hv(N * NVP), hf(N * QFINE_ROW);
-  int rc = copy_out(e, hq.data(), e->qpos, N * NQP * 4);
-  if (!rc) rc = copy_out(e, hv.data(), e->qvel, N * NVP * 4);
-  if (!rc) rc = copy_out(e, hf.data(), e->qfine, N * QFINE_ROW * 4);
+  std::vector<float> hq, hv, hf;
+  int rc = read_state(e, hq, hv, hf);
   if (rc) return rc;
   for (size_t i = 0; i < N; i++) {
-    if (qpos) for (int k = 0; k < NQ; k++)
-      qpos[i * NQ + k] = (double)hq[i * NQP + k] + (double)hf[i * QFINE_ROW + (k < NRV ? k : QFINE_CUBE_Q + (k - NRV))];
-    if (qvel) for (int k = 0; k < NV; k++)
-      qvel[i * NV + k] = (double)hv[i * NVP + k] + (double)hf[i * QFINE_ROW + (k < NRV ? QFINE / 2 + k : QFINE_CUBE_V + (k - NRV))];
+    if (qpos) for (int k = 0; k < NQ; k++) qpos[i * NQ + k] = (double)hq[i * NQP + k] + (double)hf[i * QFINE_ROW + qfine_of_q(k)];
+    if (qvel) for (int k = 0; k < NV; k++) qvel[i * NV + k] = (double)hv[i * NVP + k] + (double)hf[i * QFINE_ROW + qfine_of_v(k)];
   }
   return MRE_OK;
 }
 extern "C" int mre_set_state_f64(mre_env* e, const double* qpos, const double* qvel) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   const size_t N = (size_t)e->N;
-  std::vector<float> hq(N * NQP), hv(N * NVP), hf(N * QFINE_ROW);
-  int rc = copy_out(e, hq.data(), e->qpos, N * NQP * 4);
-  if (!rc) rc = copy_out(e, hv.data(), e->qvel, N * NVP * 4);
-  if (!rc) rc = copy_out(e, hf.data(), e->qfine, N * QFINE_ROW * 4);
+  std::vector<float> hq, hv, hf;
+  int rc = read_state(e, hq, hv, hf);
   if (rc) return rc;
   for (size_t i = 0; i < N; i++) {
     if (qpos) for (int k = 0; k < NQ; k++) {
       const float hi = (float)qpos[i * NQ + k];
       hq[i * NQP + k] = hi;
-      hf[i * QFINE_ROW + (k < NRV ? k : QFINE_CUBE_Q + (k - NRV))] = (float)(qpos[i * NQ + k] - (double)hi);
+      hf[i * QFINE_ROW + qfine_of_q(k)] = (float)(qpos[i * NQ + k] - (double)hi);
     }
     if (qvel) for (int k = 0; k < NV; k++) {
       const float hi = (float)qvel[i * NV + k];
       hv[i * NVP + k] = hi;
-      hf[i * QFINE_ROW + (k < NRV ? QFINE / 2 + k : QFINE_CUBE_V + (k - NRV))] = (float)(qvel[i * NV + k] - (double)hi);
+      hf[i * QFINE_ROW + qfine_of_v(k)] = (float)(qvel[i * NV + k] - (double)hi);
     }
   }
-  rc = copy_in(e, e->qpos, hq.data(), N * NQP * 4);
-  if (!rc) rc = copy_in(e, e->qvel, hv.data(), N * NVP * 4);
-  if (!rc) rc = copy_in(e, e->qfine, hf.data(), N * QFINE_ROW * 4);
-  if (!rc) HIPCHK(hipStreamSynchronize(e->stream));   // (the staged rows must outlive the uploads)
+  rc = store(e, e->qpos, hq);
+  if (!rc) rc = store(e, e->qvel, hv);
+  if (!rc) rc = store(e, e->qfine, hf);
   return rc;
 }
 // physics.data.time (models/robot_arm.py:68-69): physics steps since the last mre_reset times the timestep, per env
 // (envs differ after PropPlacer's settle, whose exit is per env).  Host pointer [N].
 extern "C" int mre_get_time(mre_env* e, double* time) {
-  if (!e || !time) return fail(MRE_ERR_ARG, "mre_get_time: null");
-  DRAIN(e);
-  std::vector<int> hn((size_t)e->N);
-  int rc = copy_out(e, hn.data(), e->nstep, (size_t)e->N * 4);
+  ENTER(e, time, "mre_get_time: null", DRAIN_FIRST);
+  std::vector<int> hn;
+  int rc = fetch(e, e->nstep, (size_t)e->N, hn);
   if (rc) return rc;
   for (int i = 0; i < e->N; i++) time[i] = (double)hn[i] * (double)e->hM.opt_rec.timestep;
   return MRE_OK;
 }
 extern "C" int mre_get_ctrl(mre_env* e, float* ctrl) {
-  if (!e || !ctrl) return fail(MRE_ERR_ARG, "mre_get_ctrl: null");
-  DRAIN(e);
+  ENTER(e, ctrl, "mre_get_ctrl: null", DRAIN_FIRST);
   return copy_out(e, ctrl, e->ctrl, (size_t)e->N * NU * 4);
 }
 
 extern "C" int mre_get_state(mre_env* e, float* qpos, float* qvel) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   int rc = MRE_OK;
   if (qpos) rc = copy_out(e, qpos, e->qpos, (size_t)e->N * NQP * 4);
   if (!rc && qvel) rc = copy_out(e, qvel, e->qvel, (size_t)e->N * NVP * 4);
@@ -492,10 +516,8 @@ extern "C" int mre_get_state(mre_env* e, float* qpos, float* qvel) {
 // final (qpos, qvel, status) rows of every env, packed on the device: out[N][MRE_FINAL_W] (device pointer), enqueued on
 // the handle's stream -- the local block of the end-of-rollout all_gather (bench.py, distributed.py)
 extern "C" int mre_pack_final_state(mre_env* e, float* out) {
-  if (!e || !out) return fail(MRE_ERR_ARG, "null");
+  ENTER(e, out, "null", DRAIN_FIRST);
   if (!is_device_ptr(out)) return fail(MRE_ERR_ARG, "mre_pack_final_state: out must be a device pointer");
-  DRAIN(e);
-  HIPCHK(hipSetDevice(e->device));
   mre_launch_pack_final(e->N, e->qpos, e->qvel, e->status, out, e->stream);
   HIPCHK(hipGetLastError());
   return MRE_OK;
@@ -503,12 +525,10 @@ extern "C" int mre_pack_final_state(mre_env* e, float* out) {
 // mj_jacSite / mj_fullM / qfrc_bias of the arm on the current state, packed per env by k_arm_dynamics: out[N][MRE_DYN_W]
 // (device pointer), enqueued on the handle's stream.  One kernel for every handle: the rows do not depend on the solver.
 extern "C" int mre_get_arm_dynamics(mre_env* e, int site, float* out) {
-  if (!e || !out) return fail(MRE_ERR_ARG, "mre_get_arm_dynamics: null");
+  ENTER(e, out, "mre_get_arm_dynamics: null", DRAIN_FIRST);
   if (site != 0 && site != 1) return fail(MRE_ERR_ARG, "mre_get_arm_dynamics: site must be 0 (controller site) or 1 (pinch site)");
   if (!is_device_ptr(out) || ((uintptr_t)out & 7))
     return fail(MRE_ERR_ARG, "mre_get_arm_dynamics: out must be a device pointer, 8-byte aligned");
-  DRAIN(e);
-  HIPCHK(hipSetDevice(e->device));
   DynArgs a;
   memset(&a, 0, sizeof(a));
   a.M = e->dM; a.N = e->N; a.qpos = e->qpos; a.qvel = e->qvel; a.qfine = e->qfine; a.nprops = e->nprops;
@@ -518,36 +538,20 @@ extern "C" int mre_get_arm_dynamics(mre_env* e, int site, float* out) {
   return MRE_OK;
 }
 extern "C" int mre_set_warmstart(mre_env* e, const float* w) {
-  if (!e || !w) return fail(MRE_ERR_ARG, "null");
-  DRAIN(e);
+  ENTER(e, w, "null", DRAIN_FIRST);
   return copy_in(e, e->qacc_ws, w, (size_t)e->N * NVP * 4);
 }
 extern "C" int mre_get_warmstart(mre_env* e, float* w) {
-  if (!e || !w) return fail(MRE_ERR_ARG, "null");
-  DRAIN(e);
+  ENTER(e, w, "null", DRAIN_FIRST);
   return copy_out(e, w, e->qacc_ws, (size_t)e->N * NVP * 4);
 }
 extern "C" int mre_set_ctrl(mre_env* e, const float* ctrl) {
-  if (!e || !ctrl) return fail(MRE_ERR_ARG, "null");
-  DRAIN(e);
+  ENTER(e, ctrl, "null", DRAIN_FIRST);
   return copy_in(e, e->ctrl, ctrl, (size_t)e->N * NU * 4);
 }
 
-static void fill_args(mre_env* e, StepArgs& a) {
-  memset(&a, 0, sizeof(a));
-  a.M = e->dM; a.N = e->N; a.seq_stride = e->N;
-  a.qpos = e->qpos; a.qvel = e->qvel; a.qacc_ws = e->qacc_ws; a.ctrl = e->ctrl; a.qfine = e->qfine;
-  a.nprops = e->nprops; a.prop_size = e->prop_size;
-  a.control_steps = 1; a.mode = CTRL_HELD; a.flags = e->base_flags;
-  a.osc = e->d_osc_env ? e->d_osc_env : e->d_osc; a.osc_stride = e->d_osc_env ? 1 : 0;
-  a.osc_target = e->osc_target; a.grip_closed = e->grip_closed;
-  a.sites = e->sites; a.status = e->status; a.stats = e->stats; a.nstep = e->nstep;
-  a.env_order = e->use_order ? e->order : (e->have_auto_order ? e->auto_order : nullptr);
-  a.trace = e->trace; a.trace_nenv = e->trace_nenv; a.trace_max = e->trace_max; a.trace_base = e->trace_pos;
-}
-
 extern "C" int mre_step(mre_env* e, int nsubsteps, unsigned flags) {
-  if (!e || nsubsteps < 0) return fail(MRE_ERR_ARG, "mre_step: bad argument");
+  ENTER(e, nsubsteps >= 0, "mre_step: bad argument", LEAVE_PENDING);
   StepArgs a;
   fill_args(e, a);
   a.nsteps = nsubsteps; a.flags |= flags;
@@ -563,7 +567,7 @@ extern "C" int mre_step(mre_env* e, int nsubsteps, unsigned flags) {
 // ticks_per_launch <= 0 or >= nticks: ONE launch for the whole sequence (mre_rollout).
 extern "C" int mre_rollout_ticks(mre_env* e, const float* ctrl_seq, int nticks, int control_steps, unsigned flags,
                                  int ticks_per_launch) {
-  if (!e || !ctrl_seq || nticks < 0 || control_steps < 1) return fail(MRE_ERR_ARG, "mre_rollout: bad argument");
+  ENTER(e, ctrl_seq && nticks >= 0 && control_steps >= 1, "mre_rollout: bad argument", LEAVE_PENDING);
   if (!is_device_ptr(ctrl_seq)) return fail(MRE_ERR_ARG, "mre_rollout: ctrl_seq must be a device pointer");
   int per = (ticks_per_launch <= 0 || ticks_per_launch > nticks) ? nticks : ticks_per_launch;
   bool allow_queue = ticks_per_launch >= 2;   // the caller's cut into launches of several ticks: queue launches where they apply
@@ -586,7 +590,8 @@ extern "C" int mre_rollout_ticks(mre_env* e, const float* ctrl_seq, int nticks, 
     const size_t n = (size_t)nticks * (size_t)e->N * NU;
     if (n > e->seq_cap) {
       DRAIN_PENDING(e);
-      for (float*& p : e->seq_copy) { if (p) HIPCHK(hipFree(p)); p = nullptr; HIPCHK(hipMalloc(&p, n * 4)); }
+      e->seq_cap = 0;
+      for (float*& p : e->seq_copy) { release(e, &p); int rc = alloc_dev(e, &p, n * 4); if (rc) return rc; }
       e->seq_cap = n;
     }
     float* dst = e->seq_copy[e->seq_calls++ % (unsigned)(mre_env::RING + 1)];
@@ -613,8 +618,7 @@ extern "C" int mre_rollout(mre_env* e, const float* ctrl_seq, int nticks, int co
 }
 
 extern "C" int mre_set_trace(mre_env* e, float* out, int nenv, int max_steps) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   if (out) {
     if (!is_device_ptr(out)) return fail(MRE_ERR_ARG, "mre_set_trace: trace buffer must be a device pointer");
     if (nenv <= 0 || nenv > e->N || max_steps <= 0) return fail(MRE_ERR_ARG, "mre_set_trace: bad sizes");
@@ -625,8 +629,7 @@ extern "C" int mre_set_trace(mre_env* e, float* out, int nenv, int max_steps) {
 
 extern "C" int mre_osc_configure(mre_env* e, const float* gains, const float* null_q, const float* thr,
                                  int pinv_always) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   if (gains) {
     e->osc.kp_pos = gains[0]; e->osc.kd_pos = gains[1]; e->osc.kp_ori = gains[2];
     e->osc.kd_ori = gains[3]; e->osc.kp_null = gains[4]; e->osc.kd_null = gains[5];
@@ -636,15 +639,14 @@ extern "C" int mre_osc_configure(mre_env* e, const float* gains, const float* nu
   e->osc.pinv_always = pinv_always;
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipMemcpy(e->d_osc, &e->osc, sizeof(OscConfig), hipMemcpyHostToDevice));
-  if (e->d_osc_env) { (void)hipFree(e->d_osc_env); e->d_osc_env = nullptr; }
+  release(e, &e->d_osc_env);
   return MRE_OK;
 }
 
 // per-env controller parameters (a population of gain sets, one per env): any NULL array keeps the
 // shared configuration's values; mre_osc_configure afterwards returns to one shared set
 extern "C" int mre_osc_configure_env(mre_env* e, const float* gains, const float* null_q, const float* thr) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   const size_t N = (size_t)e->N;
   std::vector<OscConfig> h(N, e->osc);
   for (size_t i = 0; i < N; i++) {
@@ -658,36 +660,28 @@ extern "C" int mre_osc_configure_env(mre_env* e, const float* gains, const float
     if (thr) { h[i].pos_thresh = thr[2 * i]; h[i].ori_thresh = thr[2 * i + 1]; }
   }
   HIPCHK(hipStreamSynchronize(e->stream));
-  if (!e->d_osc_env) HIPCHK(hipMalloc(&e->d_osc_env, N * sizeof(OscConfig)));
+  int rc = alloc_dev(e, &e->d_osc_env, N * sizeof(OscConfig));
+  if (rc) return rc;
   HIPCHK(hipMemcpy(e->d_osc_env, h.data(), N * sizeof(OscConfig), hipMemcpyHostToDevice));
   return MRE_OK;
 }
 
 extern "C" int mre_gripper_set(mre_env* e, const uint8_t* closed) {
-  if (!e || !closed) return fail(MRE_ERR_ARG, "null");
-  DRAIN(e);
+  ENTER(e, closed, "null", DRAIN_FIRST);
   return copy_in(e, e->grip_closed, closed, (size_t)e->N);
 }
 
 extern "C" int mre_get_sites(mre_env* e, float* tcp_pos, float* eef_pose, float* prop_pose) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
-  HIPCHK(hipSetDevice(e->device));
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   // refresh site poses for the current state (0 physics steps = kinematics only)
   StepArgs a;
   fill_args(e, a);
-  a.nsteps = 0; a.trace = nullptr;
-  step_kernels(e->solver).step(&a, e->stream);
-  HIPCHK(hipGetLastError());
-  const size_t N = (size_t)e->N;
-  std::vector<float> hs(N * 16), hq;
-  int rc = copy_out(e, hs.data(), e->sites, N * 64);
+  int rc = zero_step(e, a);
   if (rc) return rc;
-  if (prop_pose) {
-    hq.resize(N * NQP);
-    rc = copy_out(e, hq.data(), e->qpos, N * NQP * 4);
-    if (rc) return rc;
-  }
+  const size_t N = (size_t)e->N;
+  std::vector<float> hs, hq;
+  if ((rc = fetch(e, e->sites, N * 16, hs))) return rc;
+  if (prop_pose && (rc = fetch(e, e->qpos, N * NQP, hq))) return rc;
   // gather on the host into temporaries, then copy to the (host or device) destinations
   std::vector<float> t3(N * 3), t7(N * 7), tp(N * NPROP * 7);
   for (size_t i = 0; i < N; i++) {
@@ -697,59 +691,43 @@ extern "C" int mre_get_sites(mre_env* e, float* tcp_pos, float* eef_pose, float*
       for (int p = 0; p < NPROP; p++)
         for (int k = 0; k < 7; k++) tp[(i * NPROP + p) * 7 + k] = hq[i * NQP + NRV + 7 * p + k];
   }
-  if (tcp_pos) { rc = copy_out(e, tcp_pos, t3.data(), N * 12); if (rc) return rc; }
-  if (eef_pose) { rc = copy_out(e, eef_pose, t7.data(), N * 28); if (rc) return rc; }
-  if (prop_pose) { rc = copy_out(e, prop_pose, tp.data(), N * NPROP * 28); if (rc) return rc; }
+  if (tcp_pos && (rc = store(e, tcp_pos, t3))) return rc;
+  if (eef_pose && (rc = store(e, eef_pose, t7))) return rc;
+  if (prop_pose && (rc = store(e, prop_pose, tp))) return rc;
   return MRE_OK;
 }
 
 extern "C" int mre_get_status(mre_env* e, uint32_t* status) {
-  if (!e || !status) return fail(MRE_ERR_ARG, "null");
-  DRAIN(e);
+  ENTER(e, status, "null", DRAIN_FIRST);
   return copy_out(e, status, e->status, (size_t)e->N * 4);
 }
 extern "C" int mre_get_solver_stats(mre_env* e, int32_t* stats) {
-  if (!e || !stats) return fail(MRE_ERR_ARG, "null");
-  DRAIN(e);
+  ENTER(e, stats, "null", DRAIN_FIRST);
   return copy_out(e, stats, e->stats, (size_t)e->N * 16);
 }
 
 extern "C" int mre_osc_set_target(mre_env* e, const float* pos, const float* quat, const float* vel,
                                   const float* angvel, const uint8_t* mask) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   // small host-side merge: targets persist per env, NULL keeps the old value
   const size_t N = (size_t)e->N;
-  std::vector<float> t(N * 16);
-  int rc = copy_out(e, t.data(), e->osc_target, N * 64);
-  if (rc) return rc;
   std::vector<float> hp, hq, hv, hw;
   std::vector<uint8_t> hm;
-  auto fetch = [&](const float* src, int w, std::vector<float>& dst) -> int {
-    if (!src) return MRE_OK;
-    dst.resize(N * w);
-    return copy_out(e, dst.data(), src, N * w * 4);
-  };
-  if ((rc = fetch(pos, 3, hp)) || (rc = fetch(quat, 4, hq)) || (rc = fetch(vel, 3, hv)) ||
-      (rc = fetch(angvel, 3, hw)))
+  int rc;
+  if ((pos && (rc = fetch(e, pos, N * 3, hp))) || (quat && (rc = fetch(e, quat, N * 4, hq))) ||
+      (vel && (rc = fetch(e, vel, N * 3, hv))) || (angvel && (rc = fetch(e, angvel, N * 3, hw))) ||
+      (mask && (rc = fetch(e, mask, N, hm))))
     return rc;
-  if (mask) { hm.resize(N); rc = copy_out(e, hm.data(), mask, N); if (rc) return rc; }
-  for (size_t i = 0; i < N; i++) {
-    if (mask && !hm[i]) continue;
-    float* r = &t[i * 16];
+  return patch_rows(e, e->osc_target, 16, [&](size_t i) { return !mask || hm[i]; }, [&](size_t i, float* r) {
     if (pos) for (int k = 0; k < 3; k++) r[k] = hp[i * 3 + k];
     if (quat) for (int k = 0; k < 4; k++) r[3 + k] = hq[i * 4 + k];
     if (vel) for (int k = 0; k < 3; k++) r[7 + k] = hv[i * 3 + k];
     if (angvel) for (int k = 0; k < 3; k++) r[10 + k] = hw[i * 3 + k];
-  }
-  rc = copy_in(e, e->osc_target, t.data(), N * 64);
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(e->stream));  // t goes out of scope
-  return MRE_OK;
+  });
 }
 
 extern "C" int mre_run_controller(mre_env* e, int nticks, int control_steps, uint8_t* converged_out) {
-  if (!e || nticks < 0 || control_steps < 1) return fail(MRE_ERR_ARG, "mre_run_controller: bad argument");
+  ENTER(e, nticks >= 0 && control_steps >= 1, "mre_run_controller: bad argument", LEAVE_PENDING);
   // One scripted phase is 400 ticks (2000 steps).  With the capacity fallback an overflow costs a
   // re-run of the launch it happened in, so the call is cut into launches of RUN_CHUNK ticks: the
   // state round-trips through HBM exactly, the converged flag carries over (F_CONV_CONTINUE) and
@@ -768,7 +746,7 @@ extern "C" int mre_run_controller(mre_env* e, int nticks, int control_steps, uin
   }
   if (chunk <= 0 || chunk > nticks) chunk = nticks;
   if (queue && chunk > QUEUE_TICKS_MAX) chunk = QUEUE_TICKS_MAX;
-  DRAIN(e);
+  DRAIN(e);   // (after the cut is chosen: the drain updates what the cut is chosen by)
   if (nticks > 0 && e->converged) HIPCHK(hipMemsetAsync(e->converged, 0, (size_t)e->N, e->stream));
   int t0 = 0;
   do {
@@ -793,37 +771,34 @@ extern "C" int mre_run_controller(mre_env* e, int nticks, int control_steps, uin
 // OSC.compute_control_output() + MinMax.compute_control_output() on the current state, no stepping
 // (models/robot_arm.py:71-73): tau[N][7] arm torques, grip[N] gripper command (either may be NULL)
 extern "C" int mre_osc_compute(mre_env* e, float* tau, float* grip) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   StepArgs a;
   fill_args(e, a);
-  a.nsteps = 0; a.control_steps = 1; a.mode = CTRL_OSC; a.flags |= F_OSC_EVAL; a.trace = nullptr;
-  HIPCHK(hipSetDevice(e->device));
-  step_kernels(e->solver).step(&a, e->stream);
-  HIPCHK(hipGetLastError());
-  const size_t N = (size_t)e->N;
-  std::vector<float> h(N * NU);
-  int rc = copy_out(e, h.data(), e->ctrl, N * NU * 4);
+  a.mode = CTRL_OSC; a.flags |= F_OSC_EVAL;
+  int rc = zero_step(e, a);
   if (rc) return rc;
+  const size_t N = (size_t)e->N;
+  std::vector<float> h;
+  if ((rc = fetch(e, e->ctrl, N * NU, h))) return rc;
   std::vector<float> ht(N * 7), hg(N);
   for (size_t i = 0; i < N; i++) {
     for (int k = 0; k < 7; k++) ht[i * 7 + k] = h[i * NU + k];
     hg[i] = h[i * NU + 7];
   }
-  // (copy_out synchronises: the staging vectors die with this frame)
-  if (tau) { rc = copy_out(e, tau, ht.data(), N * 7 * 4); if (rc) return rc; }
-  if (grip) { rc = copy_out(e, grip, hg.data(), N * 4); if (rc) return rc; }
+  if (tau && (rc = store(e, tau, ht))) return rc;
+  if (grip && (rc = store(e, grip, hg))) return rc;
   return MRE_OK;
 }
 
 // ---- device buffers and launch arguments of k_pose_search (mre_place_props, mre_prop_place, mre_sort_colours)
 static int search_buffers(mre_env* e) {
-  if (e->ps_attempts) return MRE_OK;
   const size_t N = (size_t)e->N;
-  HIPCHK(hipMalloc(&e->ps_attempts, N * 4)); HIPCHK(hipMalloc(&e->ps_prop, N * 4));
-  HIPCHK(hipMalloc(&e->ps_tick, N * 4)); HIPCHK(hipMalloc(&e->ps_which, N * 4));
-  HIPCHK(hipMalloc(&e->ps_bounds, N * 6 * 8)); HIPCHK(hipMalloc(&e->ps_pose, N * 7 * 8));
-  HIPCHK(hipMalloc(&e->ps_zones, N * NPROP * 4 * 8)); HIPCHK(hipMalloc(&e->ps_pick, N * 7 * 8));
+  int rc;
+  if ((rc = alloc_dev(e, &e->ps_attempts, N * 4)) || (rc = alloc_dev(e, &e->ps_prop, N * 4)) ||
+      (rc = alloc_dev(e, &e->ps_tick, N * 4)) || (rc = alloc_dev(e, &e->ps_which, N * 4)) ||
+      (rc = alloc_dev(e, &e->ps_bounds, N * 6 * 8)) || (rc = alloc_dev(e, &e->ps_pose, N * 7 * 8)) ||
+      (rc = alloc_dev(e, &e->ps_zones, N * NPROP * 4 * 8)) || (rc = alloc_dev(e, &e->ps_pick, N * 7 * 8)))
+    return rc;
   return MRE_OK;
 }
 static void fill_search(mre_env* e, SearchArgs& sa) {
@@ -838,51 +813,44 @@ static void fill_search(mre_env* e, SearchArgs& sa) {
 // [count, (geom1, geom2, dist) x CONTACT_EXPORT]; count < 0: the list was cut at -count.
 static int detect_contacts(mre_env* e, const uint8_t* dmask, bool full = false, bool active_only = false) {
   const size_t N = (size_t)e->N, row = 1 + 3 * CONTACT_EXPORT;
-  if (!e->contacts) HIPCHK(hipMalloc(&e->contacts, N * row * 4));
-  if (full && !e->contacts_full) HIPCHK(hipMalloc(&e->contacts_full, N * CONTACT_EXPORT * 12 * 4));
+  int rc = alloc_dev(e, &e->contacts, N * row * 4);
+  if (!rc && full) rc = alloc_dev(e, &e->contacts_full, N * CONTACT_EXPORT * 12 * 4);
+  if (rc) return rc;
   StepArgs a;
   fill_args(e, a);
-  a.nsteps = 0; a.flags |= F_DETECT | (active_only ? F_DETECT_ACTIVE : 0u); a.trace = nullptr; a.env_mask = dmask;
+  a.flags |= F_DETECT | (active_only ? F_DETECT_ACTIVE : 0u); a.env_mask = dmask;
   a.contacts = e->contacts; a.contacts_full = full ? e->contacts_full : nullptr;
   a.sites = nullptr; a.geoms = nullptr;
-  step_kernels(e->solver).step(&a, e->stream);
-  HIPCHK(hipGetLastError());
-  return MRE_OK;
+  return zero_step(e, a);
 }
 
 extern "C" int mre_get_contacts(mre_env* e, int32_t* count, float* contacts) {
-  if (!e || !count || !contacts) return fail(MRE_ERR_ARG, "mre_get_contacts: null");
-  DRAIN(e);
-  HIPCHK(hipSetDevice(e->device));
+  ENTER(e, count && contacts, "mre_get_contacts: null", DRAIN_FIRST);
   int rc = detect_contacts(e, nullptr);
   if (rc) return rc;
   const size_t N = (size_t)e->N, row = 1 + 3 * CONTACT_EXPORT;
-  std::vector<float> h(N * row);
-  rc = copy_out(e, h.data(), e->contacts, h.size() * 4);
-  if (rc) return rc;
+  std::vector<float> h;
+  if ((rc = fetch(e, e->contacts, N * row, h))) return rc;
   std::vector<int32_t> hc(N);
   std::vector<float> ho(N * 3 * CONTACT_EXPORT);
   for (size_t i = 0; i < N; i++) {
     hc[i] = (int32_t)h[i * row];
     memcpy(&ho[i * 3 * CONTACT_EXPORT], &h[i * row + 1], 3 * CONTACT_EXPORT * 4);
   }
-  if ((rc = copy_out(e, count, hc.data(), N * 4))) return rc;
-  return copy_out(e, contacts, ho.data(), ho.size() * 4);
+  if ((rc = store(e, count, hc))) return rc;
+  return store(e, contacts, ho);
 }
 
 // The whole mjContact record of the same zero-step launch: rows of 15 = pos[3], frame[9], dist, geom1, geom2.
 // active_only: the launch runs collide(.., detect = false), the call every step makes -- its early-outs see
 // margin - gap, not margin, so this list is what the next solve would be given, not a filtered copy of the other.
 extern "C" int mre_get_contacts_full(mre_env* e, int active_only, int32_t* count, float* contacts) {
-  if (!e || !count || !contacts) return fail(MRE_ERR_ARG, "mre_get_contacts_full: null");
-  DRAIN(e);
-  HIPCHK(hipSetDevice(e->device));
+  ENTER(e, count && contacts, "mre_get_contacts_full: null", DRAIN_FIRST);
   int rc = detect_contacts(e, nullptr, true, active_only != 0);
   if (rc) return rc;
   const size_t N = (size_t)e->N, row = 1 + 3 * CONTACT_EXPORT, W = 15;
-  std::vector<float> h(N * row), hf(N * CONTACT_EXPORT * 12);
-  if ((rc = copy_out(e, h.data(), e->contacts, h.size() * 4))) return rc;
-  if ((rc = copy_out(e, hf.data(), e->contacts_full, hf.size() * 4))) return rc;
+  std::vector<float> h, hf;
+  if ((rc = fetch(e, e->contacts, N * row, h)) || (rc = fetch(e, e->contacts_full, N * CONTACT_EXPORT * 12, hf))) return rc;
   std::vector<int32_t> hc(N);
   std::vector<float> ho(N * CONTACT_EXPORT * W, 0.f);
   for (size_t i = 0; i < N; i++) {
@@ -897,8 +865,115 @@ extern "C" int mre_get_contacts_full(mre_env* e, int active_only, int32_t* count
       o[12] = t[2]; o[13] = t[0]; o[14] = t[1];
     }
   }
-  if ((rc = copy_out(e, count, hc.data(), N * 4))) return rc;
-  return copy_out(e, contacts, ho.data(), ho.size() * 4);
+  if ((rc = store(e, count, hc))) return rc;
+  return store(e, contacts, ho);
+}
+
+// ---- PropPlacer.__call__, in parts.  What one mre_place_props call keeps on the host between them:
+struct Placement {
+  std::vector<uint8_t> todo;     // envs whose cubes are (still) to be placed
+  std::vector<uint8_t> failed;   // no pose within max_attempts for one of the env's cubes
+  std::vector<int> nprops;       // cubes per env
+  std::vector<int> clock;        // nstep of every env when the current round began
+  bool any_todo() const { return std::any_of(todo.begin(), todo.end(), [](uint8_t t) { return t != 0; }); }
+};
+
+// A round begins: the clock is noted, the cubes of the envs to place go to their parking poses (float32 values: the
+// low-order words of the cubes' poses and velocities are zero) and, from the second round on, come to rest.
+static int place_park(mre_env* e, Placement& P, int round) {
+  const auto todo = [&](size_t i) { return P.todo[i] != 0; };
+  int rc = fetch(e, e->nstep, (size_t)e->N, P.clock);
+  if (rc) return rc;
+  rc = patch_rows(e, e->qpos, NQP, todo, [&](size_t, float* row) {
+    for (int p = 0; p < NPROP; p++) {
+      float* q = row + NRV + 7 * p;
+      for (int k = 0; k < 3; k++) q[k] = e->hM.park_pos[p][k];
+      q[3] = 1.f; q[4] = q[5] = q[6] = 0.f;
+    }
+  });
+  if (!rc) rc = store(e, e->mask, P.todo);
+  if (!rc) rc = patch_rows(e, e->qfine, QFINE_ROW, todo, [](size_t, float* row) { for (int k = QFINE_CUBE_Q; k < QFINE_ROW; k++) row[k] = 0.f; });
+  if (!rc && round > 0)   // a second try starts from rest
+    rc = patch_rows(e, e->qvel, NVP, todo, [](size_t, float* row) { for (int k = NRV; k < NVP; k++) row[k] = 0.f; });
+  return rc;
+}
+
+// one search launch per prop index: every env that still needs prop p runs its own attempt loop on
+// the device (k_pose_search) and writes the accepted pose into its qpos row
+static int place_search(mre_env* e, Placement& P, int round, uint64_t seed, const float* ws_min, const float* ws_max, int max_attempts) {
+  const size_t N = (size_t)e->N;
+  std::vector<int> att;
+  for (int p = 0; p < NPROP; p++) {
+    SearchArgs sa;
+    fill_search(e, sa);
+    sa.env_mask = e->mask; sa.seed = seed; sa.fixed_prop = p;
+    for (int k = 0; k < 3; k++) { sa.shared_bounds[k] = ws_min[k]; sa.shared_bounds[3 + k] = ws_max[k]; }
+    sa.tick0 = ((long long)round * NPROP + p) * (long long)max_attempts;
+    sa.max_attempts = max_attempts; sa.yaw_mode = 1; sa.max_dist = INFINITY; sa.commit = 1;
+    mre_launch_pose_search(&sa, e->stream);
+    HIPCHK(hipGetLastError());
+    int rc = fetch(e, e->ps_attempts, N, att);
+    if (rc) return rc;
+    bool dropped = false;
+    for (size_t i = 0; i < N; i++)
+      if (P.todo[i] && p < P.nprops[i] && att[i] <= 0) { P.failed[i] = 1; P.todo[i] = 0; dropped = true; }
+    // (_REJECTION_SAMPLING_FAILED is an exception of ONE env in the reference: here that env is flagged
+    //  MRE_ST_PLACEMENT_FAILED, its remaining cubes stay parked, and the other envs carry on)
+    if (dropped && (rc = store(e, e->mask, P.todo))) return rc;
+  }
+  return MRE_OK;
+}
+
+// The physics settles with the robot frozen, every env leaving by itself; the envs that came to rest are done.
+// *settled_now: how many did.
+static int place_settle(mre_env* e, Placement& P, int round, int settle_steps, int* settled_now) {
+  const size_t N = (size_t)e->N;
+  StepArgs a;
+  fill_args(e, a);
+  a.trace = nullptr;
+  // _max_settle_physics_time = 2 s; min time = settle_steps * dt (0.3 s in the reference)
+  a.nsteps = (int)std::lround(2.0 / e->hM.opt_rec.timestep);
+  if (a.nsteps < settle_steps) a.nsteps = settle_steps;
+  a.flags |= F_FREEZE_ROBOT | F_SETTLE_EXIT; a.env_mask = e->mask;
+  a.settle_steps = e->settle_steps; a.min_settle_steps = settle_steps;
+  const bool prof = e->profiling;
+  e->profiling = false;  // setup, not a control tick
+  int rc = launch_step(e, a, /*settle=*/true);
+  e->profiling = prof;
+  if (rc) return rc;
+  std::vector<int> hs;
+  if ((rc = fetch(e, e->settle_steps, N, hs))) return rc;
+  if (getenv("MRE_DEBUG_PLACE")) {
+    int nt = 0, ns = 0;
+    for (size_t i = 0; i < N; i++) if (P.todo[i]) { nt++; ns += hs[i] >= 0; }
+    fprintf(stderr, "mre_place_props round %d: %d envs placed, %d settled\n", round, nt, ns);
+  }
+  *settled_now = 0;
+  for (size_t i = 0; i < N; i++) {
+    if (!P.todo[i]) continue;
+    const int n = hs[i] < 0 ? -hs[i] : hs[i];
+    if (n > e->last_settle_max) e->last_settle_max = n;
+    if (hs[i] >= 0) { P.todo[i] = 0; (*settled_now)++; }               // settled
+  }
+  return MRE_OK;
+}
+
+// `physics.data.time = original_time` after EVERY failed attempt, the last one included
+// (prop_initializer.py:240-258): the clock goes back for every env that did not settle in this round
+static int place_rewind(mre_env* e, const Placement& P) {
+  if (!P.any_todo()) return MRE_OK;
+  return patch_rows(e, e->nstep, 1, [&](size_t i) { return P.todo[i] != 0; }, [&](size_t i, int* n) { *n = P.clock[i]; });
+}
+
+// status: envs that never settled (the reference logs _SETTLING_PHYSICS_FAILED and goes on), envs without a pose
+static int place_flag(mre_env* e, const Placement& P, bool settling) {
+  const auto flagged = [&](size_t i) { return P.failed[i] || (settling && P.todo[i]); };
+  bool any = false;
+  for (size_t i = 0; i < (size_t)e->N; i++) any = any || flagged(i);
+  if (!any) return MRE_OK;
+  return patch_rows(e, e->status, 1, flagged, [&](size_t i, uint32_t* st) {
+    *st |= P.failed[i] ? MRE_ST_PLACEMENT_FAILED : MRE_ST_NOT_SETTLED;
+  });
 }
 
 // ---- PropPlacer.__call__ (environment/prop_initializer.py:164-283), batched.
@@ -914,142 +989,42 @@ extern "C" int mre_get_contacts_full(mre_env* e, int active_only, int32_t* count
 // `settle_steps` steps (:240-258), at most 2 s; envs that never settle get MRE_ST_NOT_SETTLED.
 extern "C" int mre_place_props(mre_env* e, const uint8_t* mask, uint64_t seed, const float* ws_min,
                                const float* ws_max, int max_attempts, int settle_steps) {
-  if (!e || !ws_min || !ws_max || max_attempts < 1) return fail(MRE_ERR_ARG, "mre_place_props: bad argument");
-  DRAIN(e);
+  ENTER(e, ws_min && ws_max && max_attempts >= 1, "mre_place_props: bad argument", DRAIN_FIRST);
   const size_t N = (size_t)e->N;
-  std::vector<uint8_t> hm(N, 1);
+  Placement P;
+  P.todo.assign(N, 1);
+  P.failed.assign(N, 0);
   int rc;
-  if (mask) { rc = copy_out(e, hm.data(), mask, N); if (rc) return rc; }
-  std::vector<int> np(N);
-  if ((rc = copy_out(e, np.data(), e->nprops, N * 4))) return rc;
-  double lo[3], hi[3];
-  for (int k = 0; k < 3; k++) { lo[k] = ws_min[k]; hi[k] = ws_max[k]; }
-  if ((rc = search_buffers(e))) return rc;
-  if (settle_steps > 0 && !e->settle_steps) HIPCHK(hipMalloc(&e->settle_steps, N * 4));
-  if (settle_steps > 0) HIPCHK(hipMemsetAsync(e->settle_steps, 0, N * 4, e->stream));
-  std::vector<int> att(N), hs(N), nst(N);
-  std::vector<uint32_t> st(N);
-  std::vector<float> qp(N * NQP);
-  std::vector<uint8_t> todo = hm;      // envs whose cubes are (still) to be placed
-  std::vector<uint8_t> failed(N, 0);   // no pose within max_attempts for one of the env's cubes
+  if (mask && (rc = fetch(e, mask, N, P.todo))) return rc;
+  if ((rc = fetch(e, e->nprops, N, P.nprops)) || (rc = search_buffers(e))) return rc;
+  if (settle_steps > 0) {
+    if ((rc = alloc_dev(e, &e->settle_steps, N * 4))) return rc;
+    HIPCHK(hipMemsetAsync(e->settle_steps, 0, N * 4, e->stream));
+  }
   e->last_settle_max = 0;
   // PropPlacer.place_and_settle (environment/prop_initializer.py:240-258): place, settle with the robot frozen,
   // and place AGAIN the envs whose cubes are still moving after max_settle_physics_time -- up to
   // max_settle_physics_attempts (10) times, per env (the other envs keep what they have)
   const int max_settle_attempts = settle_steps > 0 ? 10 : 1;
-  for (int round = 0; round < max_settle_attempts; round++) {
-    bool any = false;
-    for (size_t i = 0; i < N; i++) any = any || todo[i];
-    if (!any) break;
-    if ((rc = copy_out(e, qp.data(), e->qpos, qp.size() * 4)) || (rc = copy_out(e, nst.data(), e->nstep, N * 4))) return rc;
-    // props that are about to be placed start from their parking pose
-    for (size_t i = 0; i < N; i++)
-      if (todo[i])
-        for (int p = 0; p < NPROP; p++) {
-          float* q = &qp[i * NQP + NRV + 7 * p];
-          for (int k = 0; k < 3; k++) q[k] = e->hM.park_pos[p][k];
-          q[3] = 1.f; q[4] = q[5] = q[6] = 0.f;
-        }
-    if ((rc = copy_in(e, e->qpos, qp.data(), qp.size() * 4)) || (rc = copy_in(e, e->mask, todo.data(), N))) return rc;
-    {   // the parked poses and the velocities written here are float32 values: their low-order words are zero
-      std::vector<float> hf(N * QFINE_ROW);
-      if ((rc = copy_out(e, hf.data(), e->qfine, hf.size() * 4))) return rc;
-      for (size_t i = 0; i < N; i++)
-        if (todo[i]) for (int k = QFINE_CUBE_Q; k < QFINE_ROW; k++) hf[i * QFINE_ROW + k] = 0.f;
-      if ((rc = copy_in(e, e->qfine, hf.data(), hf.size() * 4))) return rc;
-    }
-    if (round > 0) {   // a second try starts from rest
-      std::vector<float> z(N * NVP, 0.f), qv(N * NVP);
-      if ((rc = copy_out(e, qv.data(), e->qvel, qv.size() * 4))) return rc;
-      for (size_t i = 0; i < N; i++)
-        if (todo[i]) for (int k = NRV; k < NVP; k++) qv[i * NVP + k] = 0.f;
-      if ((rc = copy_in(e, e->qvel, qv.data(), qv.size() * 4))) return rc;
-      HIPCHK(hipStreamSynchronize(e->stream));
-    }
-    // one search launch per prop index: every env that still needs prop p runs its own attempt loop on
-    // the device (k_pose_search) and writes the accepted pose into its qpos row
-    for (int p = 0; p < NPROP; p++) {
-      SearchArgs sa;
-      fill_search(e, sa);
-      sa.env_mask = e->mask; sa.seed = seed; sa.fixed_prop = p;
-      for (int k = 0; k < 3; k++) { sa.shared_bounds[k] = lo[k]; sa.shared_bounds[3 + k] = hi[k]; }
-      sa.tick0 = ((long long)round * NPROP + p) * (long long)max_attempts;
-      sa.max_attempts = max_attempts; sa.yaw_mode = 1; sa.max_dist = INFINITY; sa.commit = 1;
-      mre_launch_pose_search(&sa, e->stream);
-      HIPCHK(hipGetLastError());
-      if ((rc = copy_out(e, att.data(), e->ps_attempts, N * 4))) return rc;
-      bool dropped = false;
-      for (size_t i = 0; i < N; i++)
-        if (todo[i] && p < np[i] && att[i] <= 0) { failed[i] = 1; todo[i] = 0; dropped = true; }
-      // (_REJECTION_SAMPLING_FAILED is an exception of ONE env in the reference: here that env is flagged
-      //  MRE_ST_PLACEMENT_FAILED, its remaining cubes stay parked, and the other envs carry on)
-      if (dropped && (rc = copy_in(e, e->mask, todo.data(), N))) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(e->stream));
+  for (int round = 0; round < max_settle_attempts && P.any_todo(); round++) {
+    if ((rc = place_park(e, P, round)) || (rc = place_search(e, P, round, seed, ws_min, ws_max, max_attempts))) return rc;
     if (settle_steps <= 0) break;
-    StepArgs a;
-    fill_args(e, a);
-    a.trace = nullptr;
-    // _max_settle_physics_time = 2 s; min time = settle_steps * dt (0.3 s in the reference)
-    a.nsteps = (int)std::lround(2.0 / e->hM.opt_rec.timestep);
-    if (a.nsteps < settle_steps) a.nsteps = settle_steps;
-    a.flags |= F_FREEZE_ROBOT | F_SETTLE_EXIT; a.env_mask = e->mask;
-    a.settle_steps = e->settle_steps; a.min_settle_steps = settle_steps;
-    const bool prof = e->profiling;
-    e->profiling = false;  // setup, not a control tick
-    rc = launch_step(e, a, /*settle=*/true);
-    e->profiling = prof;
-    if (rc) return rc;
-    if ((rc = copy_out(e, hs.data(), e->settle_steps, N * 4))) return rc;
-    if (getenv("MRE_DEBUG_PLACE")) {
-      int nt = 0, ns = 0;
-      for (size_t i = 0; i < N; i++) if (todo[i]) { nt++; ns += hs[i] >= 0; }
-      fprintf(stderr, "mre_place_props round %d: %d envs placed, %d settled\n", round, nt, ns);
-    }
     int settled_now = 0;
-    for (size_t i = 0; i < N; i++) {
-      if (!todo[i]) continue;
-      const int n = hs[i] < 0 ? -hs[i] : hs[i];
-      if (n > e->last_settle_max) e->last_settle_max = n;
-      if (hs[i] >= 0) { todo[i] = 0; settled_now++; }               // settled
-    }
+    if ((rc = place_settle(e, P, round, settle_steps, &settled_now))) return rc;
     // a round in which NO env came to rest is not bad luck of a placement but the solver: PGS at 100 sweeps leaves a
     // friction creep of 1e-3 rad/s on resting cubes that never passes the velocity test (all 4096 envs of the bench,
     // in every one of ten rounds; with Newton all settle in the first).  Placing again cannot help: stop, flag them
     // (only where that diagnosis can hold: PGS, a batch large enough that "none of them" is not chance, first round;
     //  a lone env keeps its ten attempts like the reference's)
     const bool give_up = settled_now == 0 && round == 0 && N >= 64 && e->solver != MRE_SOLVER_NEWTON;
-    bool left = false;
-    for (size_t i = 0; i < N; i++) left = left || todo[i];
-    if (left) {
-      // `physics.data.time = original_time` after EVERY failed attempt, the last one included
-      // (prop_initializer.py:240-258): the clock goes back for every env that did not settle in this round
-      std::vector<int> now(N);
-      if ((rc = copy_out(e, now.data(), e->nstep, N * 4))) return rc;
-      for (size_t i = 0; i < N; i++) if (todo[i]) now[i] = nst[i];
-      if ((rc = copy_in(e, e->nstep, now.data(), N * 4))) return rc;
-      HIPCHK(hipStreamSynchronize(e->stream));
-    }
+    if ((rc = place_rewind(e, P))) return rc;
     if (give_up) break;
   }
-  // status: envs that never settled (the reference logs _SETTLING_PHYSICS_FAILED and goes on), envs without a pose
-  bool flag = false;
-  for (size_t i = 0; i < N; i++) flag = flag || failed[i] || (settle_steps > 0 && todo[i]);
-  if (flag) {
-    if ((rc = copy_out(e, st.data(), e->status, N * 4))) return rc;
-    for (size_t i = 0; i < N; i++) {
-      if (failed[i]) st[i] |= MRE_ST_PLACEMENT_FAILED;
-      else if (settle_steps > 0 && todo[i]) st[i] |= MRE_ST_NOT_SETTLED;
-    }
-    if ((rc = copy_in(e, e->status, st.data(), N * 4))) return rc;
-    HIPCHK(hipStreamSynchronize(e->stream));
-  }
-  return MRE_OK;
+  return place_flag(e, P, settle_steps > 0);
 }
 
 extern "C" int mre_get_settle_steps(mre_env* e, int32_t* steps) {
-  if (!e || !steps) return fail(MRE_ERR_ARG, "mre_get_settle_steps: null");
-  DRAIN(e);
+  ENTER(e, steps, "mre_get_settle_steps: null", DRAIN_FIRST);
   if (!e->settle_steps) return fail(MRE_ERR_ARG, "mre_get_settle_steps: no settle has run");
   return copy_out(e, steps, e->settle_steps, (size_t)e->N * 4);
 }
@@ -1062,10 +1037,7 @@ extern "C" int mre_get_settle_steps(mre_env* e, int32_t* steps) {
 // < 0 = no pose within max_attempts (the reference raises "Failed to find collision free place pose.").
 extern "C" int mre_prop_place(mre_env* e, uint64_t seed, const int32_t* prop, const double* bounds, const int32_t* tick,
                               int max_attempts, float max_dist, double* pose, int32_t* attempts) {
-  if (!e || !prop || !bounds || !tick || !pose || !attempts || max_attempts < 1)
-    return fail(MRE_ERR_ARG, "mre_prop_place: bad argument");
-  DRAIN(e);
-  HIPCHK(hipSetDevice(e->device));
+  ENTER(e, prop && bounds && tick && pose && attempts && max_attempts >= 1, "mre_prop_place: bad argument", DRAIN_FIRST);
   const size_t N = (size_t)e->N;
   int rc = search_buffers(e);
   if (rc) return rc;
@@ -1093,17 +1065,15 @@ extern "C" int mre_prop_place(mre_env* e, uint64_t seed, const int32_t* prop, co
 extern "C" int mre_sort_colours(mre_env* e, uint64_t seed, const int32_t* call_counts, const double* zones,
                                 int max_attempts, float max_dist, int32_t* which, double* pick, double* place,
                                 int32_t* attempts) {
-  if (!e || !call_counts || !zones || !which || !pick || !place || !attempts || max_attempts < 1)
-    return fail(MRE_ERR_ARG, "mre_sort_colours: bad argument");
-  DRAIN(e);
-  HIPCHK(hipSetDevice(e->device));
+  ENTER(e, call_counts && zones && which && pick && place && attempts && max_attempts >= 1, "mre_sort_colours: bad argument",
+        DRAIN_FIRST);
   const size_t N = (size_t)e->N;
   int rc = search_buffers(e);
   if (rc) return rc;
-  std::vector<int32_t> ticks(N);
-  if ((rc = copy_out(e, ticks.data(), call_counts, N * 4))) return rc;
+  std::vector<int32_t> ticks;
+  if ((rc = fetch(e, call_counts, N, ticks))) return rc;
   for (size_t i = 0; i < N; i++) ticks[i] *= 10000;   // MAX_PLACE_ATTEMPTS draws reserved per call
-  if ((rc = copy_in(e, e->ps_tick, ticks.data(), N * 4)) || (rc = copy_in(e, e->ps_zones, zones, N * NPROP * 32))) return rc;
+  if ((rc = store(e, e->ps_tick, ticks)) || (rc = copy_in(e, e->ps_zones, zones, N * NPROP * 32))) return rc;
   SortArgs so;
   so.M = e->dM; so.N = e->N; so.qpos = e->qpos; so.nprops = e->nprops; so.zones = e->ps_zones; so.place_z = 0.4;
   so.which = e->ps_which; so.pick = e->ps_pick; so.bounds = e->ps_bounds;
@@ -1128,45 +1098,36 @@ extern "C" int mre_sort_colours(mre_env* e, uint64_t seed, const int32_t* call_c
 // info[i] = {overflow flag (-1: env was not part of the launch), max contacts | duration << 16 (s_memtime
 // ticks >> 10), max constraint rows, max robot rows | max cube-cube contacts << 16}.
 extern "C" int mre_get_launch_info(mre_env* e, int32_t* info) {
-  if (!e || !info) return fail(MRE_ERR_ARG, "mre_get_launch_info: null");
-  DRAIN(e);
-  HIPCHK(hipSetDevice(e->device));
+  ENTER(e, info, "mre_get_launch_info: null", DRAIN_FIRST);
   HIPCHK(hipStreamSynchronize(e->stream));
   return copy_out(e, info, e->h_info_last, (size_t)e->N * 16);
 }
 
 extern "C" int mre_set_env_ids(mre_env* e, const long long* ids) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   if (ids) e->env_ids.assign(ids, ids + e->N); else e->env_ids.clear();
-  if (e->d_env_ids) { HIPCHK(hipFree(e->d_env_ids)); e->d_env_ids = nullptr; }
-  if (ids) {
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMalloc(&e->d_env_ids, (size_t)e->N * 8));
-    return copy_in(e, e->d_env_ids, e->env_ids.data(), (size_t)e->N * 8);
-  }
-  return MRE_OK;
+  release(e, &e->d_env_ids);
+  if (!ids) return MRE_OK;
+  int rc = alloc_dev(e, &e->d_env_ids, (size_t)e->N * 8);
+  return rc ? rc : copy_in(e, e->d_env_ids, e->env_ids.data(), (size_t)e->N * 8);   // (env_ids lives as long as the handle)
 }
 
 extern "C" int mre_set_env_id_offset(mre_env* e, long long offset) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   e->env_ids.clear();
-  if (e->d_env_ids) { (void)hipFree(e->d_env_ids); e->d_env_ids = nullptr; }
+  release(e, &e->d_env_ids);
   e->env_id_offset = offset;
   return MRE_OK;
 }
 
 extern "C" int mre_profile_enable(mre_env* e, int on) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   e->profiling = on != 0;
   e->events_used = 0;
   return MRE_OK;
 }
 extern "C" int mre_profile_read(mre_env* e, float* total_ms, int* launches) {
-  if (!e || !total_ms || !launches) return fail(MRE_ERR_ARG, "null");
-  DRAIN(e);
+  ENTER(e, total_ms && launches, "null", DRAIN_FIRST);
   HIPCHK(hipStreamSynchronize(e->stream));
   float tot = 0.f;
   for (size_t k = 0; k < e->events_used; k++) {
@@ -1180,8 +1141,7 @@ extern "C" int mre_profile_read(mre_env* e, float* total_ms, int* launches) {
 }
 
 extern "C" int mre_set_env_order(mre_env* e, const int32_t* order) {
-  if (!e) return fail(MRE_ERR_ARG, "null handle");
-  DRAIN(e);
+  ENTER(e, true, "null handle", DRAIN_FIRST);
   if (!order) { e->use_order = false; return MRE_OK; }
   int rc = copy_in(e, e->order, order, (size_t)e->N * 4);
   if (rc) return rc;

@@ -1,9 +1,11 @@
 // mre_env.h -- the handle behind the C ABI (struct mre_env) and what the two host units that work on it share: the
-// drain of pending launches that every entry point starts with, and the scheduler's four entry points (mre_sched.cpp);
-// error reporting comes with mre_host.h.  Private to csrc/: mre_api.cpp and mre_sched.cpp include it, nothing else does.
+// four functions through which a handle comes to own a buffer, an event or a stream, the drain of pending launches that
+// every entry point starts with, and the scheduler's three entry points (mre_sched.cpp); error reporting comes with
+// mre_host.h.  Private to csrc/: mre_api.cpp and mre_sched.cpp include it, nothing else does.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 #include <utility>
 #include <vector>
@@ -15,6 +17,14 @@
 
 struct mre_env {
   int N = 0, device = 0;
+  // Everything the handle has created on its device, recorded where it is created (alloc_dev, alloc_host, new_event,
+  // new_stream below): mre_destroy walks these four records and names no buffer, event or stream.  The members further
+  // down are views of them, for the code that launches.
+  struct Owned {
+    std::vector<void*> dev, host;   // hipMalloc / hipHostMalloc
+    std::vector<hipEvent_t> events;
+    std::vector<hipStream_t> streams;
+  } owned;
   hipStream_t stream = nullptr;
   mre::DevModel* dM = nullptr;
   mre::DevModel hM;
@@ -33,13 +43,13 @@ struct mre_env {
   int* stats = nullptr;
   mre::OscConfig osc;
   mre::OscConfig* d_osc = nullptr;
-  mre::OscConfig* d_osc_env = nullptr;
+  mre::OscConfig* d_osc_env = nullptr;   // [N] per-env controller parameters (mre_osc_configure_env) or null
   float* geoms = nullptr;        // [N][NG][16] geom poses for the renderer (allocated on first use)
   // cached image of the static geoms (ground, table) for the last camera: depth | rgb | seg
   float* bg_depth = nullptr; uint8_t* bg_rgb = nullptr; uint8_t* bg_seg = nullptr;
   float bg_key[16] = {0}; int bg_h = 0, bg_w = 0; bool bg_valid = false;
   uint8_t* prop_rgb = nullptr;   // [N][NPROP][3]
-  float geom_rgb[mre::NG][3];  // [N] per-env controller parameters (mre_osc_configure_env) or null
+  float geom_rgb[mre::NG][3];   // albedo of every geom but the cubes (mre_set_render_colours)
   float* trace = nullptr;
   int trace_nenv = 0, trace_max = 0, trace_pos = 0;
   long long env_id_offset = 0;
@@ -55,8 +65,8 @@ struct mre_env {
   // ---- capacity fallback (see launch_step): per-env kernel choice, pre-launch state copies
   bool fallback = true;
   unsigned base_flags = 0;    // StepFlags of every launch (F_CLIP_ALWAYS under MRE_NARROW_GENERIC=1, F_NW_ALL_TILES under MRE_NEWTON_GENERIC=1)
-  bool large_only = false;
-  bool compact_only = false;  // mre_set_fallback(0)  // mre_set_fallback(2): every env on the large kernel (reference run for the fallback)
+  bool large_only = false;    // mre_set_fallback(2): every env on the large kernel (reference run for the fallback)
+  bool compact_only = false;  // mre_set_fallback(0): every env on the compact kernel
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_order = nullptr;
   uint8_t *d_large = nullptr, *mask_r = nullptr;
@@ -196,14 +206,62 @@ struct mre_env {
 
 namespace mre {
 // ---- the launch scheduler (mre_sched.cpp)
-// the env groups, the queue state and their streams and events (from create_buffers / mre_destroy)
+// the env groups, the queue state and their streams and events (from create_buffers; the handle owns them)
 int sched_create(mre_env* e);
-void sched_destroy(mre_env* e);
 // One stepping launch of `a` over the batch: synchronous, pipelined over the env groups, or a queue launch.
 int launch_step(mre_env* e, const StepArgs& a, bool settle = false, bool pipeline_ok = true, bool allow_queue = false);
 // Complete every pending group launch: every entry point that reads or writes device state starts here.
 int drain(mre_env* e, bool api_call = false);
 }  // namespace mre
+
+// ---- What a handle owns.  Each of the four selects the handle's device first (the HIP current device is per thread, and
+// a caller with two handles may have moved it) and records what it made in mre_env::owned at once, so a failure half-way
+// through mre_create or a first use leaks nothing: mre_destroy releases exactly what exists.
+// A device buffer behind *p; a no-op when *p is set, so a buffer of first use is one call where it is needed.
+template <class T> int alloc_dev(mre_env* e, T** p, size_t bytes) {
+  if (*p) return MRE_OK;
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipMalloc((void**)p, bytes));
+  e->owned.dev.push_back(*p);
+  return MRE_OK;
+}
+// Pinned (hipHostMallocDefault) or mapped host memory; dev_alias: where the kernels see mapped bytes.
+template <class T> int alloc_host(mre_env* e, T** p, size_t bytes, unsigned flags, T** dev_alias = nullptr) {
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipHostMalloc((void**)p, bytes, flags));
+  e->owned.host.push_back(*p);
+  if (dev_alias) HIPCHK(hipHostGetDevicePointer((void**)dev_alias, *p, 0));
+  return MRE_OK;
+}
+inline int new_event(mre_env* e, hipEvent_t* ev, unsigned flags = hipEventDisableTiming) {
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipEventCreateWithFlags(ev, flags));
+  e->owned.events.push_back(*ev);
+  return MRE_OK;
+}
+// A non-blocking stream, of the default priority unless one is named.
+inline int new_stream(mre_env* e, hipStream_t* s, const int* priority = nullptr) {
+  HIPCHK(hipSetDevice(e->device));
+  if (priority) HIPCHK(hipStreamCreateWithPriority(s, hipStreamNonBlocking, *priority));
+  else HIPCHK(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+  e->owned.streams.push_back(*s);
+  return MRE_OK;
+}
+// A device buffer that is about to be replaced or dropped: freed, forgotten and nulled, so that whatever happens next
+// the member and the record agree.  The caller has completed the work that reads it.
+template <class T> void release(mre_env* e, T** p) {
+  if (!*p) return;
+  (void)hipFree(*p);
+  auto& v = e->owned.dev;
+  v.erase(std::remove(v.begin(), v.end(), (void*)*p), v.end());
+  *p = nullptr;
+}
+
+// Where the low-order word of coordinate k of a qpos row (k < NQ) / of a qvel row (k < NV) sits in the env's qfine row:
+// the robot's joints first, angles then velocities, then the cubes' poses, then their velocities.
+constexpr int qfine_of_q(int k) { return k < mre::NRV ? k : mre::QFINE_CUBE_Q + (k - mre::NRV); }
+constexpr int qfine_of_v(int k) { return k < mre::NRV ? mre::QFINE / 2 + k : mre::QFINE_CUBE_V + (k - mre::NRV); }
+
 #define DRAIN(e) do { int rc_ = mre::drain(e, true); if (rc_) return rc_; } while (0)
 #define DRAIN_PENDING(e) do { int rc_ = mre::drain(e, false); if (rc_) return rc_; } while (0)
 
@@ -213,7 +271,9 @@ inline int profile_events(mre_env* e, hipEvent_t* e0, hipEvent_t* e1) {
   if (!e->profiling) return MRE_OK;
   if (e->events_used == e->events.size()) {
     hipEvent_t x, y;
-    HIPCHK(hipEventCreate(&x)); HIPCHK(hipEventCreate(&y));
+    int rc = new_event(e, &x, hipEventDefault);   // (timing enabled)
+    if (!rc) rc = new_event(e, &y, hipEventDefault);
+    if (rc) return rc;
     e->events.emplace_back(x, y);
   }
   *e0 = e->events[e->events_used].first; *e1 = e->events[e->events_used].second;

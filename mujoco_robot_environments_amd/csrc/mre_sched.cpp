@@ -395,7 +395,17 @@ int mre::launch_step(mre_env* e, const StepArgs& a, bool settle, bool pipeline_o
   return MRE_OK;
 }
 
-// ------------------------------------------------------------------- set-up and release
+// ------------------------------------------------------------------- set-up (the release is mre_destroy's: the handle owns all of it)
+// a group's stream pair (the large kernel's at `pr2`), its fork / join events and one event per ring entry
+static int group_create(mre_env* e, mre_env::Group& G, int pr, int pr2) {
+  int rc;
+  if ((rc = new_stream(e, &G.st, &pr)) || (rc = new_stream(e, &G.st2, &pr2)) || (rc = new_event(e, &G.ev_fork)) ||
+      (rc = new_event(e, &G.ev_join)))
+    return rc;
+  for (auto& o : G.out) if ((rc = new_event(e, &o.ev_info))) return rc;
+  return MRE_OK;
+}
+
 int mre::sched_create(mre_env* e) {
   const int num_envs = e->N;
   const size_t N = (size_t)num_envs;
@@ -409,27 +419,23 @@ int mre::sched_create(mre_env* e) {
   if (ng > 8) ng = 8;
   if (const char* r = getenv("MRE_RING")) { e->ring = atoi(r); if (e->ring < 2) e->ring = 2; if (e->ring > mre_env::RING) e->ring = mre_env::RING; }
   while (ng > 1 && num_envs < min_envs * ng) ng--;
-  HIPCHK(hipHostMalloc((void**)&e->h_grp_order, mre_env::NSTAGE * N * 4, hipHostMallocMapped | hipHostMallocCoherent));
-  HIPCHK(hipHostGetDevicePointer((void**)&e->d_grp_order, e->h_grp_order, 0));
+  const unsigned mapped = hipHostMallocMapped | hipHostMallocCoherent;
+  int rc;
+  if ((rc = alloc_host(e, &e->h_grp_order, mre_env::NSTAGE * N * 4, mapped, &e->d_grp_order))) return rc;
   for (int k = 0; k < mre_env::NSTAGE; k++)
     for (int i = 0; i < num_envs; i++) e->h_grp_order[(size_t)k * N + i] = i;
-  HIPCHK(hipEventCreateWithFlags(&e->ev_main, hipEventDisableTiming));
+  if ((rc = new_event(e, &e->ev_main))) return rc;
   e->groups.resize(ng);
   // the queue's group: all envs, default stream priority
   auto& Q = e->qgroup;
   Q.lo = 0; Q.n = num_envs;
-  HIPCHK(hipHostMalloc((void**)&e->h_qgrp_order, mre_env::NSTAGE * N * 4, hipHostMallocMapped | hipHostMallocCoherent));
+  if ((rc = alloc_host(e, &e->h_qgrp_order, mre_env::NSTAGE * N * 4, mapped, &Q.d_order))) return rc;
   Q.h_order = e->h_qgrp_order;
-  HIPCHK(hipHostGetDevicePointer((void**)&Q.d_order, Q.h_order, 0));
   for (int k = 0; k < mre_env::NSTAGE; k++)
     for (int i = 0; i < num_envs; i++) Q.h_order[(size_t)k * N + i] = i;
   // the large kernel's waves on a stream of HIGHER priority: its own hardware queue (streams of one priority share a
   // few), and its few workgroups are placed before the compact kernel's 2048 fill the compute units' LDS
-  HIPCHK(hipStreamCreateWithPriority(&Q.st, hipStreamNonBlocking, least));
-  HIPCHK(hipStreamCreateWithPriority(&Q.st2, hipStreamNonBlocking, greatest));
-  HIPCHK(hipEventCreateWithFlags(&Q.ev_fork, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&Q.ev_join, hipEventDisableTiming));
-  for (auto& o : Q.out) HIPCHK(hipEventCreateWithFlags(&o.ev_info, hipEventDisableTiming));
+  if ((rc = group_create(e, Q, least, greatest))) return rc;
   if (const char* q = getenv("MRE_QUEUE")) e->queue_ok = atoi(q) != 0;
   if (const char* q = getenv("MRE_QUEUE_TICKS")) { const int v = atoi(q); if (v >= 2 && v <= QUEUE_TICKS_MAX) e->queue_ticks = v; }
   if (e->queue_run_ticks > e->queue_ticks) e->queue_run_ticks = e->queue_ticks;
@@ -445,12 +451,14 @@ int mre::sched_create(mre_env* e) {
   if (const char* q = getenv("MRE_QUEUE_SPARE_LARGE")) { const int v = atoi(q); if (v >= 0) e->queue_spare_large = v; }
   e->queue_large_waves_max = 2 * prop.multiProcessorCount;
   if (const char* q = getenv("MRE_QUEUE_LSHARDS")) { const int v = atoi(q); if (v >= 1 && v <= QUEUE_LSHARDS_MAX) e->queue_lshards = v; }
-  HIPCHK(hipMalloc(&e->q_ws, ((2 * (size_t)(QUEUE_SHARDS_MAX + QUEUE_LSHARDS_MAX) * QUEUE_TICKS_MAX + 16 + 4 * N +
-                               (size_t)QUEUE_TICKS_MAX * (2 * N + QUEUE_SHARDS_MAX + QUEUE_LSHARDS_MAX)) * 4 + 15) / 16 * 16));
-  HIPCHK(hipMalloc(&e->q_gen, 64));
+  if ((rc = alloc_dev(e, &e->q_ws, ((2 * (size_t)(QUEUE_SHARDS_MAX + QUEUE_LSHARDS_MAX) * QUEUE_TICKS_MAX + 16 + 4 * N +
+                                     (size_t)QUEUE_TICKS_MAX * (2 * N + QUEUE_SHARDS_MAX + QUEUE_LSHARDS_MAX)) * 4 + 15) / 16 * 16)) ||
+      (rc = alloc_dev(e, &e->q_gen, 64)))
+    return rc;
   HIPCHK(hipMemsetAsync(e->q_gen, 0, 64, e->stream));
-  HIPCHK(hipHostMalloc((void**)&e->h_qlist, (size_t)(mre_env::RING + 1) * (N + 32) * 4, hipHostMallocDefault));
-  HIPCHK(hipHostMalloc((void**)&e->h_q_err, 64, hipHostMallocMapped | hipHostMallocCoherent));
+  if ((rc = alloc_host(e, &e->h_qlist, (size_t)(mre_env::RING + 1) * (N + 32) * 4, hipHostMallocDefault)) ||
+      (rc = alloc_host(e, &e->h_q_err, 64, mapped)))
+    return rc;
   *e->h_q_err = 0;
   for (int g = 0; g < ng; g++) {
     auto& G = e->groups[g];
@@ -466,30 +474,7 @@ int mre::sched_create(mre_env* e) {
     if (const char* map = getenv("MRE_GROUP_PRIO_MAP")) {
       if ((int)strlen(map) > g && map[g] >= '0' && map[g] <= '9') { pr = greatest + (map[g] - '0'); if (pr > least) pr = least; }
     }
-    HIPCHK(hipStreamCreateWithPriority(&G.st, hipStreamNonBlocking, pr));
-    HIPCHK(hipStreamCreateWithPriority(&G.st2, hipStreamNonBlocking, pr));
-    HIPCHK(hipEventCreateWithFlags(&G.ev_fork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&G.ev_join, hipEventDisableTiming));
-    for (auto& o : G.out) HIPCHK(hipEventCreateWithFlags(&o.ev_info, hipEventDisableTiming));
+    if ((rc = group_create(e, G, pr, pr))) return rc;
   }
   return MRE_OK;
-}
-
-void mre::sched_destroy(mre_env* e) {
-  auto free_group = [](mre_env::Group& G) {
-    if (G.st) { (void)hipStreamSynchronize(G.st); (void)hipStreamDestroy(G.st); }
-    if (G.st2) { (void)hipStreamSynchronize(G.st2); (void)hipStreamDestroy(G.st2); }
-    if (G.ev_fork) (void)hipEventDestroy(G.ev_fork);
-    if (G.ev_join) (void)hipEventDestroy(G.ev_join);
-    for (auto& O : G.out) if (O.ev_info) (void)hipEventDestroy(O.ev_info);
-  };
-  for (auto& G : e->groups) free_group(G);
-  free_group(e->qgroup);
-  if (e->q_ws) (void)hipFree(e->q_ws);
-  if (e->q_gen) (void)hipFree(e->q_gen);
-  if (e->h_q_err) (void)hipHostFree(e->h_q_err);
-  if (e->h_qlist) (void)hipHostFree(e->h_qlist);
-  if (e->h_qgrp_order) (void)hipHostFree(e->h_qgrp_order);
-  if (e->ev_main) (void)hipEventDestroy(e->ev_main);
-  if (e->h_grp_order) (void)hipHostFree(e->h_grp_order);
 }
