@@ -36,7 +36,7 @@ class BatchedLasaDrawEnv(BatchedArmTaskEnv):
     def move_to_draw_target(self, target_position, target_velocity):
         """tasks/lasa_draw.py:326-349; returns (qpos [N, 7], qvel [N, 7], ctrl [N, 7])."""
         pos = np.asarray(target_position, np.float64) + np.array([0.0, 0.0, self.TARGET_OFFSET])
-        self._osc_tick(pos, self.mocap_quat, np.asarray(target_velocity, np.float64))
+        self._osc_tick(pos, self.mocap_quat, np.asarray(target_velocity, np.float64), self.TICK_STEPS)
         qpos, qvel = self._physics.get_state()
         tau = self._physics.ctrl()[:, :7]
         return qpos[:, :7].astype(np.float64), qvel[:, :7].astype(np.float64), tau.astype(np.float64)
@@ -49,9 +49,8 @@ class BatchedLasaDrawEnv(BatchedArmTaskEnv):
         c = np.zeros((self.num_envs, 8), np.float32)
         c[:, :7] = np.asarray(target_position, np.float32)
         self._physics.set_control(c)
-        self._physics.step(5)
-        for _ in range(5):
-            self._robot.time += self._robot.timestep
+        self._physics.step(self.TICK_STEPS)
+        self._advance_clock(self.TICK_STEPS)
         return self._physics.qpos()[:, :7].astype(np.float64)
 
 
