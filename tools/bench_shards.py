@@ -123,7 +123,7 @@ def _shard_bytes(directory: str, episodes=None):
         for _, length, _ in recs:
             if episodes is not None and count >= episodes:
                 return total, count
-            total += 12 + length + 4
+            total += D.record_bytes(length)
             count += 1
     return total, count
 
